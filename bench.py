@@ -2,6 +2,8 @@
 """Headline benchmark: clips/sec forward of Video ProtoASNet on synthetic echo batches (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full      # + everything beyond the headline (see below)
+    python bench.py ... --dump-outputs DIR                       # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus N ...          # no launcher: this process starts N fresh rank processes itself (see spawn_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -10,11 +12,18 @@ over one batch of 32 clips of (3,16,224,224), inputs resident in HBM, weights ra
 activations with fp32 accumulation.  Multi-GPU: every rank runs its own batch (weak scaling, no data-path collective:
 clips are independent units); timing = barrier + synchronize on both sides, MAX over ranks.
 
-The JSON line also carries
-  roofline     -- the dominant kernel instance (by device time): algorithmic bytes per launch / its average launch
-                  duration, measured with HIP events recorded on the launch stream inside the timed region (around its launches in
-                  three of the timed steps: first, middle, last -- bracketing every launch of every step cost the job 1.5-2 %);
-  cpu_baseline -- the CPU oracle (restated reference op sequence, torch fp32, all host cores) on a bounded sample.
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config).  With --full the line also carries
+  roofline     -- the dominant kernel family (by device time): algorithmic bytes per launch / its average launch duration,
+                  measured with HIP events recorded on the launch stream around its launches in three steps run launch by launch
+                  AFTER the timed region; kernel_ms_per_step / roofline_instances from two probe steps before it;
+  trunk_algorithmic -- the step's byte and FLOP counts against the HBM peak (this build's launches and the per-layer count);
+  cpu_baseline -- the CPU oracle (restated reference op sequence, torch fp32, up to 16 host threads) on a bounded sample, and
+                  parity_observed: the timed batch's own clips checked against it;
+  secondary    -- the other BASELINE configs, each measured after the headline (N = 1, the default workload only).
+
+--dump-outputs DIR writes what the last timed step returned (logits, similarity, occurrence_map) as DIR/<name>.npy in float32;
+inputs and weights are seeded, so the same arguments give the same inputs in every run and two builds compare output for output.
 """
 import argparse
 import json
@@ -32,6 +41,7 @@ import torch  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md: ~6.3 TB/s achievable; measured on this pool's boxes: copy 4.7-5.3 TB/s, fill 6.9 -- DESIGN.md section 6)
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.0}  # dense peaks, same guide (never the 2:1-sparsity figures)
 MFMA_BF16_PEAK_TFLOPS = 2500.0
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def spawn_ranks(gpus: int, script: str, argv) -> None:
@@ -117,6 +127,11 @@ def parse():
                     "config 5, config 4 push sweep, config 3 train step: reported under the \"secondary\" key, N = 1 only)")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal for the CPU test suite: ranks, process group, "
                     "barriers, MAX-over-ranks timing and the JSON line, with NO device work (the metric says so)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: roofline and "
+                    "per-kernel split (--no-roofline skips them), byte accounting, CPU baseline + parity against it (--cpu-clips 0 skips it), "
+                    "the secondary BASELINE configs (--no-secondary skips them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32; "
+                    f"a fixed, seeded sample of each array if they exceed {DUMP_BUDGET_BYTES >> 20} MB together)")
     return ap.parse_args()
 
 
@@ -126,6 +141,8 @@ def main():
     if args.dry_run:
         return dry_run(args)
     if args.mode == "train":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: forward mode only")
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import train_bench
 
@@ -144,7 +161,7 @@ def main():
                img_size=args.size)
     model = model_builder.build(cfg)
     synth.load_synth(model)
-    cpu_state = {k: v.clone() for k, v in model.state_dict().items()} if (rank == 0 and world == 1 and args.cpu_clips) else None
+    cpu_state = {k: v.clone() for k, v in model.state_dict().items()} if (args.full and rank == 0 and world == 1 and args.cpu_clips) else None
     model = model.to(dev).eval()
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     model.set_compute_dtype(dtype)
@@ -178,13 +195,13 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up (also compiles the plan) + pick the dominant kernel instance by device time -----------------
+    # ---- warm-up (also compiles the plan) + (--full) pick the dominant kernel instance by device time -----------------
     for _ in range(max(args.warmup, 1)):
         out = step()
     torch.cuda.synchronize()
     plan = trunk.plan_for(x)
     dominant, timers = None, None
-    if not args.no_roofline:
+    if (args.full or args.per_op) and not args.no_roofline:
         probe = {i: [] for i in range(len(plan.ops))}
         trunk._timers = probe
         for _ in range(2):
@@ -229,6 +246,8 @@ def main():
         out = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before anything else runs the model: the graph's outputs are static buffers
+        _dump_outputs(args.dump_outputs, dict(zip(("logits", "similarity", "occurrence_map"), out)))
     # roofline samples: three more steps of the same workload AFTER the timed region, launch by launch with HIP events around the
     # dominant kernel's launches on the launch stream (round 5: inside the region they were 15 % of the driver's 20-step line)
     if timers is not None:
@@ -262,7 +281,7 @@ def main():
                    "global_batch": args.batch * world, "parallelism": f"dp{world} (independent clips, no collective)",
                    "launch": "host enqueue per launch" if graphed is None else
                              ("hipGraph replay of the forward's launch list (one graph launch per step"
-                              + ("" if args.no_roofline else "; the 3 roofline-sample steps run AFTER the timed region, launch by launch with HIP events "
+                              + ("" if timers is None else "; the 3 roofline-sample steps run AFTER the timed region, launch by launch with HIP events "
                                                             "around the dominant kernel's launches") + ")"),
                    "tuning": _tuning_in_force()},
     }
@@ -330,16 +349,17 @@ def main():
     # its own inputs and outputs only).  "layerwise_bytes_per_clip" is SURVEY section 8(d)'s accounting -- every layer's input and output
     # once, norm / activation fused, residual read once -- i.e. the same plan compiled with every cross-layer fusion switched off; it does
     # not move when a fusion removes traffic, so it is the figure the throughput can be compared against across rounds.
-    layerwise = _layerwise_bytes(trunk, x, dtype)
-    result["trunk_algorithmic"] = {
-        "bytes_per_clip": int(total_bytes / args.batch), "flops_per_clip": int(total_flops / args.batch),
-        "hbm_frac_whole_step": round(total_bytes * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 4),
-        "layerwise_bytes_per_clip": int(layerwise / args.batch) if layerwise else None,
-        "hbm_frac_whole_step_layerwise": round(layerwise * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 4) if layerwise else None,
-        "arena_bytes": plan.arena_bytes,
-        "note": "bytes_per_clip counts what this build's launches move (fused launches skip their intermediates); layerwise_bytes_per_clip is the "
-                "per-layer count of SURVEY 8(d), constant across builds: compare rounds on hbm_frac_whole_step_layerwise",
-    }
+    if args.full:
+        layerwise = _layerwise_bytes(trunk, x, dtype)
+        result["trunk_algorithmic"] = {
+            "bytes_per_clip": int(total_bytes / args.batch), "flops_per_clip": int(total_flops / args.batch),
+            "hbm_frac_whole_step": round(total_bytes * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 4),
+            "layerwise_bytes_per_clip": int(layerwise / args.batch) if layerwise else None,
+            "hbm_frac_whole_step_layerwise": round(layerwise * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 4) if layerwise else None,
+            "arena_bytes": plan.arena_bytes,
+            "note": "bytes_per_clip counts what this build's launches move (fused launches skip their intermediates); layerwise_bytes_per_clip is the "
+                    "per-layer count of SURVEY 8(d), constant across builds: compare rounds on hbm_frac_whole_step_layerwise",
+        }
 
     # ---- CPU baseline: the oracle (restated reference op sequence) on a bounded sample of the same workload ---------
     if cpu_state is not None:
@@ -378,13 +398,29 @@ def main():
             "similarity_max_abs": round(err, 6), "logits_max_abs": round(err_l, 6),
             "gates": {"similarity": 1e-3, "logits": 2e-3, "where": "tests/test_gpu_models.py (BF16_SIM, BF16_LOGITS)"}}
     # ---- the other BASELINE configs, measured in this process AFTER the headline's timed region (the headline is untouched) ---------
-    if world == 1 and not args.no_secondary and args.arch == "x3d_s" and args.input == "clip3":
+    if args.full and world == 1 and not args.no_secondary and args.arch == "x3d_s" and args.input == "clip3":
         del model, trunk, plan, x, out
         torch.cuda.empty_cache()
         result["secondary"] = secondary(dev)
     print(json.dumps(result))
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def _dump_outputs(path: str, arrays: dict) -> None:
+    """``arrays`` (name -> device tensor) as ``path/<name>.npy`` in float32.  Above DUMP_BUDGET_BYTES together, each array is cut to a
+    fixed, seeded sample of its flattened elements (the same indices for the same shape in every run), in proportion to its size."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total, room = sum(a.nbytes for a in host.values()), DUMP_BUDGET_BYTES - 4096 * len(host)  # (room for the .npy headers)
+    for name, a in host.items():
+        if total > room:
+            keep = max(1, int(a.size * (room / total)))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _tuning_in_force():

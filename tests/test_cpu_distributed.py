@@ -241,3 +241,24 @@ def test_bench_needs_the_gpu_and_says_so():
         pytest.skip("GPU present")
     r, line = _run_bench(["--steps", "1", "--warmup", "1"])
     assert r.returncode != 0 and line is None
+
+
+def test_bench_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32; above the budget, a fixed sample of each array (same elements in every
+    run) that keeps all files together within it."""
+    import bench
+
+    small = {"logits": torch.randn(4, 3, dtype=torch.bfloat16), "similarity": torch.rand(4, 30)}
+    bench._dump_outputs(str(tmp_path / "small"), small)
+    for name, t in small.items():
+        a = np.load(tmp_path / "small" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy()), name
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 64 << 10)
+    big = {"similarity": torch.rand(8, 30), "occurrence_map": torch.rand(8, 30, 1, 4, 14, 14)}
+    for run in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / run), big)
+    assert sum(os.path.getsize(tmp_path / "a" / f"{name}.npy") for name in big) <= 64 << 10
+    for name, t in big.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < t.numel() and np.array_equal(a, b), name
+        assert np.isin(a, t.numpy().reshape(-1)).all(), name

@@ -2,19 +2,19 @@
 
 Every ``src/configs/*.yml`` sets ``pretrained: True`` (``:14-15``); the reference then reads ``./pretrained_models/<file>`` through
 ``model_zoo.load_url`` (resnet_features.py:8-18,243-247,314-319).  These tests put SYNTHETIC files with the published key layout there
-(nothing is copied from the reference; the YAML is read where it lies and skipped when the directory is absent, as on the GPU box).
+(nothing is copied from the reference).  The configs' ``model:`` sections and image sizes are stored in
+``tests/golden/reference_configs.json`` (``tests/golden/make_reference_configs.py`` extracts them from a reference checkout).
 """
-import glob
+import json
 import os
-import re
 
 import pytest
 import torch
-import yaml
 
+from conftest import GOLDEN
 from protoasnet_amd import backbones, model_builder, synth
 
-REF_CONFIGS = "/root/reference/src/configs"
+REF_CONFIGS = os.path.join(GOLDEN, "reference_configs.json")
 
 
 def _tv_r2plus1d_state():
@@ -34,16 +34,6 @@ def _tv_resnet18_state():
     return sd
 
 
-def _model_section(path):
-    """(``model:`` mapping, ``data.img_size``) of a reference config.  Baseline_ProtoPNet.yml does not parse as a whole (a stray comma in
-    its ``data:`` section, ``:68``), so the top-level ``model:`` block is cut out as text and parsed on its own."""
-    text = open(path).read()
-    m = re.search(r"^model:.*?\n(?=^\S)", text, flags=re.S | re.M)
-    model_config = yaml.safe_load(m.group(0))["model"]
-    img_size = int(re.search(r"^data:.*?^  img_size:\s*(\d+)", text, flags=re.S | re.M).group(1))
-    return model_config, img_size
-
-
 @pytest.fixture
 def pretrained_dir(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)  # the reference's model_dir is relative to the working directory
@@ -54,12 +44,11 @@ def pretrained_dir(tmp_path, monkeypatch):
     return d
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="reference configs not present on this box")
 def test_every_reference_config_builds_unchanged(pretrained_dir):
-    paths = sorted(glob.glob(os.path.join(REF_CONFIGS, "*.yml")))
-    assert len(paths) == 6
-    for path in paths:
-        model_config, img_size = _model_section(path)
+    configs = json.load(open(REF_CONFIGS))
+    assert len(configs) == 6
+    for entry in configs.values():
+        model_config, img_size = entry["model"], entry["img_size"]
         assert model_config["pretrained"] is True
         model_config.update({"img_size": img_size})  # base.py:37-42
         model = model_builder.build(model_config)

@@ -176,6 +176,34 @@ def test_headline_batch_of_32_vs_oracle():
         assert torch.equal(a, b)
 
 
+@pytest.mark.timeout(600)
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs on a small shape, twice with the same arguments: float32 logits / similarity / occurrence_map of the last timed
+    step, identical in both runs (seeded inputs and weights); a plain run's line carries the headline fields and none of --full's extras."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--frames", "4", "--size", "64", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True,
+                           timeout=540)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    line = lines[0]
+    assert line["metric"] == "clips/sec forward" and line["value"] > 0 and line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "bf16"
+    assert not {"roofline", "kernel_ms_per_step", "trunk_algorithmic", "cpu_baseline", "parity_observed", "secondary"} & set(line), sorted(line)
+    for name, lead in (("logits", (2, 3)), ("similarity", (2, 30)), ("occurrence_map", (2, 30))):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape[:2] == lead and np.isfinite(a).all(), (name, a.dtype, a.shape)
+        assert np.array_equal(a, b), name
+
+
 CFG_VIDEO_X3D_M = dict(CFG_VIDEO_X3D, base_architecture="x3d_m", prototype_shape="(60, 256, 1, 1, 1)", img_size=312)
 
 

@@ -8,8 +8,8 @@ CMD="python3 $R/bench.py --arch resnet2p1d_18 --batch 8 --frames 32 --size 112 -
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- $CMD > $O/stats.log 2>&1 || echo "stats pass failed"
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 cd $R
-python3 bench.py --arch resnet2p1d_18 --batch 8 --frames 32 --size 112 --steps 20 --warmup 5 --cpu-clips 0 --per-op $O/per_launch_table.txt > $O/bench.json 2> $O/bench.err
-python3 bench.py --arch resnet2p1d_18 --batch 32 --frames 16 --size 224 --steps 5 --warmup 2 --cpu-clips 0 --no-roofline > $O/bench_cfg2_shape.json 2>> $O/bench.err
+python3 bench.py --full --arch resnet2p1d_18 --batch 8 --frames 32 --size 112 --steps 20 --warmup 5 --cpu-clips 0 --per-op $O/per_launch_table.txt > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --arch resnet2p1d_18 --batch 32 --frames 16 --size 224 --steps 5 --warmup 2 --cpu-clips 0 --no-roofline > $O/bench_cfg2_shape.json 2>> $O/bench.err
 tail -1 $O/bench.json | cut -c1-300
 head -8 $O/kernel_stats.csv
 rm -rf $O/stats

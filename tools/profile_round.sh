@@ -14,7 +14,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv 
 cd $R
 python3 tools/pmc_traffic.py $(find $O/fetch -name "*counter_collection.csv" | head -1) $(find $O/write -name "*counter_collection.csv" | head -1) $TAG > $O/pmc_traffic.json
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
-python3 bench.py --steps 20 --warmup 5 --per-op $O/per_launch_table.txt > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --steps 20 --warmup 5 --per-op $O/per_launch_table.txt > $O/bench.json 2> $O/bench.err
 tail -1 $O/bench.json | cut -c1-400
 head -12 $O/kernel_stats.csv
 # the heavy raw traces stay on the box
