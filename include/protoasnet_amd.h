@@ -32,7 +32,8 @@ extern "C" {
 
 #define PASN_VERSION 100 /* round 1 */
 
-enum { PASN_F32 = 0, PASN_BF16 = 1, PASN_U8 = 2 /* input clips of the *_gray_fwd entry points only */ };
+enum { PASN_F32 = 0, PASN_BF16 = 1, PASN_U8 = 2 /* input clips of the *_gray_fwd entry points and pasn_clip_augment only */,
+       PASN_I32 = 3 /* pasn_clip_augment parameter tables only */ };
 enum { PASN_ACT_NONE = 0, PASN_ACT_RELU = 1, PASN_ACT_SIGMOID = 2, PASN_ACT_SWISH = 3, PASN_ACT_ABS = 4 };
 enum { PASN_OK = 0, PASN_ERR_ARG = 1, PASN_ERR_LAUNCH = 2, PASN_ERR_UNSUPPORTED = 3 };
 
@@ -568,6 +569,20 @@ int pasn_l2_head_bwd(const void* z, const float* protos, const float* fc_w, cons
  * (N,P,T',H',W') occurrence maps: N*P*T' planes).  bwd is the adjoint on fp32 (dx zeroed by the caller; fp32 atomics). */
 int pasn_affine_warp_fwd(const void* x, void* y, long planes, int H, int W, float angle_deg, float scale, int dtype, void* stream);
 int pasn_affine_warp_bwd(const float* dy, float* dx, long planes, int H, int W, float angle_deg, float scale, void* stream);
+
+/* The train-split augmentation and normalisation of the reference's dataset, on the device (as_dataloader.py:127-133 + 221-224,
+ * replacing torchvision's RandomResizedCropVideo(size=(Ho,Wo), scale=(min_crop_ratio, 1)), video_transforms.RandomRotateVideo(degrees)
+ * and bin_to_norm, which run per clip and frame on the host there).  One launch maps the single-channel batch x (N,1,T,H,W) or
+ * (N,1,H,W) (T = 1), in_dtype PASN_F32 / PASN_BF16 / PASN_U8, to y (N,1,T,Ho,Wo) in out_dtype PASN_F32 / PASN_BF16.  Per clip,
+ * params[n] = {i, j, h, w, cos t, sin t}: param_dtype PASN_F32 (six floats) or PASN_I32 (four int32, then cos / sin as fp32 bit patterns).
+ * Per output pixel, in the reference's order:
+ *   crop x[..., i:i+h, j:j+w] + F.interpolate(size=(Ho,Wo), bilinear, align_corners=False, no antialias);
+ *   torchvision F.rotate(t, NEAREST, expand=False, fill=0) of the Ho x Wo result (source index rounded half to even; outside -> 0);
+ *   (v * scale - mean) / std (scale 1/255 for uint8; mean 0.099, std 0.171, or 0 and 1 for an unnormalised clip).
+ * Identity parameters {0, 0, H, W, 1, 0} with Ho = H, Wo = W give (x * scale - mean) / std in fp32, bit for bit.  Crop indices outside
+ * the clip are clamped to its border (no out-of-bounds read). */
+int pasn_clip_augment(const void* x, void* y, const void* params, int N, int T, int H, int W, int Ho, int Wo, float scale, float mean,
+                      float stdev, int in_dtype, int out_dtype, int param_dtype, void* stream);
 
 /*
  * Training: all conv weights of a step packed from the live fp32 parameters into the layouts the forward kernels read, in ONE launch

@@ -9,7 +9,7 @@ import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_void_p
 
-F32, BF16, U8 = 0, 1, 2
+F32, BF16, U8, I32 = 0, 1, 2, 3
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "swish": 3, "abs": 4}
 
 # (PASN_LIB_PATH: another build of the same C-ABI library -- A/B runs of two commits on one GPU box, tools/ab_bench.sh)
@@ -128,6 +128,7 @@ SIGNATURES = {
     "pasn_l2_head_bwd": (c_int, [c_void_p] * 11 + [c_int] * 8 + [c_float, c_void_p]),
     "pasn_affine_warp_fwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_float, c_int, c_void_p]),
     "pasn_affine_warp_bwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_float, c_void_p]),
+    "pasn_clip_augment": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_float] * 3 + [c_int] * 3 + [c_void_p]),
     "pasn_push_ppnet_update": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
 }
 

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void first_conv_wgrad_kernel(const TIN* __rest
                                                                pasn_conv_desc d, int col_tiles, int rows_per_wave) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = lane & 31, k = lane >> 5;
-    const int cols = 3 * d.kh * d.kw;
+    const int cols = d.Cin * d.kh * d.kw;
     const int col_t = blockIdx.y % col_tiles, co_t = blockIdx.y / col_tiles;
     const int co = co_t * 32 + m, col = col_t * 32 + m;
     const bool a_ok = co < d.Cout_p, b_ok = col < cols;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void first_conv_wgrad_kernel(const TIN* __rest
             const int to = (int)(q % d.To), n = (int)(q / d.To);
             const int hi = ho * d.sh - d.ph + th, wi = wo * d.sw - d.pw + tw;
             const bool in = hi >= 0 && hi < d.Hi && wi >= 0 && wi < d.Wi;
-            const long off = in ? ((((long)n * 3 + ci) * d.Ti + to) * d.Hi + hi) * d.Wi + wi : 0;
+            const long off = in ? ((((long)n * d.Cin + ci) * d.Ti + to) * d.Hi + hi) * d.Wi + wi : 0;
             ra[u] = dy[rc * d.Cout_p + coc];
             rx[u] = x[off];
             ma[u] = (rok && a_ok) ? 1.0f : 0.0f;
@@ -308,7 +308,7 @@ extern "C" int pasn_conv3d_wgrad(const void* x, const void* dy, float* dw, const
 // gather costs one pass over the clip's windows instead of one scattered 2-byte load per MFMA operand element.
 template <typename TIN>
 __global__ __launch_bounds__(256) void first_conv_im2col_kernel(const TIN* __restrict__ x, __bf16* __restrict__ X, pasn_conv_desc d, int colp) {
-    const int groups = colp / 8, cols = 3 * d.kh * d.kw;
+    const int groups = colp / 8, cols = d.Cin * d.kh * d.kw;
     const long R = (long)d.N * d.To * d.Ho * d.Wo, total = R * groups;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int g = (int)(idx % groups);
@@ -325,50 +325,89 @@ __global__ __launch_bounds__(256) void first_conv_im2col_kernel(const TIN* __res
             const int ci = col / (d.kh * d.kw), r = (col / d.kw) % d.kh, sx = col % d.kw;
             const int hi = ho * d.sh - d.ph + r, wi = wo * d.sw - d.pw + sx;
             const bool ok = col < cols && hi >= 0 && hi < d.Hi && wi >= 0 && wi < d.Wi;
-            v[j] = ok ? (float)x[((((long)n * 3 + ci) * d.Ti + to) * d.Hi + hi) * d.Wi + wi] : 0.0f;
+            v[j] = ok ? (float)x[((((long)n * d.Cin + ci) * d.Ti + to) * d.Hi + hi) * d.Wi + wi] : 0.0f;
         }
         store8(X + row * colp + g * 8, v);
     }
 }
 
-extern "C" size_t pasn_first_conv_wgrad_workspace_bytes(const pasn_conv_desc* d, int dtype) {
-    if (!d || dtype != PASN_BF16 || tune("PASN_NO_FIRST_IM2COL")) return 0;
-    const int colp = (3 * d->kh * d->kw + 7) / 8 * 8;
+// grey clip (Cin = 1): the three input-channel slices of conv.weight see the same sum dy * x, computed once into [Cout][kh*kw] scratch and
+// written to all three slices here -- bitwise identical whatever order the atomics of the gradient kernel took
+__global__ __launch_bounds__(256) void first_conv_grey_expand_kernel(const float* __restrict__ g, float* __restrict__ dw, int Cout, int K) {
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < Cout * K; idx += gridDim.x * 256) {
+        const int co = idx / K, k = idx % K;
+        const float v = g[idx];
+#pragma unroll
+        for (int ci = 0; ci < 3; ++ci) dw[((long)co * 3 + ci) * K + k] += v;
+    }
+}
+
+static size_t first_im2col_bytes(const pasn_conv_desc* d, int dtype) {
+    if (dtype != PASN_BF16 || tune("PASN_NO_FIRST_IM2COL")) return 0;
+    const int colp = (d->Cin * d->kh * d->kw + 7) / 8 * 8;
     if (colp > 512) return 0;
     return (size_t)d->N * d->To * d->Ho * d->Wo * colp * sizeof(__bf16);
+}
+
+// the grey clip's [Cout][kh*kw] gradient scratch, first in the workspace (256-byte aligned, so the im2col after it stays aligned)
+static size_t first_grey_bytes(const pasn_conv_desc* d) {
+    return d->Cin == 1 ? ((size_t)d->Cout * d->kh * d->kw * sizeof(float) + 255) / 256 * 256 : 0;
+}
+
+extern "C" size_t pasn_first_conv_wgrad_workspace_bytes(const pasn_conv_desc* d, int dtype) {
+    if (!d) return 0;
+    const size_t im2col = first_im2col_bytes(d, dtype);
+    return im2col ? first_grey_bytes(d) + im2col : first_grey_bytes(d);
 }
 
 extern "C" int pasn_first_conv_wgrad(const void* x, const void* dy, float* dw, const pasn_conv_desc* d, int in_dtype, int dtype,
                                      void* ws, void* stream) {
     PASN_REQUIRE(x && dy && dw && d, "null pointer");
-    PASN_REQUIRE(d->kt == 1 && d->st == 1 && d->pt == 0 && d->Cin == 3, "first conv is (1,kh,kw) over 3 planar channels");
-    const int cols = 3 * d->kh * d->kw;
+    PASN_REQUIRE(d->kt == 1 && d->st == 1 && d->pt == 0 && (d->Cin == 3 || d->Cin == 1),
+                 "first conv is (1,kh,kw) over 3 planar channels (or the single channel of a grey clip)");
+    PASN_REQUIRE(d->Cin == 3 || ws, "a grey clip (Cin = 1) needs pasn_first_conv_wgrad_workspace_bytes of workspace");
+    const int cols = d->Cin * d->kh * d->kw;
     hipStream_t s = (hipStream_t)stream;
-    if (ws && pasn_first_conv_wgrad_workspace_bytes(d, dtype)) {
+    // where the [Cout][cols] gradient goes: dw itself, or (grey) the scratch that is then written to the three channel slices of dw
+    float* g = dw;
+    const size_t gb = first_grey_bytes(d);
+    if (gb) {
+        g = static_cast<float*>(ws);
+        if (hipMemsetAsync(g, 0, (size_t)d->Cout * cols * sizeof(float), s) != hipSuccess) return check_launch("first_conv_wgrad scratch");
+    }
+    auto finish = [&]() -> int {
+        if (gb) {
+            const int nb = std::max(1, std::min(1024, ceil_div((long)d->Cout * cols, 256)));
+            hipLaunchKernelGGL(first_conv_grey_expand_kernel, dim3(nb), dim3(256), 0, s, g, dw, d->Cout, cols);
+        }
+        return check_launch("first_conv_wgrad");
+    };
+    if (ws && first_im2col_bytes(d, dtype)) {
+        __bf16* X = reinterpret_cast<__bf16*>(static_cast<unsigned char*>(ws) + gb);
         const int colp = (cols + 7) / 8 * 8;
         const long R = (long)d->N * d->To * d->Ho * d->Wo, total = R * (colp / 8);
         const int nb = (int)std::min<long>((total + 255) / 256, 1 << 20);
         if (in_dtype == PASN_BF16)
-            hipLaunchKernelGGL(first_conv_im2col_kernel<__bf16>, dim3(nb), dim3(256), 0, s, (const __bf16*)x, (__bf16*)ws, *d, colp);
+            hipLaunchKernelGGL(first_conv_im2col_kernel<__bf16>, dim3(nb), dim3(256), 0, s, (const __bf16*)x, X, *d, colp);
         else
-            hipLaunchKernelGGL(first_conv_im2col_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, (__bf16*)ws, *d, colp);
-        pasn_conv_desc g = *d;  // the equivalent pointwise problem over the im2col rows
-        g.Ti = d->To; g.Hi = d->Ho; g.Wi = d->Wo;
-        g.Cin = cols; g.Cin_p = colp;
-        g.kt = g.kh = g.kw = 1; g.st = g.sh = g.sw = 1; g.pt = g.ph = g.pw = 0;
-        if (pw_wgrad_bf16(ws, dy, dw, g, s)) return check_launch("first_conv_wgrad");
+            hipLaunchKernelGGL(first_conv_im2col_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, X, *d, colp);
+        pasn_conv_desc pw = *d;  // the equivalent pointwise problem over the im2col rows
+        pw.Ti = d->To; pw.Hi = d->Ho; pw.Wi = d->Wo;
+        pw.Cin = cols; pw.Cin_p = colp;
+        pw.kt = pw.kh = pw.kw = 1; pw.st = pw.sh = pw.sw = 1; pw.pt = pw.ph = pw.pw = 0;
+        if (pw_wgrad_bf16(X, dy, g, pw, s)) return finish();
     }
     const int co_tiles = ceil_div(d->Cout, 32), col_tiles = ceil_div(cols, 32);
     const long R = (long)d->N * d->To * d->Ho * d->Wo;
     const int rpw = wgrad_rows_per_wave(R, co_tiles * col_tiles);
     const dim3 grid(ceil_div(R, (long)rpw * 4), co_tiles * col_tiles);
-#define FW(TI, T) hipLaunchKernelGGL((first_conv_wgrad_kernel<TI, T>), grid, dim3(256), 0, s, (const TI*)x, (const T*)dy, dw, *d, col_tiles, rpw)
+#define FW(TI, T) hipLaunchKernelGGL((first_conv_wgrad_kernel<TI, T>), grid, dim3(256), 0, s, (const TI*)x, (const T*)dy, g, *d, col_tiles, rpw)
     if (in_dtype == PASN_BF16 && dtype == PASN_BF16) FW(__bf16, __bf16);
     else if (in_dtype == PASN_F32 && dtype == PASN_BF16) FW(float, __bf16);
     else if (in_dtype == PASN_BF16) FW(__bf16, float);
     else FW(float, float);
 #undef FW
-    return check_launch("first_conv_wgrad");
+    return finish();
 }
 
 // 3x3x3, stride (1,2,2), pad 1 (the first block of every X3D stage): a thread owns a 2x2 input patch.  Even rows / columns

@@ -7,13 +7,22 @@ conv reads.  Here the clip stays SINGLE-channel (fp32, bf16 or uint8) until it i
 layer's loads (``HipTrunk.set_input_normalization``) and the channel expansion is folded into the first conv's weights (summed over
 the input channels: 9 spatial taps instead of 27 for the X3D stem) -- ``pasn_x3d_stem_gray_fwd`` / ``pasn_first_conv_gray_fwd``.
 
+Training takes the grey clip too: ``DeviceClipPipeline.normalized`` runs the train split's augmentation (torchvision's
+``RandomResizedCropVideo`` + the reference's ``RandomRotateVideo``, as_dataloader.py:127-133) and ``bin_to_norm`` in ONE launch
+(``pasn_clip_augment``, csrc/augment.hip) on per-clip parameters drawn here, on the host, from a private generator
+(``sample_augment_params``).  ``transform_time_dilation`` picks the frame window on the raw cine before the host resize, so it stays in
+the user's dataset.
+
 ``bin_to_norm`` / ``gray_to_gray3`` keep the reference's names and semantics for code that still wants the 3-channel tensor.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
+
+from . import _lib
 
 ECHO_MEAN, ECHO_STD = 0.099, 0.171  # as_dataloader.py:180-181
 
@@ -28,6 +37,52 @@ def bin_to_norm(in_tensor: torch.Tensor) -> torch.Tensor:
     return (in_tensor - ECHO_MEAN) / ECHO_STD
 
 
+class GreyInputError(ValueError, NotImplementedError):
+    """A grey clip the training pass (or ``DeviceClipPipeline.normalized``) refuses: uint8 pixels, or a clip that meets an input
+    normalisation left on the trunk by someone else.  A ``ValueError``; also a ``NotImplementedError``, which is what every grey clip in
+    train mode raised before the training pass accepted normalised ones, so callers that catch that keep catching these refusals."""
+
+
+def sample_augment_params(n: int, height: int, width: int, min_crop_ratio: float, rotate_degrees: float,
+                          generator: torch.Generator) -> torch.Tensor:
+    """Per-clip parameters of ``pasn_clip_augment``: float32 (n, 6) rows {i, j, h, w, cos t, sin t}.
+
+    The crop restates torchvision's ``RandomResizedCrop.get_params`` (scale (min_crop_ratio, 1), ratio (3/4, 4/3), log-uniform aspect,
+    10 attempts, then the central-crop fallback); the angle is uniform in [-rotate_degrees, rotate_degrees] (video_transforms.py:26).
+    Every draw comes from ``generator``, so a seed fixes the table."""
+    area = height * width
+    log_ratio = (math.log(3.0 / 4.0), math.log(4.0 / 3.0))
+    rows = []
+    for _ in range(n):
+        for _ in range(10):
+            target_area = area * torch.empty(1).uniform_(min_crop_ratio, 1.0, generator=generator).item()
+            aspect = math.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1], generator=generator).item())
+            w = int(round(math.sqrt(target_area * aspect)))
+            h = int(round(math.sqrt(target_area / aspect)))
+            if 0 < w <= width and 0 < h <= height:
+                i = int(torch.randint(0, height - h + 1, size=(1,), generator=generator).item())
+                j = int(torch.randint(0, width - w + 1, size=(1,), generator=generator).item())
+                break
+        else:  # central crop at the nearest allowed aspect
+            in_ratio = float(width) / float(height)
+            if in_ratio < 3.0 / 4.0:
+                w, h = width, int(round(width / (3.0 / 4.0)))
+            elif in_ratio > 4.0 / 3.0:
+                h, w = height, int(round(height * (4.0 / 3.0)))
+            else:
+                w, h = width, height
+            i, j = (height - h) // 2, (width - w) // 2
+        angle = torch.empty(1).uniform_(-float(rotate_degrees), float(rotate_degrees), generator=generator).item() if rotate_degrees else 0.0
+        t = math.radians(angle)
+        rows.append((i, j, h, w, math.cos(t), math.sin(t)))
+    return torch.tensor(rows, dtype=torch.float32).reshape(n, 6)
+
+
+def identity_augment_params(n: int, height: int, width: int) -> torch.Tensor:
+    """The table under which ``pasn_clip_augment`` is plain normalisation: full crop, no rotation."""
+    return torch.tensor([[0, 0, height, width, 1.0, 0.0]], dtype=torch.float32).repeat(n, 1)
+
+
 class DeviceClipPipeline:
     """Batches of single-channel clips -> what ``model(x)`` takes, with the normalisation and channel expansion left to the GPU.
 
@@ -35,15 +90,35 @@ class DeviceClipPipeline:
     device batch shaped (N,T,H,W) / (N,1,T,H,W) (video) or (N,H,W) / (N,1,H,W) (image) in [0, 1] (float) or [0, 255] (uint8), moves
     it to the model's device asynchronously (one third of the reference's bytes, a twelfth for uint8) and returns the (N,1,...)
     tensor the HIP trunk accepts directly.  ``normalize=False``: the clip is already normalised.
+
+    In train mode ``pipe(cine)`` returns ``normalized(cine, augment)``: the training pass takes a materialised, normalised clip
+    (``augment=True`` draws a crop and an angle per clip: ``rotate_degrees``, ``min_crop_ratio``, from a generator seeded by ``seed``).
     """
 
-    def __init__(self, model: torch.nn.Module, normalize: bool = True, video: Optional[bool] = None):
+    def __init__(self, model: torch.nn.Module, normalize: bool = True, video: Optional[bool] = None, augment: bool = False,
+                 rotate_degrees: float = 0.0, min_crop_ratio: float = 1.0, seed: int = 0):
+        self.model = model
         self.trunk = getattr(model, "cnn_backbone", None) or getattr(model, "features")
         self.device = next(model.parameters()).device
         self.normalize = normalize
         self.video = type(model).__name__.startswith("Video") if video is None else bool(video)
+        self.augment, self.rotate_degrees, self.min_crop_ratio = bool(augment), float(rotate_degrees), float(min_crop_ratio)
+        if not 0.0 < self.min_crop_ratio <= 1.0:
+            raise ValueError(f"min_crop_ratio must lie in (0, 1], not {min_crop_ratio}")
+        self.generator = torch.Generator().manual_seed(int(seed))
+        self._identity = {}      # (n, H, W) -> identity parameter table on the device
+        self._affine = None      # the trunk's input normalisation as this pipeline last set it (None: never set)
+        self._in_flight = []     # (pinned table, event of its upload): a pinned buffer lives until its copy has completed
 
-    def __call__(self, cine: torch.Tensor) -> torch.Tensor:
+    @classmethod
+    def from_config(cls, model: torch.nn.Module, data_cfg: dict, seed: int = 0) -> "DeviceClipPipeline":
+        """The reference's ``data`` keys (src/configs/*.yml): ``augmentation``, ``transform_rotate_degrees``, ``transform_min_crop_ratio``,
+        ``normalize``.  ``transform_time_dilation`` is the dataset's (the frame window is picked before the host resize)."""
+        return cls(model, normalize=bool(data_cfg.get("normalize", True)), augment=bool(data_cfg.get("augmentation", False)),
+                   rotate_degrees=float(data_cfg.get("transform_rotate_degrees", 0.0) or 0.0),
+                   min_crop_ratio=float(data_cfg.get("transform_min_crop_ratio", 1.0) or 1.0), seed=seed)
+
+    def _grey(self, cine: torch.Tensor) -> torch.Tensor:
         x = cine
         if x.dim() == (4 if self.video else 3):  # (N,T,H,W) / (N,H,W): add the channel axis
             x = x.unsqueeze(1)
@@ -52,9 +127,54 @@ class DeviceClipPipeline:
                              % ("T," if self.video else ""))
         if x.dtype not in (torch.uint8, torch.float32, torch.bfloat16):
             x = x.float()
+        return x
+
+    def _params(self, n: int, height: int, width: int, augment: bool) -> torch.Tensor:
+        if not augment:
+            key = (n, height, width)
+            if key not in self._identity:
+                self._identity[key] = identity_augment_params(n, height, width).to(self.device)
+            return self._identity[key]
+        self._in_flight = [(b, e) for b, e in self._in_flight if not e.query()]
+        host = sample_augment_params(n, height, width, self.min_crop_ratio, self.rotate_degrees, self.generator).pin_memory()
+        table = host.to(self.device, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._in_flight.append((host, ev))
+        return table
+
+    def normalized(self, cine: torch.Tensor, augment: bool = False) -> torch.Tensor:
+        """The normalised grey clip (N,1,...) in the model's compute dtype, what the training pass takes: ONE ``pasn_clip_augment`` launch
+        (crop + bilinear resize + rotation when ``augment``, then ``bin_to_norm`` when ``normalize``).  Switches the trunk's fused input
+        normalisation off, since the clip it returns is already normalised.  A normalisation on the trunk that this pipeline did not set
+        (``set_input_normalization``, another pipeline) is never dropped silently: ``GreyInputError``."""
+        have = tuple(self.trunk.input_affine)
+        if have != (1.0, 0.0) and have != self._affine:
+            raise GreyInputError("the trunk carries an input normalisation this pipeline did not set (set_input_normalization or another "
+                                 "DeviceClipPipeline); normalized() would drop it, and a normalised grey clip on top of it would be normalised "
+                                 "twice.  Call set_input_normalization(None) first, or train on the reference's 3-channel clip")
+        x = self._grey(cine).contiguous().to(self.device, non_blocking=True)
+        n, height, width = x.shape[0], x.shape[-2], x.shape[-1]
+        frames = x.shape[2] if x.dim() == 5 else 1
+        out_dtype = self.model._dtype() if hasattr(self.model, "_dtype") else torch.float32
+        y = torch.empty(x.shape, dtype=out_dtype, device=self.device)
+        params = self._params(n, height, width, augment)
+        mean, std = (ECHO_MEAN, ECHO_STD) if self.normalize else (0.0, 1.0)
+        _lib.check(_lib.lib().pasn_clip_augment(
+            x.data_ptr(), y.data_ptr(), params.data_ptr(), n, frames, height, width, height, width, 1.0 / 255.0 if x.dtype == torch.uint8 else 1.0,
+            mean, std, _lib.dtype_code(x.dtype), _lib.dtype_code(out_dtype), _lib.F32, _lib.current_stream()))
+        self.trunk.set_input_normalization(None)
+        self._affine = tuple(self.trunk.input_affine)
+        return y
+
+    def __call__(self, cine: torch.Tensor) -> torch.Tensor:
+        if self.model.training:
+            return self.normalized(cine, self.augment)
+        x = self._grey(cine)
         scale = 1.0 / 255.0 if x.dtype == torch.uint8 else 1.0
         if self.normalize:
             self.trunk.set_input_normalization(ECHO_MEAN, ECHO_STD, scale)
         else:
             self.trunk.set_input_normalization(None)
+        self._affine = tuple(self.trunk.input_affine)
         return x.contiguous().to(self.device, non_blocking=True)

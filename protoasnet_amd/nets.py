@@ -19,6 +19,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import XProtoDesc
 from .backbones import base_architecture_to_features
+from .data import GreyInputError
 from .plan import Act, HipTrunk, PlanBuilder, channels_last_rows, logical_view, pack_conv_weight, round_up
 from .receptive_field import compute_proto_layer_rf_info_v2
 
@@ -271,18 +272,31 @@ class PPNet(nn.Module):
             return -distances
         return self.prototype_activation_function(distances)
 
+    def _train_input(self, x: torch.Tensor) -> torch.Tensor:
+        """The clip a training pass takes: the reference's 3-channel clip, or its single grey channel (N,1,...) ALREADY normalised, fp32 or
+        bf16 -- the first conv sums its taps over the three identical channels (``DeviceClipPipeline.normalized`` makes such a clip)."""
+        if not x.is_cuda:
+            raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
+        if x.shape[1] == 1:
+            if x.dtype == torch.uint8:
+                raise GreyInputError("the training pass takes the reference's 3-channel clip or a normalised grey clip, not uint8 pixels: "
+                                     "use protoasnet_amd.data.DeviceClipPipeline.normalized(cine, augment) first")
+            trunk = getattr(self, "cnn_backbone", None) or self.features
+            if tuple(getattr(trunk, "input_affine", (1.0, 0.0))) != (1.0, 0.0):
+                raise GreyInputError("the trunk carries an input normalisation (set_input_normalization), which only the eval-mode first layer "
+                                     "applies; the training pass takes the reference's 3-channel clip or a normalised grey clip: use "
+                                     "protoasnet_amd.data.DeviceClipPipeline.normalized(cine, augment), or call set_input_normalization(None)")
+        elif x.shape[1] != 3:
+            raise NotImplementedError("the training pass takes the reference's 3-channel clip or its single grey channel")
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        return x.contiguous()
+
     def _train_pass_a(self, x: torch.Tensor):
         """Train-mode forward of the ProtoPNet model (differentiable; ``train.TrainRunner`` with head A)."""
         from .train import TrainRunner
 
-        if not x.is_cuda:
-            raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
-        if x.shape[1] != 3:
-            raise NotImplementedError("the training pass takes the reference's 3-channel clip; single-channel (grey) input is an "
-                                      "eval-mode path (protoasnet_amd.data.DeviceClipPipeline)")
-        if x.dtype not in (torch.float32, torch.bfloat16):
-            x = x.float()
-        x = x.contiguous()
+        x = self._train_input(x)
         runners = self.__dict__.setdefault("_train_runners", {})
         key = (tuple(x.shape), x.dtype, self._dtype(), "A", hash(tuple((p.data_ptr(), p.requires_grad) for p in self.parameters())),
                tuple(self.prototype_shape), _lib.tuning_epoch())
@@ -343,14 +357,7 @@ class _XProtoHeadMixin:
         (Video_XProtoNet_e2e.py:118-141; ``compute_occurence_map`` is called with gradients by loss.py:302)."""
         from .train import TrainRunner
 
-        if not x.is_cuda:
-            raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
-        if x.shape[1] != 3:
-            raise NotImplementedError("the training pass takes the reference's 3-channel clip; single-channel (grey) input is an "
-                                      "eval-mode path (protoasnet_amd.data.DeviceClipPipeline)")
-        if x.dtype not in (torch.float32, torch.bfloat16):
-            x = x.float()
-        x = x.contiguous()
+        x = self._train_input(x)
         runners = self.__dict__.setdefault("_train_runners", {})
         # the launch lists hold the parameters' device addresses: a model moved / cast / pruned since gets a fresh compilation
         key = (tuple(x.shape), x.dtype, self._dtype(), mode, hash(tuple((p.data_ptr(), p.requires_grad) for p in self.parameters())),

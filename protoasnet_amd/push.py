@@ -271,6 +271,8 @@ def _save_xproto_artefacts(root: str, epoch_number, merged, rec, names, log) -> 
     os.makedirs(proto_epoch_dir, exist_ok=True)
     dist, index, _ = merged
     occ, logits, imgs, gts = (t.detach().cpu().numpy() for t in rec)
+    if imgs.shape[1] == 1:  # winners from single-channel clips: the artefact keeps the reference's (P, 3, ...) layout
+        imgs = np.repeat(imgs, 3, axis=1)
     idx = index.detach().cpu().numpy().astype(np.int64)
     bases = sorted(names)
     files = []

@@ -45,7 +45,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from . import _lib, dp, losses
+from . import _lib, data, dp, losses
 from . import push as push_mod
 
 
@@ -88,6 +88,7 @@ class DPTrainer:
         self.get_optimizer()
         self.scheduler = self.get_lr_scheduler()
         self.params = [p for g in self.optimizer.param_groups for p in g["params"]]
+        self._clip_pipe = None  # built on the first single-channel batch (clip_pipeline)
         self.sync_model_state()  # ranks built from different seeds / checkpoints would otherwise stay different models for ever
 
     # ---- one model on every rank ------------------------------------------------------------------------------------------------
@@ -220,6 +221,24 @@ class DPTrainer:
         self.log(f"Checkpoint loaded successfully from '{file_name}' at (epoch {ck['epoch']}) at (iteration {ck['iteration']})")
         return True
 
+    # ---- single-channel clips: augmentation and normalisation on the device --------------------------------------------------------
+    def clip_pipeline(self) -> "data.DeviceClipPipeline":
+        """The device input pipeline of single-channel batches, from the reference's ``data`` keys (augmentation, rotation, crop ratio,
+        normalize); its generator is seeded by ``train.seed`` and the rank, so ranks draw different crops and a rerun draws the same."""
+        if self._clip_pipe is None:
+            seed = int(self.train_config.get("seed", 0) or 0) * 7919 + self.rank
+            self._clip_pipe = data.DeviceClipPipeline.from_config(self.model, self.config.get("data", {}) or {}, seed=seed)
+        return self._clip_pipe
+
+    def prepare_input(self, cine: torch.Tensor, train: bool = False) -> torch.Tensor:
+        """A batch's ``cine`` as the model takes it: a 3-channel clip moves to the device as it is; a single-channel (N,1,...) clip
+        (fp32 / bf16 in [0, 1], or uint8) becomes the normalised grey clip in ONE launch, augmented in ``train`` epochs when the config's
+        ``data.augmentation`` says so (the reference's train split; val, test and push clips are never augmented)."""
+        if cine.dim() >= 4 and cine.shape[1] == 1:
+            pipe = self.clip_pipeline()
+            return pipe.normalized(cine, train and pipe.augment)
+        return cine.to(self.device, non_blocking=True)
+
     # ---- Video_XProtoNet_e2e.py:36-361, minus the per-batch host work ------------------------------------------------------------
     def compute_loss(self, inp, target, logit, similarities, occurrence_map, occurrence_map_transformed=None, affine_config=None):
         terms = [
@@ -260,7 +279,7 @@ class DPTrainer:
         warp_in_batch = self.Trans_occurrence.loss_weight != 0 and (mode != "train" or (hasattr(self.model, "forward_pair") and _lib.tuning_get("PASN_NO_TRAIN_PAIR") != "1"))
         with torch.set_grad_enabled(mode == "train"):
             for i, sample in enumerate(loader):
-                inp = sample["cine"].to(self.device, non_blocking=True)
+                inp = self.prepare_input(sample["cine"], train=mode == "train")
                 target = sample["target_AS"].to(self.device, non_blocking=True)
                 if warp_in_batch:  # the reference's second trunk pass (loss.py:302) shares the launch list of the first
                     cfg = losses.get_affine_config()
@@ -306,7 +325,8 @@ class DPTrainer:
         return push_mod.push_prototypes(
             self.data_loaders["train_push"], self.model, class_specific=True, abstain_class=abstain,
             root_dir_for_saving_prototypes=self.config.get("save_dir") and os.path.join(self.config["save_dir"], "img"),
-            epoch_number=self.current_epoch, log=self.log, replace_prototypes=replace_prototypes, rank=self.rank, world_size=self.world_size)
+            epoch_number=self.current_epoch, log=self.log, replace_prototypes=replace_prototypes, rank=self.rank, world_size=self.world_size,
+            preprocess_input_function=self.prepare_input)
 
     def save_model_w_condition(self, model_name: str, metric_dict: dict, threshold: float) -> None:
         name, metric = next(iter(metric_dict.items()))
