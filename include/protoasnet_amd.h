@@ -584,6 +584,37 @@ int pasn_affine_warp_bwd(const float* dy, float* dx, long planes, int H, int W, 
 int pasn_clip_augment(const void* x, void* y, const void* params, int N, int T, int H, int W, int Ho, int Wo, float scale, float mean,
                       float stdev, int in_dtype, int out_dtype, int param_dtype, void* stream);
 
+/* Local explanation, ranking (local_explainability.py:88-91 contributions, :112-125 per-class sort; explainability_utils.py:69-72 the
+ * prediction over the non-abstain logits).  One workgroup per clip, N clips per launch:
+ *   sim [N][P] (1 - proto_dist), fc_w [K][P], logits [N][K]: fp32.  P % K == 0, G = P / K prototypes per class block, P <= 16384.
+ *   contrib [N][K][P] or NULL: fc_w[k][p] * sim[n][p], one fp32 product (numpy's, bit for bit)
+ *   totals  [N][K] or NULL:    sim @ fc_w.T (exact products summed in fp64, one rounding to fp32)
+ *   order   [N][P] int32:      per class block c, the prototype indices c*G .. c*G+G-1 by DESCENDING similarity; equal similarities: the
+ *                              HIGHER index first (the reversed stable ascending argsort; the reference's np.argsort quicksort leaves
+ *                              ties unspecified).  NaN similarities give an unspecified order.
+ *   rank    [N][P] int32 or NULL: position of p inside its block's order (the inverse permutation)
+ *   pred    [N] int32:         argmax of logits[n][0 .. K_real) (K_real = K - 1 with an abstain class), the lowest index on ties, NaN
+ *                              counts as the largest value (torch.argmax)
+ *   sel     [N][k_sel] int32 or NULL: the first k_sel (1 <= k_sel <= G) entries of the predicted class's block of order */
+int pasn_explain_rank(const float* sim, const float* fc_w, const float* logits, int N, int P, int K, int K_real, int k_sel,
+                      float* contrib, float* totals, int32_t* order, int32_t* rank, int32_t* pred, int32_t* sel, void* stream);
+
+/* Local explanation, heat maps (explainability_utils.py:158-174 get_normalized_upsample_occurence_maps, :177-200 get_heatmap,
+ * local_explainability.py:76 / :104 the 0.3 overlay).  Two launches on `stream` (stats, write); `workspace` holds
+ * pasn_explain_maps_workspace_bytes(...) bytes (8-byte aligned) and needs no initialisation.
+ *   occ [N][P][Ti][Hi][Wi] fp32 (push_forward's occurrence maps; Ti = 1 for images), sel [N][k] int32 prototype indices or NULL (= all
+ *   P in index order, k == P).  Per selected map: torch.nn.Upsample(size=(To,Ho,Wo), trilinear; bilinear when Ti = To = 1,
+ *   align_corners=False) with torch's CPU arithmetic (explain.hip's header), min / max over the map's To*Ho*Wo voxels,
+ *   v = (u - min) / ((max - min) + 1e-7f), IEEE division.
+ *   maps [N][k][To][Ho][Wo] or NULL: maps_dtype PASN_F32 (v) or PASN_U8 ((uint8)(255.0f * v), truncated as numpy's np.uint8)
+ *   overlay [N][k][To][Ho][Wo][3] fp32 or NULL: (src * std + mean) + alpha * lut[(uint8)(255 v)][c]; src [N][src_channels][To][Ho][Wo]
+ *           (PASN_F32 / PASN_BF16; one channel counts as three identical ones), lut [256][3] fp32 (the caller's colour table)
+ *   maps and overlay 16-byte aligned.  2 * Hi * Wo * 4 > 64 KiB returns PASN_ERR_UNSUPPORTED (no slow path). */
+size_t pasn_explain_maps_workspace_bytes(int N, int P, int k, int Ti, int Hi, int Wi, int To, int Ho, int Wo);
+int pasn_explain_maps(const float* occ, const int32_t* sel, int N, int P, int k, int Ti, int Hi, int Wi, int To, int Ho, int Wo,
+                      void* maps, int maps_dtype, float* overlay, const void* src, int src_dtype, int src_channels, const float* lut,
+                      float mean, float stdv, float alpha, void* workspace, void* stream);
+
 /*
  * Training: all conv weights of a step packed from the live fp32 parameters into the layouts the forward kernels read, in ONE launch
  * (replaces the per-parameter torch expressions of the host side: the reference has no counterpart -- cuDNN reads the parameters as they

@@ -130,6 +130,11 @@ SIGNATURES = {
     "pasn_affine_warp_bwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_float, c_void_p]),
     "pasn_clip_augment": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_float] * 3 + [c_int] * 3 + [c_void_p]),
     "pasn_push_ppnet_update": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    # ---- local explanation (explain.py)
+    "pasn_explain_rank": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 7),
+    "pasn_explain_maps_workspace_bytes": (c_size_t, [c_int] * 9),
+    "pasn_explain_maps": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                                                      c_float, c_float, c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

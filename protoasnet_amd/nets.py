@@ -465,6 +465,12 @@ class _XProtoHeadMixin:
         logits, sim, occ, feats = self._xproto(x, 0)
         return feats, 1 - sim, occ, logits
 
+    def explain(self, x: torch.Tensor, **kw):
+        """Local explanation of the clips ``x`` (explain.explain_batch: ranking, contributions, normalised maps, overlays)."""
+        from .explain import explain_batch
+
+        return explain_batch(self, x, **kw)
+
 
 class XProtoNet(_XProtoHeadMixin, PPNet):
     """Image ProtoASNet / XProtoNet (reference src/models/XProtoNet.py:8-106) -- head B on a 2-D trunk."""
