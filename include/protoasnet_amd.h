@@ -615,6 +615,41 @@ int pasn_explain_maps(const float* occ, const int32_t* sel, int N, int P, int k,
                       void* maps, int maps_dtype, float* overlay, const void* src, int src_dtype, int src_channels, const float* lut,
                       float mean, float stdv, float alpha, void* workspace, void* stream);
 
+/* Evaluation statistics of one batch (Video_XProtoNet_e2e.py:114-117 the real-class probabilities, :157 SparsityMetric, :159-171 the
+ * diversity counters, :173 the similarity sums; src/utils/metrics.py:16-25; XProtoNet_Base.py:416-432).  One launch on `stream`, no
+ * host synchronisation; accumulates into the caller's epoch state (zeroed by the caller at the start of an epoch):
+ *   logits [N][K] fp32, sim [N][P] fp32, target [N] int64; K_real <= K real classes (K - 1 with an abstain class); the prototypes of the
+ *   real classes are [0, P_cls), the abstention prototypes [P_cls, P).  Rows n land at epoch row row_offset + n < capacity.
+ *   probs    [capacity][K_real] fp32 or NULL: softmax(logits[n][0 .. K_real))
+ *   labels   [capacity] int32 or NULL:         (int32) target[n]
+ *   logits_out [capacity][K] fp32 or NULL:     a copy of logits[n]
+ *   sparsity [2] int64 or NULL:  += {sum of the per-row results, N}.  Per row: norm = sim / s (s = the row sum in fp64, rounded once to
+ *                                fp32; IEEE division), sorted descending, prefix sums in fp64 each rounded to fp32; the result is the
+ *                                first index whose prefix is >= level, 0 when there is none (argmax of an all-false mask: all-zero or NaN
+ *                                rows).  An index, not a count, as the reference computes it.
+ *   div_counts [P] int64 or NULL: += 1 for each prototype among the row's top min(k_cls, P_cls) of [0, P_cls) and its top
+ *                                min(k_abs, P - P_cls) of [P_cls, P) by similarity; ties: the lower index first (stable descending sort).
+ *                                Rows holding NaN: unspecified.
+ *   sim_sums [P] fp64 or NULL:   += the column sums; one thread per column adds the rows in order (bitwise reproducible).
+ *   P > 4096 returns PASN_ERR_UNSUPPORTED (no slow path). */
+int pasn_eval_batch_stats(const float* logits, const float* sim, const int64_t* target, int N, int K, int K_real, int P, int P_cls, int k_cls,
+                          int k_abs, float level, long row_offset, long capacity, float* probs, int32_t* labels, float* logits_out,
+                          int64_t* sparsity, int64_t* div_counts, double* sim_sums, void* stream);
+
+/* Weighted one-vs-rest ROC AUC (Video_XProtoNet_e2e.py:256-266 roc_auc_score(average="weighted", multi_class="ovr",
+ * labels=range(K_real)) with its `except ValueError: AUC = 0`; XProtoNet_Base.py:515-525).  probs [M][K_real] fp32, labels [M] int32;
+ * label < 0 is a padding row and is ignored.  Per class k, over the valid rows:
+ *   U2_k = sum over positives i (label k), negatives j (label != k) of 2 [s_j < s_i] + [s_j == s_i]   (s = probs[.][k]; int64)
+ *   auc_per_class[k] = U2_k / (2 n_pos n_neg) in fp64 (sklearn's trapezoidal AUC: the Mann-Whitney statistic with ties counted 1/2)
+ *   auc[0] = sum_k n_pos_k auc_k / sum_k n_pos_k
+ * If a class has no positive or no negative row, a label is >= K_real or a probability of a valid row is NaN, auc[0] = 0.0 (sklearn
+ * raises) and the classes without a defined AUC -- every class, for NaN or a bad label -- hold NaN.  Two launches (tiled pairwise count,
+ * finish) on `stream`; `workspace` holds pasn_roc_auc_workspace_bytes(M, K_real) bytes (4-byte aligned) and needs no initialisation.
+ * 2 <= K_real <= 16, 1 <= M <= 2^24.  auc and auc_per_class are device memory (fp64). */
+size_t pasn_roc_auc_workspace_bytes(long M, int K_real);
+int pasn_roc_auc_ovr(const float* probs, const int32_t* labels, long M, int K_real, double* auc, double* auc_per_class, void* workspace,
+                     void* stream);
+
 /*
  * Training: all conv weights of a step packed from the live fp32 parameters into the layouts the forward kernels read, in ONE launch
  * (replaces the per-parameter torch expressions of the host side: the reference has no counterpart -- cuDNN reads the parameters as they

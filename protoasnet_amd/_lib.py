@@ -135,6 +135,10 @@ SIGNATURES = {
     "pasn_explain_maps_workspace_bytes": (c_size_t, [c_int] * 9),
     "pasn_explain_maps": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                                       c_float, c_float, c_float, c_void_p, c_void_p]),
+    # ---- evaluation statistics (metrics.py)
+    "pasn_eval_batch_stats": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_float, c_long, c_long] + [c_void_p] * 7),
+    "pasn_roc_auc_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "pasn_roc_auc_ovr": (c_int, [c_void_p, c_void_p, c_long, c_int] + [c_void_p] * 4),
 }
 
 _lib = None

@@ -33,7 +33,14 @@ What it changes, because it has to scale:
   rank with fewer would issue fewer gradient all-reduces and hang the job); gradients of a trailing partial accumulation are kept
   across the epoch boundary, as the reference keeps them (it never zeroes at the start of an epoch).
 
-Out of scope: wandb / CSV logging, AUC, the diversity counters with their hard-coded ``[:30]`` split, plots.
+Evaluation metrics (``protoasnet_amd.metrics``): on a GPU model every epoch, in every mode as in the reference, also accumulates the
+weighted one-vs-rest ROC AUC, the prototype sparsity, the diversity counters and the similarity sums on the device (one launch per batch;
+Video_XProtoNet_e2e.py:154-173, 256-281) and returns them with the confusion-matrix metrics; ``val_push`` / ``test`` epochs write the
+reference's per-clip prediction CSV (``save_dir/csv_<mode>/e<epoch>_f1_<f1>.csv``, :313-319).  Across ranks the additive counters ride in
+the one per-epoch all-reduce, the AUC sees every rank's rows (one ``all_gather``), and the CSV rows reach rank 0 rank-major: rank 0's
+clips in its loader order, then rank 1's, and so on.  ``evaluate(mode)`` is the reference's ``eval_only`` entry (main.py:52-53).
+
+Out of scope: wandb, plots, the ``classification_report`` text.
 """
 from __future__ import annotations
 
@@ -45,7 +52,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from . import _lib, data, dp, losses
+from . import _lib, data, dp, losses, metrics as metrics_mod
 from . import push as push_mod
 
 
@@ -277,6 +284,9 @@ class DPTrainer:
         # the reference's second trunk pass (loss.py:302) rides in the first one's launch list: eval epochs on running statistics, training
         # epochs with two statistics groups (model.forward_pair; PASN_NO_TRAIN_PAIR=1: two passes)
         warp_in_batch = self.Trans_occurrence.loss_weight != 0 and (mode != "train" or (hasattr(self.model, "forward_pair") and _lib.tuning_get("PASN_NO_TRAIN_PAIR") != "1"))
+        write_csv = mode in ("val_push", "test") and bool(self.config.get("save_dir"))
+        ev = self.evaluator(loader, keep_logits=write_csv)  # None on a CPU model: its epoch dict stays the confusion-matrix one
+        metas = []
         with torch.set_grad_enabled(mode == "train"):
             for i, sample in enumerate(loader):
                 inp = self.prepare_input(sample["cine"], train=mode == "train")
@@ -299,6 +309,10 @@ class DPTrainer:
                 cm += torch.bincount(target.clamp(0, K - 1) * K + pred, minlength=K * K)
                 loss_sum += terms
                 n_batches += 1
+                if ev is not None:
+                    ev.update(logit, similarities, target)
+                    if write_csv:
+                        metas.append(metrics_mod.batch_log_meta(sample))
                 if mode == "train":
                     self._norm_dirty = True  # this rank's running statistics moved on their own
                     loss.backward()  # undivided, as the reference accumulates it
@@ -308,7 +322,11 @@ class DPTrainer:
                         self.optimizer.zero_grad(set_to_none=True)
                     self.current_iteration += 1
         stats = torch.cat([cm.float(), loss_sum, torch.tensor([float(n_batches)], device=self.device)])
-        if self.world_size > 1:  # one tiny all-reduce per epoch: every rank sees the global confusion matrix and takes the same decisions
+        evm = None
+        if ev is not None:  # the evaluation counters ride in the same single all-reduce (fp64; the stats come back as the fp32 sums)
+            evm, stats = ev.finish_with(self.world_size, stats)
+            stats = stats.float()
+        elif self.world_size > 1:  # one tiny all-reduce per epoch: every rank sees the global confusion matrix and takes the same decisions
             stats = push_mod._for_collective(stats)
             dist.all_reduce(stats)
         stats = stats.cpu()
@@ -317,7 +335,47 @@ class DPTrainer:
         metrics["loss_terms"] = (stats[K * K: K * K + 7] / nb).tolist()
         metrics["loss"] = float(sum(metrics["loss_terms"]))
         self.log(f"Epoch: {epoch} | {mode} | loss {metrics['loss']:.4f} | acc {metrics['accuracy']:.2%} | f1 {metrics['f1_mean']:.3f}")
+        if evm is not None:
+            metrics.update(evm)
+            div = f"diversity {evm['diversity']}" + ("" if evm["diversity_abstain"] is None else f" | diversity_abstain {evm['diversity_abstain']}")
+            self.log(f"Epoch: {epoch} | {mode} | AUC {evm['auc']:.4f} | sparsity {evm['sparsity']:.3f} | {div}")
+            if write_csv:
+                self.write_prediction_log(epoch, mode, metrics["f1_mean"], metas, ev)
         return metrics
+
+    # ---- evaluation metrics: Video_XProtoNet_e2e.py:154-173, 221-233, 240-319 -------------------------------------------------------
+    def evaluator(self, loader, keep_logits: bool = False) -> Optional["metrics_mod.EpochEvaluator"]:
+        """The epoch's device metric state (``metrics.EpochEvaluator``), or None on a CPU model; its buffers sized ``len(loader) *
+        batch_size`` when the loader knows both."""
+        if self.device.type != "cuda":
+            return None
+        cap = len(loader) * int(getattr(loader, "batch_size", 0) or 0) if hasattr(loader, "__len__") else 0
+        return metrics_mod.EpochEvaluator(self.model, level=0.8, keep_logits=keep_logits, abstain_class=bool(self.config.get("abstain_class")),
+                                          capacity=cap)
+
+    def write_prediction_log(self, epoch: int, mode: str, f1_mean: float, metas, ev) -> Optional[str]:
+        """The reference's per-clip CSV (base.py:195-211; file name Video_XProtoNet_e2e.py:314-318).  With several ranks every rank's rows
+        reach rank 0 through ``all_gather_object``, rank-major; rank 0 writes."""
+        names = metrics_mod.logit_names(self.num_real_classes, bool(self.config.get("abstain_class")), self.config.get("class_labels"))
+        rows = metrics_mod.prediction_rows(metas, ev.logits[: ev.rows].cpu().numpy(), names)
+        if self.world_size > 1:
+            every = [None] * self.world_size
+            dist.all_gather_object(every, rows)
+            rows = [r for part in every for r in part]
+        if self.rank != 0:
+            return None
+        d = os.path.join(self.config["save_dir"], f"csv_{mode}")
+        os.makedirs(d, exist_ok=True)
+        path = os.path.join(d, f"e{epoch:02d}_f1_{f1_mean:.0%}.csv")
+        metrics_mod.write_prediction_log(path, rows)
+        return path
+
+    def evaluate(self, mode: str = "val") -> Dict[str, object]:
+        """One evaluation epoch at the current epoch (the reference's ``eval_only`` run: main.py:52-53, ProtoPNet_Base.py:203-205);
+        ``mode`` is ``val``, ``val_push`` or ``test`` -- a key of ``data_loaders`` (``val_push`` reads ``val``)."""
+        if mode == "train":
+            raise ValueError("evaluate runs an evaluation epoch: val, val_push or test")
+        return self.run_epoch(self.current_epoch, mode)
 
     def push(self, replace_prototypes: bool = True):
         abstain = bool(self.config.get("abstain_class"))
