@@ -650,6 +650,25 @@ size_t pasn_roc_auc_workspace_bytes(long M, int K_real);
 int pasn_roc_auc_ovr(const float* probs, const int32_t* labels, long M, int K_real, double* auc, double* auc_per_class, void* workspace,
                      void* stream);
 
+/* The reference dataset's clip resize on the device (as_dataloader.py:204-207, skimage.transform.resize(window, (T, H, W)) of
+ * scikit-image >= 0.19 with its defaults: uint8 / 255, Gaussian anti-aliasing (sigma = max(0, (f - 1) / 2), mode 'mirror', truncate 4)
+ * on the shrinking axes, linear zoom with grid_mode (source (o + 0.5) f - 0.5, mode 'mirror')).  That operator is separable,
+ * A_T (x) A_H (x) A_W, each axis a banded table the host builds in float64 and rounds to fp32 once (protoasnet_amd/resample.py).
+ * One launch over a RAGGED batch of N windows:
+ *   src      the flat source buffer (device, 16-byte aligned, src_bytes a multiple of 16), uint8 (in_dtype PASN_U8) or fp32 (PASN_F32)
+ *   desc     int64 [N][8]: {byte offset of the source cine in src, first frame of the window, T_w, H0, W0 (window of the cine
+ *            (T_src, H0, W0) stored C-contiguous), offsets (int32 units) into bands of the T, H and W tables}
+ *   bands    int32 [bands_len]: tables {n_in, n_out, S, start[n_out], weights[n_out][S] as fp32 bits}; starts non-decreasing
+ *   y        (N, T, H, W) in out_dtype PASN_F32 / PASN_BF16: (A v * scale - mean) / std, fp32 accumulation (mean 0, std 1: the clip)
+ * Geometry: a workgroup owns tile_h x tile_w output pixels (at most pasn_cine_resize_pixels_per_block(T)) of one clip; tmp_rows >= the
+ * largest H-band union of a tile, raw_pitch (a multiple of 16) >= its W-band union in bytes + 15, chunk_rows rows staged at a time,
+ * band_floats >= tile_w (S_W + 1) + tile_h (S_H + 1) over the batch's tables (the tile's bands, staged in LDS).
+ * A clip whose descriptor, tables or source range disagree with the launch is not read: its outputs are NaN. */
+int pasn_cine_resize_pixels_per_block(int T);
+int pasn_cine_resize(const void* src, long src_bytes, const long long* desc, const int* bands, long bands_len, void* y, int N, int T, int H,
+                     int W, int tile_h, int tile_w, int tmp_rows, int raw_pitch, int chunk_rows, int band_floats, float mean, float stdev,
+                     int in_dtype, int out_dtype, void* stream);
+
 /*
  * Training: all conv weights of a step packed from the live fp32 parameters into the layouts the forward kernels read, in ONE launch
  * (replaces the per-parameter torch expressions of the host side: the reference has no counterpart -- cuDNN reads the parameters as they

@@ -139,6 +139,9 @@ SIGNATURES = {
     "pasn_eval_batch_stats": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_float, c_long, c_long] + [c_void_p] * 7),
     "pasn_roc_auc_workspace_bytes": (c_size_t, [c_long, c_int]),
     "pasn_roc_auc_ovr": (c_int, [c_void_p, c_void_p, c_long, c_int] + [c_void_p] * 4),
+    # ---- raw cine windows -> model clips (resample.py)
+    "pasn_cine_resize_pixels_per_block": (c_int, [c_int]),
+    "pasn_cine_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p] + [c_int] * 10 + [c_float] * 2 + [c_int] * 2 + [c_void_p]),
 }
 
 _lib = None

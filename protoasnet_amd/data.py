@@ -10,8 +10,14 @@ the input channels: 9 spatial taps instead of 27 for the X3D stem) -- ``pasn_x3d
 Training takes the grey clip too: ``DeviceClipPipeline.normalized`` runs the train split's augmentation (torchvision's
 ``RandomResizedCropVideo`` + the reference's ``RandomRotateVideo``, as_dataloader.py:127-133) and ``bin_to_norm`` in ONE launch
 (``pasn_clip_augment``, csrc/augment.hip) on per-clip parameters drawn here, on the host, from a private generator
-(``sample_augment_params``).  ``transform_time_dilation`` picks the frame window on the raw cine before the host resize, so it stays in
-the user's dataset.
+(``sample_augment_params``).
+
+The reference's host resize (``skimage.transform.resize(cine[window_start:window_end], (frames, img_size, img_size))``,
+as_dataloader.py:204-207) runs on the device too: a dataset returns the raw cine with its window, ``collate_raw_cines`` packs a batch
+into a ``RawCineBatch`` (each distinct source, keyed by filename, stored once and only over the frames its windows cover) and
+``DeviceClipPipeline`` resizes it in one ``pasn_cine_resize`` launch (csrc/cine_resize.hip; band tables in ``resample.py``) before the
+normalisation / augmentation above.  Choosing the window (``transform_time_dilation``, ``compute_intervals``) and decoding the cine
+stay in the user's dataset.
 
 ``bin_to_norm`` / ``gray_to_gray3`` keep the reference's names and semantics for code that still wants the 3-channel tensor.
 """
@@ -20,9 +26,10 @@ from __future__ import annotations
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, resample
 
 ECHO_MEAN, ECHO_STD = 0.099, 0.171  # as_dataloader.py:180-181
 
@@ -83,6 +90,107 @@ def identity_augment_params(n: int, height: int, width: int) -> torch.Tensor:
     return torch.tensor([[0, 0, height, width, 1.0, 0.0]], dtype=torch.float32).repeat(n, 1)
 
 
+class RawCineBatch:
+    """A ragged batch of raw cine windows on the host or the device: what ``collate_raw_cines`` builds and ``DeviceClipPipeline`` resizes.
+
+    ``buffer``: the sources as one flat uint8 tensor (each source C-contiguous (frames, H0, W0) in ``dtype``, uint8 or float32, at a
+    16-byte aligned offset; the length a multiple of 16).  ``windows``: int64 (N, 5) host tensor, per clip {byte offset of its source,
+    first frame of the window inside the stored frames, T_w, H0, W0}.  ``ready``: the event of an asynchronous upload to wait on before
+    reading ``buffer`` (set by whoever issued the copy on another stream), or None."""
+
+    def __init__(self, buffer: torch.Tensor, windows: torch.Tensor, dtype: torch.dtype, ready=None):
+        if buffer.dtype != torch.uint8 or buffer.dim() != 1 or buffer.numel() % 16:
+            raise ValueError("RawCineBatch.buffer is a flat uint8 tensor whose length is a multiple of 16")
+        if windows.dtype != torch.int64 or windows.dim() != 2 or windows.shape[1] != 5 or windows.device.type != "cpu":
+            raise ValueError("RawCineBatch.windows is an int64 (N, 5) host tensor")
+        if dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f"raw cines are uint8 or float32, not {dtype}")
+        self.buffer, self.windows, self.dtype, self.ready = buffer, windows, dtype, ready
+
+    def __len__(self) -> int:
+        return int(self.windows.shape[0])
+
+    @property
+    def device(self) -> torch.device:
+        return self.buffer.device
+
+    def is_pinned(self) -> bool:
+        return self.buffer.is_pinned()
+
+    def pin_memory(self, device=None) -> "RawCineBatch":
+        """The batch with its buffer in page-locked memory (``DataLoader(pin_memory=True)`` calls this)."""
+        return self if self.buffer.is_cuda or self.buffer.is_pinned() else RawCineBatch(self.buffer.pin_memory(), self.windows, self.dtype)
+
+    def to(self, device, non_blocking: bool = False) -> "RawCineBatch":
+        """The batch with its buffer on ``device`` (the window table stays on the host: the launch reads it there)."""
+        return RawCineBatch(self.buffer.to(device, non_blocking=non_blocking), self.windows, self.dtype, self.ready)
+
+    def window(self, i: int) -> torch.Tensor:
+        """Clip ``i``'s raw window (T_w, H0, W0) as a view of the buffer (host or device)."""
+        off, first, tw, h0, w0 = (int(v) for v in self.windows[i])
+        es = 1 if self.dtype == torch.uint8 else 4
+        start = off + first * h0 * w0 * es
+        return self.buffer[start:start + tw * h0 * w0 * es].view(self.dtype).view(tw, h0, w0)
+
+
+def _as_cine(cine, i: int) -> np.ndarray:
+    a = cine.detach().cpu().numpy() if isinstance(cine, torch.Tensor) else np.asarray(cine)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError(f"collate_raw_cines: item {i}'s cine has shape {tuple(a.shape)}; it takes the single-channel (T, H, W) cine "
+                         "(a 3-channel clip is already resized: collate it with the default collate)")
+    if a.dtype not in (np.uint8, np.float32):
+        raise TypeError(f"collate_raw_cines: item {i}'s cine is {a.dtype}; raw cines are uint8 or float32")
+    return a
+
+
+def collate_raw_cines(items) -> dict:
+    """``collate_fn`` for dataset items carrying the full single-channel ``cine`` (T x H0 x W0, uint8 or float32) with ``window_start`` /
+    ``window_end`` (the frame window, end exclusive, as_dataloader.py:225-231) instead of the resized clip.
+
+    ``batch["cine"]`` is a ``RawCineBatch``: one flat buffer in which each distinct source (keyed by ``filename``; an item without one is
+    its own source) is stored ONCE, over the frame range its windows cover -- many intervals of one cine (``iterate_intervals``) cost one
+    copy.  Every other key collates as ``default_collate`` does."""
+    if not items:
+        raise ValueError("collate_raw_cines: empty batch")
+    sources, order, dtype = {}, [], None
+    for i, it in enumerate(items):
+        a = _as_cine(it["cine"], i)
+        s, e = int(it["window_start"]), int(it["window_end"])
+        if not 0 <= s < e <= a.shape[0]:
+            raise ValueError(f"collate_raw_cines: item {i} has the empty or out-of-range window [{s}, {e}) of a {a.shape[0]}-frame cine")
+        if dtype is None:
+            dtype = a.dtype
+        elif a.dtype != dtype:
+            raise TypeError(f"collate_raw_cines: one batch holds one source dtype, got {dtype} and {a.dtype}")
+        key = ("file", it["filename"]) if it.get("filename") is not None else ("item", i)
+        if key in sources:
+            src = sources[key]
+            if src["cine"].shape != a.shape:
+                raise ValueError(f"collate_raw_cines: two cines named {it['filename']!r} differ in shape: {src['cine'].shape} and {a.shape}")
+            src["lo"], src["hi"] = min(src["lo"], s), max(src["hi"], e)
+        else:
+            sources[key] = {"cine": a, "lo": s, "hi": e}
+        order.append((key, s, e))
+    es = dtype.itemsize
+    at = 0
+    for src in sources.values():
+        src["off"] = at
+        at += (src["hi"] - src["lo"]) * src["cine"].shape[1] * src["cine"].shape[2] * es
+        at = (at + 15) // 16 * 16
+    buffer = torch.zeros(max(at, 16), dtype=torch.uint8)
+    flat = buffer.numpy()
+    for src in sources.values():
+        part = np.ascontiguousarray(src["cine"][src["lo"]:src["hi"]]).reshape(-1).view(np.uint8)
+        flat[src["off"]:src["off"] + part.size] = part
+    windows = torch.tensor([[sources[k]["off"], s - sources[k]["lo"], e - s, *sources[k]["cine"].shape[1:]] for k, s, e in order],
+                           dtype=torch.int64)
+    rest = torch.utils.data.default_collate([{k: v for k, v in it.items() if k != "cine"} for it in items])
+    rest["cine"] = RawCineBatch(buffer, windows, torch.uint8 if dtype == np.uint8 else torch.float32)
+    return rest
+
+
 class DeviceClipPipeline:
     """Batches of single-channel clips -> what ``model(x)`` takes, with the normalisation and channel expansion left to the GPU.
 
@@ -93,10 +201,16 @@ class DeviceClipPipeline:
 
     In train mode ``pipe(cine)`` returns ``normalized(cine, augment)``: the training pass takes a materialised, normalised clip
     (``augment=True`` draws a crop and an angle per clip: ``rotate_degrees``, ``min_crop_ratio``, from a generator seeded by ``seed``).
+
+    ``cine`` may also be a ``RawCineBatch`` (``collate_raw_cines``): its windows are first resized to (``frames``, ``img_size``,
+    ``img_size``) on the device (``pasn_cine_resize``; ``frames`` is 1 for an image model).  Eval: one launch to [0, 1] in the model's
+    dtype, normalisation fused into the trunk as for clips.  Train without augmentation: one launch, normalised in its epilogue.  Train
+    with augmentation: the resize, then ``pasn_clip_augment`` (the reference's order: resize, then crop / rotate).
     """
 
     def __init__(self, model: torch.nn.Module, normalize: bool = True, video: Optional[bool] = None, augment: bool = False,
-                 rotate_degrees: float = 0.0, min_crop_ratio: float = 1.0, seed: int = 0):
+                 rotate_degrees: float = 0.0, min_crop_ratio: float = 1.0, seed: int = 0, frames: Optional[int] = None,
+                 img_size: Optional[int] = None):
         self.model = model
         self.trunk = getattr(model, "cnn_backbone", None) or getattr(model, "features")
         self.device = next(model.parameters()).device
@@ -109,14 +223,32 @@ class DeviceClipPipeline:
         self._identity = {}      # (n, H, W) -> identity parameter table on the device
         self._affine = None      # the trunk's input normalisation as this pipeline last set it (None: never set)
         self._in_flight = []     # (pinned table, event of its upload): a pinned buffer lives until its copy has completed
+        self.frames = None if frames is None else int(frames)        # output shape of a RawCineBatch's resize
+        self.img_size = None if img_size is None else int(img_size)
 
     @classmethod
     def from_config(cls, model: torch.nn.Module, data_cfg: dict, seed: int = 0) -> "DeviceClipPipeline":
         """The reference's ``data`` keys (src/configs/*.yml): ``augmentation``, ``transform_rotate_degrees``, ``transform_min_crop_ratio``,
-        ``normalize``.  ``transform_time_dilation`` is the dataset's (the frame window is picked before the host resize)."""
+        ``normalize``, and ``frames`` / ``img_size`` (the resize of raw batches).  ``transform_time_dilation`` is the dataset's (it picks
+        the frame window)."""
         return cls(model, normalize=bool(data_cfg.get("normalize", True)), augment=bool(data_cfg.get("augmentation", False)),
                    rotate_degrees=float(data_cfg.get("transform_rotate_degrees", 0.0) or 0.0),
-                   min_crop_ratio=float(data_cfg.get("transform_min_crop_ratio", 1.0) or 1.0), seed=seed)
+                   min_crop_ratio=float(data_cfg.get("transform_min_crop_ratio", 1.0) or 1.0), seed=seed,
+                   frames=data_cfg.get("frames"), img_size=data_cfg.get("img_size"))
+
+    def resize(self, raw: "RawCineBatch", out_dtype: torch.dtype = torch.float32, normalize: bool = False) -> torch.Tensor:
+        """One ``pasn_cine_resize`` launch: the batch's windows resized to (N,1,frames,img_size,img_size) ((N,1,img_size,img_size) for
+        an image model) in [0, 1], or normalised by ``bin_to_norm`` in the epilogue when ``normalize``.  A host batch is uploaded
+        asynchronously first."""
+        if self.img_size is None or (self.video and self.frames is None):
+            raise ValueError("resizing a RawCineBatch needs the output shape: DeviceClipPipeline(frames=..., img_size=...) or from_config "
+                             "with the data config's frames / img_size")
+        if raw.device != self.device:
+            raw = raw.to(self.device, non_blocking=True)
+        frames = self.frames if self.video else 1
+        mean, std = (ECHO_MEAN, ECHO_STD) if normalize else (0.0, 1.0)
+        y = resample.resize_raw(raw, (frames, self.img_size, self.img_size), out_dtype, mean, std)
+        return y.unsqueeze(1) if self.video else y.reshape(len(raw), 1, self.img_size, self.img_size)
 
     def _grey(self, cine: torch.Tensor) -> torch.Tensor:
         x = cine
@@ -153,10 +285,17 @@ class DeviceClipPipeline:
             raise GreyInputError("the trunk carries an input normalisation this pipeline did not set (set_input_normalization or another "
                                  "DeviceClipPipeline); normalized() would drop it, and a normalised grey clip on top of it would be normalised "
                                  "twice.  Call set_input_normalization(None) first, or train on the reference's 3-channel clip")
+        out_dtype = self.model._dtype() if hasattr(self.model, "_dtype") else torch.float32
+        if isinstance(cine, RawCineBatch):
+            if not augment:  # resize + bin_to_norm: one launch
+                y = self.resize(cine, out_dtype, normalize=self.normalize)
+                self.trunk.set_input_normalization(None)
+                self._affine = tuple(self.trunk.input_affine)
+                return y
+            cine = self.resize(cine, torch.float32)  # the reference resizes first, then crops and rotates
         x = self._grey(cine).contiguous().to(self.device, non_blocking=True)
         n, height, width = x.shape[0], x.shape[-2], x.shape[-1]
         frames = x.shape[2] if x.dim() == 5 else 1
-        out_dtype = self.model._dtype() if hasattr(self.model, "_dtype") else torch.float32
         y = torch.empty(x.shape, dtype=out_dtype, device=self.device)
         params = self._params(n, height, width, augment)
         mean, std = (ECHO_MEAN, ECHO_STD) if self.normalize else (0.0, 1.0)
@@ -170,6 +309,8 @@ class DeviceClipPipeline:
     def __call__(self, cine: torch.Tensor) -> torch.Tensor:
         if self.model.training:
             return self.normalized(cine, self.augment)
+        if isinstance(cine, RawCineBatch):
+            cine = self.resize(cine, self.model._dtype() if hasattr(self.model, "_dtype") else torch.float32)
         x = self._grey(cine)
         scale = 1.0 / 255.0 if x.dtype == torch.uint8 else 1.0
         if self.normalize:

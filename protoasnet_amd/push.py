@@ -133,6 +133,11 @@ def _labels_to_device(labels, device, pinned: list) -> torch.Tensor:
     return stage.to(device, non_blocking=True)
 
 
+def batch_len(cine) -> int:
+    """Clips in a batch's ``cine``: a clip tensor's first dimension, or a ``data.RawCineBatch``'s length."""
+    return int(len(cine))
+
+
 def _iter_shard(dataloader, rank: int, world_size: int):
     """Yields ``(batch index, global index of the batch's first clip, sample)`` for this rank's contiguous batch range.
 
@@ -164,7 +169,7 @@ def _iter_shard(dataloader, rank: int, world_size: int):
             break
         if i >= mine.start:
             yield i, (i * batch_size if batch_size else seen), sample
-        seen += int(sample["cine"].shape[0])
+        seen += batch_len(sample["cine"])
 
 
 def _finish(model, state_tensors, prototype_shape, replace_prototypes: bool, log, start: float) -> Dict[str, torch.Tensor]:

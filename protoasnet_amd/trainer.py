@@ -96,6 +96,7 @@ class DPTrainer:
         self.scheduler = self.get_lr_scheduler()
         self.params = [p for g in self.optimizer.param_groups for p in g["params"]]
         self._clip_pipe = None  # built on the first single-channel batch (clip_pipeline)
+        self._copy_stream = None  # side stream of raw-batch uploads (staged)
         self.sync_model_state()  # ranks built from different seeds / checkpoints would otherwise stay different models for ever
 
     # ---- one model on every rank ------------------------------------------------------------------------------------------------
@@ -241,10 +242,41 @@ class DPTrainer:
         """A batch's ``cine`` as the model takes it: a 3-channel clip moves to the device as it is; a single-channel (N,1,...) clip
         (fp32 / bf16 in [0, 1], or uint8) becomes the normalised grey clip in ONE launch, augmented in ``train`` epochs when the config's
         ``data.augmentation`` says so (the reference's train split; val, test and push clips are never augmented)."""
-        if cine.dim() >= 4 and cine.shape[1] == 1:
+        if isinstance(cine, data.RawCineBatch) or (cine.dim() >= 4 and cine.shape[1] == 1):
             pipe = self.clip_pipeline()
             return pipe.normalized(cine, train and pipe.augment)
         return cine.to(self.device, non_blocking=True)
+
+    def staged(self, loader):
+        """The loader's samples, each raw batch (``data.RawCineBatch``) already uploaded: batch i + 1's copy is issued on a side stream
+        before batch i is handed out, so it overlaps step i; the resize waits on the copy's event (``RawCineBatch.ready``)."""
+        pending = None
+        for sample in loader:
+            if self.device.type == "cuda" and isinstance(sample, dict) and isinstance(sample.get("cine"), data.RawCineBatch):
+                sample = dict(sample, cine=self._upload_raw(sample["cine"]))
+                if pending is not None:
+                    yield pending
+                pending = sample
+                continue
+            if pending is not None:  # clip batches are handed out as they come
+                yield pending
+                pending = None
+            yield sample
+        if pending is not None:
+            yield pending
+
+    def _upload_raw(self, raw: "data.RawCineBatch") -> "data.RawCineBatch":
+        if raw.device == self.device:
+            return raw
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(self.device)
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self._copy_stream):
+            dev = raw.to(self.device, non_blocking=True)
+            dev.ready = torch.cuda.Event()
+            dev.ready.record(self._copy_stream)
+        dev.buffer.record_stream(main)  # allocated on the copy stream, read on the compute stream
+        return dev
 
     # ---- Video_XProtoNet_e2e.py:36-361, minus the per-batch host work ------------------------------------------------------------
     def compute_loss(self, inp, target, logit, similarities, occurrence_map, occurrence_map_transformed=None, affine_config=None):
@@ -288,7 +320,7 @@ class DPTrainer:
         ev = self.evaluator(loader, keep_logits=write_csv)  # None on a CPU model: its epoch dict stays the confusion-matrix one
         metas = []
         with torch.set_grad_enabled(mode == "train"):
-            for i, sample in enumerate(loader):
+            for i, sample in enumerate(self.staged(loader)):
                 inp = self.prepare_input(sample["cine"], train=mode == "train")
                 target = sample["target_AS"].to(self.device, non_blocking=True)
                 if warp_in_batch:  # the reference's second trunk pass (loss.py:302) shares the launch list of the first
