@@ -670,6 +670,49 @@ int pasn_cine_resize(const void* src, long src_bytes, const long long* desc, con
                      int in_dtype, int out_dtype, void* stream);
 
 /*
+ * The training loss recipe in the library (csrc/proto_loss.hip): the seven terms of XProtoNet_Base.py:54-81 as
+ * Video_XProtoNet_e2e.py:86-110 applies them -- the classes of src/loss/loss.py:23-254 and :323-371 -- and the per-batch statistics of
+ * Video_XProtoNet_e2e.py:112-153, replacing their eager tensor expressions and what autograd replays for them.  A term whose weight is 0
+ * is skipped, as the reference returns before computing it, and its slot is 0.  reduction: 0 = 'mean' (batch mean, then the sum over
+ * classes / prototypes), 1 = 'sum'.
+ *   ce_mode 0: CeLoss (loss.py:23-34) on logits [N][K];  1 / 2: CeLossAbstain (loss.py:323-371) with the 'joined' / 'separate' logit path,
+ *              K - 1 >= 2 real classes and the abstention output in column K - 1; ab_weight as there
+ *   scores [N][P]: ClusterRoiFeat / SeparationRoiFeat (loss.py:98-186) on similarities -- the per-class MAXIMUM over the C class-major
+ *              prototype groups of P / C; sep_abstain: class C - 1 is never penalised.  patch = 1: ClusterPatch / SeparationPatch
+ *              (loss.py:37-95) on min_distances -- the per-class MINIMUM and the opposite signs
+ *   protos [P][D]: OrthogonalityLoss (loss.py:189-231), ortho_mode 0 = 'per_class' (the same C groups), 1 = 'all': the upper triangle of
+ *              the pairwise cosine similarities, each vector divided by max(|v|, 1e-8) as torch.nn.functional.cosine_similarity does
+ *   occ [N][P][S], map_dtype PASN_F32 / PASN_BF16: L_norm (loss.py:234-254) with map_p = 1 / 2 over each row of S map elements
+ *   fc_w [fc_rows][P] (+ fc_mask of the same shape, or NULL): L_norm with fc_p = 1 / 2 over the whole masked weight
+ * Labels outside the classes are clamped into them (the eager path raises a device assertion there).
+ */
+typedef struct pasn_proto_loss_desc {
+    int32_t N, K, K_real;            /* rows; logit columns; real classes of the confusion matrix (<= K) */
+    int32_t P, D, C, fc_rows;        /* prototypes, prototype depth, prototype classes (groups), rows of the last layer's weight */
+    int64_t S;                       /* elements of one (clip, prototype) map row */
+    int32_t ce_mode, ce_reduction, cluster_reduction, sep_reduction, sep_abstain, patch, ortho_mode, map_p, map_reduction, fc_p, map_dtype;
+    float w_ce, ab_weight, w_cluster, w_sep, w_ortho, w_map, w_fc;
+} pasn_proto_loss_desc;
+
+/* Forward, at most two launches, no host synchronisation.  terms [7] fp32: the weighted terms in the trainer's order (cross entropy,
+ * cluster, separation, orthogonality, map norm, transform, last-layer norm); loss [1]: their sum, added in that order.  transform_term:
+ * the already weighted TransformLoss value (losses.py / warp.hip) as a device scalar, NULL = 0.  workspace: N * P + P floats, written
+ * here and read by the backward (row norms, per-prototype orthogonality sums); may be NULL when w_map and w_ortho are 0.  Optional epoch
+ * statistics, accumulated in the same launch: cm [K_real][K_real] int64 += 1 at (label clamped to [0, K_real), first largest of the
+ * K_real real-class logits); loss_sum [7] fp32 += terms.  Every sum runs in a fixed order: two calls are bitwise equal. */
+int pasn_proto_loss_fwd(const float* logits, const float* scores, const int64_t* target, const float* protos, const void* occ,
+                        const float* fc_w, const float* fc_mask, const float* transform_term, float* terms, float* loss, float* workspace,
+                        int64_t* cm, float* loss_sum, const pasn_proto_loss_desc* d, void* stream);
+
+/* Backward of pasn_proto_loss_fwd for the upstream gradient grad_loss, a DEVICE scalar; at most two launches.  Every non-NULL output is
+ * fully written (zeros where its terms are off); NULL skips that gradient (a frozen parameter).  d_occ has the maps' dtype.  Subgradients
+ * as autograd takes them: sign(0) = 0, an all-zero row or weight under p = 2 gets zero, a tied per-class maximum / minimum sends its
+ * gradient to the first index.  The transform term's gradient is grad_loss itself and is left to the caller. */
+int pasn_proto_loss_bwd(const float* grad_loss, const float* logits, const float* scores, const int64_t* target, const float* protos,
+                        const void* occ, const float* fc_w, const float* fc_mask, const float* workspace, float* d_logits, float* d_scores,
+                        float* d_protos, void* d_occ, float* d_fc_w, const pasn_proto_loss_desc* d, void* stream);
+
+/*
  * Training: all conv weights of a step packed from the live fp32 parameters into the layouts the forward kernels read, in ONE launch
  * (replaces the per-parameter torch expressions of the host side: the reference has no counterpart -- cuDNN reads the parameters as they
  * are, model/XProtoNet.py keeps nn.Conv modules).  `jobs`, `block_job`, `block_chunk` are DEVICE arrays: block b packs destination

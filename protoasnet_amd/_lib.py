@@ -27,6 +27,13 @@ class XProtoDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("N", "S", "Cb", "Cbp", "D", "Dp", "Hd", "Hp", "P", "Pp", "K", "mode")]
 
 
+class ProtoLossDesc(ctypes.Structure):
+    _fields_ = ([(n, c_int32) for n in ("N", "K", "K_real", "P", "D", "C", "fc_rows")] + [("S", c_int64)]
+                + [(n, c_int32) for n in ("ce_mode", "ce_reduction", "cluster_reduction", "sep_reduction", "sep_abstain", "patch", "ortho_mode",
+                                          "map_p", "map_reduction", "fc_p", "map_dtype")]
+                + [(n, c_float) for n in ("w_ce", "ab_weight", "w_cluster", "w_sep", "w_ortho", "w_map", "w_fc")])
+
+
 # name -> (restype, argtypes); every symbol the header declares
 SIGNATURES = {
     "pasn_version": (c_int, []),
@@ -139,6 +146,9 @@ SIGNATURES = {
     "pasn_eval_batch_stats": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_float, c_long, c_long] + [c_void_p] * 7),
     "pasn_roc_auc_workspace_bytes": (c_size_t, [c_long, c_int]),
     "pasn_roc_auc_ovr": (c_int, [c_void_p, c_void_p, c_long, c_int] + [c_void_p] * 4),
+    # ---- the training loss recipe (losses.FusedCriterion)
+    "pasn_proto_loss_fwd": (c_int, [c_void_p] * 13 + [POINTER(ProtoLossDesc), c_void_p]),
+    "pasn_proto_loss_bwd": (c_int, [c_void_p] * 14 + [POINTER(ProtoLossDesc), c_void_p]),
     # ---- raw cine windows -> model clips (resample.py)
     "pasn_cine_resize_pixels_per_block": (c_int, [c_int]),
     "pasn_cine_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p] + [c_int] * 10 + [c_float] * 2 + [c_int] * 2 + [c_void_p]),

@@ -8,6 +8,7 @@ the (N, P, T', H', W') maps is a plain torch op on a tiny tensor.  Same construc
 reference class, so an agent swaps the import only.  No torchvision is needed (it is absent from this image)."""
 from __future__ import annotations
 
+import ctypes
 import random
 
 import torch
@@ -236,3 +237,170 @@ class CeLossAbstain(object):
         loss_abs = -torch.log(1 - abstain).squeeze()
         loss_abs = loss_abs.mean() if self.reduction == "mean" else loss_abs.sum() if self.reduction == "sum" else loss_abs
         return self.loss_weight * (loss_pred + self.ab_weight * loss_abs)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# The same recipe in the library: ``pasn_proto_loss_fwd`` / ``_bwd`` (csrc/proto_loss.hip) compute the seven terms of a training
+# step (XProtoNet_Base.py:54-81 as Video_XProtoNet_e2e.py:86-110 applies them), their sum and the epoch statistics in at most two
+# launches each way, where the classes above cost a few dozen eager launches forward and again under autograd.
+# --------------------------------------------------------------------------------------------------------------------------
+def _reduction_code(reduction):
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"{reduction} is not a valid value for reduction")  # what torch's criteria say (loss.py:25,336)
+    return 0 if reduction == "mean" else 1
+
+
+def _norm_p(loss, what):
+    if loss.loss_weight != 0 and loss.p not in (1, 2):
+        raise ValueError(f"L_norm of {what}: p must be 1 or 2, not {loss.p!r}")
+    return int(loss.p) if loss.p in (1, 2) else 1
+
+
+class _FusedLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, crit, target, stats, logit, scores, occ, protos, fc_w, transform_term):
+        d, mask = crit._describe(logit, scores, occ, protos, fc_w)
+        dev = logit.device
+        logit, scores, target = logit.contiguous(), scores.contiguous(), target.contiguous()
+        occ = None if occ is None or d.w_map == 0 else occ.contiguous()
+        protos = None if protos is None else protos.contiguous()
+        fc_w = None if fc_w is None else fc_w.contiguous()
+        tt = None if transform_term is None else transform_term.detach().float().reshape(1)
+        out = torch.empty(8, dtype=torch.float32, device=dev)  # the seven terms, then their sum
+        ws = torch.empty(d.N * d.P + d.P, dtype=torch.float32, device=dev) if (d.w_map != 0 or d.w_ortho != 0) else None
+        cm, loss_sum = stats if stats is not None else (None, None)
+        _lib.check(_lib.lib().pasn_proto_loss_fwd(logit.data_ptr(), scores.data_ptr(), target.data_ptr(), _lib.ptr(protos), _lib.ptr(occ),
+                                                  _lib.ptr(fc_w), _lib.ptr(mask), _lib.ptr(tt), out.data_ptr(), out[7:].data_ptr(), _lib.ptr(ws),
+                                                  _lib.ptr(cm), _lib.ptr(loss_sum), ctypes.byref(d), _lib.current_stream()))
+        ctx.desc = d
+        ctx.save_for_backward(logit, scores, target, protos, occ, fc_w, mask, ws)
+        terms = out[:7]
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)  # no zero-filled gradient for the terms
+        return out[7], terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        if grad_loss is None:
+            return (None,) * 9
+        d = ctx.desc
+        logit, scores, target, protos, occ, fc_w, mask, ws = ctx.saved_tensors
+        need = ctx.needs_input_grad[3:]
+        g = grad_loss.detach().float().contiguous().reshape(1)  # stays on the device
+        d_logit = torch.empty_like(logit) if need[0] else None
+        d_scores = torch.empty_like(scores) if need[1] else None
+        d_occ = torch.empty_like(occ) if need[2] and occ is not None else None  # weight 0: no gradient (None is autograd's zero)
+        d_protos = torch.empty_like(protos) if need[3] and protos is not None and d.w_ortho != 0 else None
+        d_fc = torch.empty_like(fc_w) if need[4] and fc_w is not None and d.w_fc != 0 else None
+        if any(t is not None for t in (d_logit, d_scores, d_occ, d_protos, d_fc)):
+            _lib.check(_lib.lib().pasn_proto_loss_bwd(g.data_ptr(), logit.data_ptr(), scores.data_ptr(), target.data_ptr(), _lib.ptr(protos),
+                                                      _lib.ptr(occ), _lib.ptr(fc_w), _lib.ptr(mask), _lib.ptr(ws), _lib.ptr(d_logit),
+                                                      _lib.ptr(d_scores), _lib.ptr(d_protos), _lib.ptr(d_occ), _lib.ptr(d_fc), ctypes.byref(d),
+                                                      _lib.current_stream()))
+        return None, None, None, d_logit, d_scores, d_occ, d_protos, d_fc, (grad_loss if need[5] else None)
+
+
+class FusedCriterion(object):
+    """The seven loss objects of a trainer (``CeLoss`` or ``CeLossAbstain``; ``ClusterRoiFeat`` + ``SeparationRoiFeat`` or the ProtoPNet
+    pair ``ClusterPatch`` + ``SeparationPatch``; ``OrthogonalityLoss``; the two ``L_norm``; ``TransformLoss``) evaluated by ONE library call.
+    ``transform`` stays what it is -- its value enters ``compute`` as ``transform_term``; ``orthogonality`` / ``lnorm_occurrence`` /
+    ``lnorm_fc`` may be None (weight 0).  Construction needs no device and checks what the kernels cover; ``compute`` runs on the GPU
+    only."""
+
+    TERMS = ("ce", "cluster", "separation", "orthogonality", "lnorm_occurrence", "transform", "lnorm_fc")
+
+    def __init__(self, ce, cluster, separation, orthogonality=None, lnorm_occurrence=None, transform=None, lnorm_fc=None):
+        self.ce, self.cluster, self.separation = ce, cluster, separation
+        self.orthogonality = orthogonality or OrthogonalityLoss(0)
+        self.lnorm_occurrence = lnorm_occurrence or L_norm(loss_weight=0)
+        self.transform = transform or TransformLoss(0)
+        self.lnorm_fc = lnorm_fc or L_norm(loss_weight=0)
+        if isinstance(ce, CeLossAbstain):
+            if ce.ab_logitpath not in ("joined", "separate"):
+                raise AssertionError("ab_logitpath must be 'joined' or 'separate'")
+            self.ce_mode = 1 if ce.ab_logitpath == "joined" else 2
+        elif isinstance(ce, CeLoss):
+            self.ce_mode = 0
+        else:
+            raise TypeError(f"ce must be a CeLoss or a CeLossAbstain, not {type(ce).__name__}")
+        patch = isinstance(cluster, ClusterPatch), isinstance(separation, SeparationPatch)
+        if patch[0] != patch[1] or not isinstance(cluster, (ClusterPatch, ClusterRoiFeat)) or not isinstance(separation, (SeparationPatch, SeparationRoiFeat)):
+            raise TypeError("cluster / separation must be ClusterRoiFeat + SeparationRoiFeat or ClusterPatch + SeparationPatch")
+        self.patch = int(patch[0])
+        if cluster.num_classes != separation.num_classes or (self.orthogonality.loss_weight != 0 and self.orthogonality.num_classes != cluster.num_classes):
+            raise ValueError("the cluster, separation and orthogonality costs must group the prototypes into the same number of classes")
+        if self.orthogonality.mode not in ("per_class", "all"):
+            raise ValueError("mode must be 'per_class' or 'all'")
+        self.reductions = [_reduction_code(x.reduction) for x in (ce, cluster, separation)]
+        self.map_reduction = _reduction_code(self.lnorm_occurrence.reduction) if self.lnorm_occurrence.loss_weight != 0 else 1
+        self.map_p, self.fc_p = _norm_p(self.lnorm_occurrence, "the occurrence maps"), _norm_p(self.lnorm_fc, "the last layer")
+        if self.lnorm_occurrence.mask is not None:
+            raise ValueError("L_norm of the occurrence maps takes no mask")
+        self._mask = None
+
+    @classmethod
+    def from_config(cls, criterion: dict, model, abstain_class: bool) -> "FusedCriterion":
+        """From a ``train.criterion`` block of the reference's XProto configs, as ``XProtoNet_Base.get_criterion`` reads it (:54-81)."""
+        cfg, K = criterion, model.num_classes
+        ce = CeLossAbstain(**cfg["CeLossAbstain"]) if abstain_class else CeLoss(**cfg["CeLoss"])
+        return cls(ce, ClusterRoiFeat(num_classes=K, **cfg["ClusterRoiFeat"]),
+                   SeparationRoiFeat(num_classes=K, **cfg["SeparationRoiFeat"], abstain_class=bool(abstain_class)),
+                   OrthogonalityLoss(num_classes=K, **cfg["OrthogonalityLoss"]), L_norm(**cfg["Lnorm_occurrence"]),
+                   TransformLoss(**cfg["trans_occurrence"]), L_norm(**cfg["Lnorm_FC"], mask=1 - torch.t(model.prototype_class_identity)))
+
+    def _describe(self, logit, scores, occ, protos, fc_w):
+        for name, t in (("logit", logit), ("similarities", scores), ("prototype_vectors", protos), ("fc_weight", fc_w)):
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError(f"FusedCriterion: {name} must be float32, not {t.dtype}")
+        if logit.dim() != 2 or scores.dim() != 2 or scores.shape[0] != logit.shape[0]:
+            raise ValueError("FusedCriterion: logit is (N, K) and similarities (N, P)")
+        d = _lib.ProtoLossDesc()
+        d.N, d.K, d.P = logit.shape[0], logit.shape[1], scores.shape[1]
+        d.K_real = d.K - 1 if self.ce_mode else d.K
+        d.C, d.patch = self.cluster.num_classes, self.patch
+        d.ce_mode, d.ab_weight = self.ce_mode, float(getattr(self.ce, "ab_weight", 0.0))
+        d.ce_reduction, d.cluster_reduction, d.sep_reduction = self.reductions
+        d.sep_abstain = int(bool(getattr(self.separation, "abstain_class", False)))
+        d.ortho_mode, d.map_p, d.map_reduction, d.fc_p = int(self.orthogonality.mode == "all"), self.map_p, self.map_reduction, self.fc_p
+        d.w_ce, d.w_cluster, d.w_sep = float(self.ce.loss_weight), float(self.cluster.loss_weight), float(self.separation.loss_weight)
+        d.w_ortho = float(self.orthogonality.loss_weight) if protos is not None else 0.0
+        d.w_map = float(self.lnorm_occurrence.loss_weight) if occ is not None else 0.0
+        d.w_fc = float(self.lnorm_fc.loss_weight) if fc_w is not None else 0.0
+        if protos is not None:
+            if protos.shape[0] != d.P or protos.numel() != d.P * protos.shape[1]:
+                raise ValueError("FusedCriterion: prototype_vectors is (P, D, 1, ...)")
+            d.D = protos.shape[1]
+        if occ is not None and d.w_map != 0:
+            if occ.shape[0] != d.N or occ.shape[1] != d.P:
+                raise ValueError("FusedCriterion: occurrence_map is (N, P, 1, [T,] H, W)")
+            d.S, d.map_dtype = occ.numel() // (d.N * d.P), _lib.dtype_code(occ.dtype)
+        mask = None
+        if fc_w is not None and d.w_fc != 0:
+            if fc_w.dim() != 2 or fc_w.shape[1] != d.P:
+                raise ValueError("FusedCriterion: fc_weight is (K, P)")
+            d.fc_rows = fc_w.shape[0]
+            if self.lnorm_fc.mask is not None:
+                if self._mask is None or self._mask.device != fc_w.device:
+                    self._mask = self.lnorm_fc.mask.to(device=fc_w.device, dtype=torch.float32).contiguous()
+                if self._mask.shape != fc_w.shape:
+                    raise ValueError("FusedCriterion: the mask of the last-layer norm must have the weight's shape")
+                mask = self._mask
+        return d, mask
+
+    def compute(self, logit, similarities, occurrence_map, prototype_vectors, fc_weight, target, transform_term=None, stats=None):
+        """``(loss, terms)``: the differentiable sum and the detached (7,) fp32 vector of the weighted terms in ``TERMS`` order.
+        ``transform_term``: the value of ``TransformLoss.compute`` / ``compute_from_maps`` (None = 0); it is added in the launch and
+        receives the upstream gradient.  ``stats = (cm, loss_sum)``: a (K_real * K_real) int64 confusion matrix [label, prediction] and
+        a (7,) fp32 vector, both updated in the same launch."""
+        for t in (logit, similarities, occurrence_map, prototype_vectors, fc_weight, target, transform_term) + tuple(stats or ()):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("protoasnet_amd.losses run on the GPU only; there is no CPU fallback")
+        if target.dtype != torch.int64:
+            target = target.long()
+        if stats is not None:
+            cm, loss_sum = stats
+            k = logit.shape[1] - 1 if self.ce_mode else logit.shape[1]
+            if cm.dtype != torch.int64 or cm.numel() != k * k or loss_sum.dtype != torch.float32 or loss_sum.numel() != 7 or not (
+                    cm.is_contiguous() and loss_sum.is_contiguous()):
+                raise ValueError("FusedCriterion: stats is (int64 confusion matrix of K_real * K_real, float32 loss_sum of 7), both contiguous")
+        return _FusedLossFn.apply(self, target, stats, logit, similarities, occurrence_map, prototype_vectors, fc_weight, transform_term)

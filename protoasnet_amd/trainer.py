@@ -171,6 +171,11 @@ class DPTrainer:
         self.Lnorm_occurrence = losses.L_norm(**cfg["Lnorm_occurrence"])
         self.Trans_occurrence = losses.TransformLoss(**cfg["trans_occurrence"])
         self.Lnorm_fc = losses.L_norm(**cfg["Lnorm_FC"], mask=1 - torch.t(self.model.prototype_class_identity))
+        # train.fused_loss (not a key of the reference's configs; default off): the same seven objects evaluated by one library call
+        self.fused = None
+        if self.train_config.get("fused_loss", False):
+            self.fused = losses.FusedCriterion(self.CeLoss, self.Cluster, self.Separation, self.Orthogonality, self.Lnorm_occurrence,
+                                               self.Trans_occurrence, self.Lnorm_fc)
 
     # ---- XProtoNet_e2e.py:36-82 --------------------------------------------------------------------------------------------------
     def get_optimizer(self) -> None:
@@ -279,7 +284,16 @@ class DPTrainer:
         return dev
 
     # ---- Video_XProtoNet_e2e.py:36-361, minus the per-batch host work ------------------------------------------------------------
-    def compute_loss(self, inp, target, logit, similarities, occurrence_map, occurrence_map_transformed=None, affine_config=None):
+    def compute_loss(self, inp, target, logit, similarities, occurrence_map, occurrence_map_transformed=None, affine_config=None, stats=None):
+        if self.fused is not None:  # ``stats``: the epoch's (confusion matrix, loss_sum), updated in the criterion's launch
+            if self.Trans_occurrence.loss_weight == 0:
+                trans = None
+            elif occurrence_map_transformed is not None:
+                trans = self.Trans_occurrence.compute_from_maps(occurrence_map, occurrence_map_transformed, affine_config)
+            else:
+                trans = self.Trans_occurrence.compute(inp, occurrence_map, self.model)
+            return self.fused.compute(logit, similarities, occurrence_map, self.model.prototype_vectors, self.model.last_layer.weight, target,
+                                      transform_term=trans, stats=stats)
         terms = [
             self.CeLoss.compute(logits=logit, target=target),
             self.Cluster.compute(similarities, target),
@@ -303,6 +317,7 @@ class DPTrainer:
         cm = torch.zeros(K * K, dtype=torch.int64, device=self.device)
         loss_sum = torch.zeros(7, dtype=torch.float32, device=self.device)
         n_batches = 0
+        fused_stats = {"stats": (cm, loss_sum)} if self.fused is not None else {}
         if self.world_size > 1:
             if hasattr(loader, "__len__"):  # a rank with fewer micro-batches would issue fewer collectives: the job would hang in RCCL
                 n = torch.tensor([len(loader), -len(loader)], dtype=torch.int64, device=self.device)
@@ -333,13 +348,14 @@ class DPTrainer:
                         logit, similarities, occurrence_map = self.model(torch.cat([inp, warped]))
                         occ_t = occurrence_map[nb:]
                         logit, similarities, occurrence_map = logit[:nb], similarities[:nb], occurrence_map[:nb]
-                    loss, terms = self.compute_loss(inp, target, logit, similarities, occurrence_map, occ_t, cfg)
+                    loss, terms = self.compute_loss(inp, target, logit, similarities, occurrence_map, occ_t, cfg, **fused_stats)
                 else:
                     logit, similarities, occurrence_map = self.model(inp)
-                    loss, terms = self.compute_loss(inp, target, logit, similarities, occurrence_map)
-                pred = logit[:, :K].argmax(dim=1)  # softmax is monotone: the class of the largest real-class logit
-                cm += torch.bincount(target.clamp(0, K - 1) * K + pred, minlength=K * K)
-                loss_sum += terms
+                    loss, terms = self.compute_loss(inp, target, logit, similarities, occurrence_map, **fused_stats)
+                if not fused_stats:  # (the fused criterion counted and summed in its launch)
+                    pred = logit[:, :K].argmax(dim=1)  # softmax is monotone: the class of the largest real-class logit
+                    cm += torch.bincount(target.clamp(0, K - 1) * K + pred, minlength=K * K)
+                    loss_sum += terms
                 n_batches += 1
                 if ev is not None:
                     ev.update(logit, similarities, target)
