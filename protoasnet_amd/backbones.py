@@ -316,80 +316,78 @@ class X3DFeatures(_plan.HipTrunk):
         x = pb.x3d_stem(x, self.stem.conv_xy, self.stem.conv_t, self.stem.bn)  # one T-marching launch (two if unsupported)
         for stage in self.stages:
             blocks = list(stage)
+            edp = self._whole_blocks(pb, x, blocks)
             pre = None  # this block's expand-conv output when the previous block's chained launch already made it
-            edp = [False] * len(blocks)  # blocks that run as ONE launch (expand -> stencil -> project [-> next expand]): 7 x 7 planes, no squeeze-excite
             for i, blk in enumerate(blocks):
-                sc = x
-                if i == 0:  # (behind the stage's first block the shape is fixed: decide for the whole stage before any pairing)
-                    sb = _plan._triple(blk.conv_b.stride, 1)
-                    co = blk.conv_c.out_channels
-                    xs = _plan.Act(x.N, x.T, (x.H - 1) // sb[1] + 1, (x.W - 1) // sb[2] + 1, co, _plan.round_up(co, 8), -1)
-                    edp = [j >= 1 and b.se is None and b.shortcut is None and bool(pb.x3d_edp(xs, b.conv_a, b.bn_a, b.conv_b, b.bn_b, b.conv_c, b.bn_c, probe=True))
-                           for j, b in enumerate(blocks)]
+                # the next block where its expand conv may ride in this block's last launch (a whole-block launch makes its own)
+                nxt = blocks[i + 1] if i + 1 < len(blocks) and blocks[i + 1].shortcut is None and not edp[i + 1] else None
+                whole = None
                 if edp[i] and pre is None:
-                    nb_ = blocks[i + 1] if i + 1 < len(blocks) else None
-                    chain = nb_ is not None and nb_.shortcut is None and not edp[i + 1]
-                    whole = pb.x3d_edp(x, blk.conv_a, blk.bn_a, blk.conv_b, blk.bn_b, blk.conv_c, blk.bn_c, nb_.conv_a if chain else None, nb_.bn_a if chain else None)
-                    if whole is not None:
-                        x, pre = whole
-                        continue
-                fuse_short = blk.shortcut is not None and pb.short_fusable(x, blk)  # the strided shortcut conv rides in the project conv's launch
-                if blk.shortcut is not None and not fuse_short:
-                    sc = pb.conv(x, blk.shortcut.conv, blk.shortcut.bn, act="none")
-                act_b = "none" if blk.se is not None else "swish"  # no gate between BN and Swish: the stencil applies Swish
-                gate = None
-                # expand conv + stencil in one launch where the pair is covered (block width <= 48): the expanded activation never leaves LDS
-                front = pb.expand_dw(x, blk.conv_a, blk.bn_a, blk.conv_b, blk.bn_b, act_b, pool=blk.se is not None) if pre is None else None
-                if front is not None:
-                    if blk.se is not None:
-                        y, pooled = front
-                        gate = pb.se_gate_or_prologue(y, pooled, blk.se.fc1, blk.se.fc2, consumer=(blk.conv_c, True))
-                    else:
-                        y = front
-                e = None if front is not None else pre if pre is not None else pb.conv(x, blk.conv_a, blk.bn_a, act="relu")
-                if front is not None:
-                    pass
-                elif blk.se is not None:
-                    # stencil + gate in one launch where that pays; where the project conv can compute the gate in its own prologue, only
-                    # the pool partial rows are produced here (gate = ("pooled", ...))
-                    y, gate = pb.dwconv_se(e, blk.conv_b, blk.bn_b, blk.se.fc1, blk.se.fc2, consumer=(blk.conv_c, True))
-                else:
-                    y = pb.dwconv(e, blk.conv_b, blk.bn_b, act=act_b)
-                # project conv; where the geometry allows, chained in ONE launch with the next block's expand conv
-                nxt = blocks[i + 1] if i + 1 < len(blocks) else None
-                pair = None
-                if isinstance(gate, tuple):  # squeeze-excite gate in the project conv's prologue
-                    if fuse_short:  # (not combined with the fused shortcut: different kernels)
-                        sc = pb.conv(x, blk.shortcut.conv, blk.shortcut.bn, act="none")
-                        fuse_short = False
-                    if nxt is not None and nxt.shortcut is None and not edp[i + 1]:  # ... chained with the next block's expand conv where that is covered (a whole-block launch makes its own)
-                        pair = pb.conv_pair(y, blk.conv_c, blk.bn_c, "relu", sc, nxt.conv_a, nxt.bn_a, "relu", in_swish=True,
-                                            se=(gate[1], blk.se.fc1, blk.se.fc2))
-                        if pair is not None:
-                            x, pre = pair
-                            continue
-                    yc = pb.conv_se(y, blk.conv_c, blk.bn_c, "relu", sc, gate[1], blk.se.fc1, blk.se.fc2)
-                    if yc is not None:
-                        x, pre = yc, None
-                        continue
-                    gate = pb.se_gate(gate[1], blk.se.fc1, blk.se.fc2)
-                if fuse_short:
-                    fused = pb.conv_short(y, blk.conv_c, blk.bn_c, "relu", x, blk.shortcut.conv, blk.shortcut.bn, in_gate=gate,
-                                          in_swish=blk.se is not None)
-                    if fused is None:  # (short_fusable said yes on the same descriptors; kept for safety)
-                        sc = pb.conv(x, blk.shortcut.conv, blk.shortcut.bn, act="none")
-                    else:
-                        x, pre = fused, None
-                        continue
-                if nxt is not None and nxt.shortcut is None and not edp[i + 1]:
-                    pair = pb.conv_pair(y, blk.conv_c, blk.bn_c, "relu", sc, nxt.conv_a, nxt.bn_a, "relu",
-                                        in_gate=gate, in_swish=blk.se is not None)
-                if pair is not None:
-                    x, pre = pair
-                else:
-                    x = pb.conv(y, blk.conv_c, blk.bn_c, act="relu", residual=sc, in_gate=gate, in_swish=blk.se is not None)
-                    pre = None
+                    whole = pb.x3d_edp(x, blk.conv_a, blk.bn_a, blk.conv_b, blk.bn_b, blk.conv_c, blk.bn_c, nxt.conv_a if nxt else None, nxt.bn_a if nxt else None)
+                if whole is None:
+                    # the residual: the block input, the strided shortcut conv's output, or None while that conv is to ride in the project
+                    # conv's launch (asked BEFORE the block's launches are emitted)
+                    sc = x if blk.shortcut is None else None if pb.short_fusable(x, blk) else self._shortcut(pb, x, blk)
+                    y, gate = self._front_half(pb, x, blk, pre)
+                    whole = self._back_half(pb, x, sc, y, gate, blk, nxt)
+                x, pre = whole
         return x
+
+    @staticmethod
+    def _whole_blocks(pb, x, blocks):
+        """Which blocks of a stage run as ONE launch (expand -> stencil -> project [-> next expand]): 7 x 7 planes, no squeeze-excite.
+        Behind the stage's first block the shape is fixed, so this is decided for the whole stage before any pairing."""
+        sb, co = _plan._triple(blocks[0].conv_b.stride, 1), blocks[0].conv_c.out_channels
+        xs = pb._geom(x, co, (1, 1, 1), sb, (0, 0, 0))
+        return [j >= 1 and b.se is None and b.shortcut is None and bool(pb.x3d_edp(xs, b.conv_a, b.bn_a, b.conv_b, b.bn_b, b.conv_c, b.bn_c, probe=True))
+                for j, b in enumerate(blocks)]
+
+    @staticmethod
+    def _shortcut(pb, x, blk):
+        return pb.conv(x, blk.shortcut.conv, blk.shortcut.bn, act="none")
+
+    @staticmethod
+    def _front_half(pb, x, blk, pre):
+        """Expand conv + stencil (+ squeeze-excite gate) -> (y, gate).  ``gate``: None (no SE: the stencil applies Swish), the gate buffer,
+        or ("pooled", pool partial rows) where the project conv can compute the gate in its own prologue."""
+        se = blk.se
+        act_b = "none" if se is not None else "swish"  # no gate between BN and Swish: the stencil applies Swish
+        consumer = (blk.conv_c, True)
+        # expand conv + stencil in one launch where the pair is covered (block width <= 48): the expanded activation never leaves LDS
+        front = pb.expand_dw(x, blk.conv_a, blk.bn_a, blk.conv_b, blk.bn_b, act_b, pool=se is not None) if pre is None else None
+        if front is not None and se is None:
+            return front, None
+        if front is not None:
+            y, pooled = front
+            return y, pb.se_gate_or_prologue(y, pooled, se.fc1, se.fc2, consumer=consumer)
+        e = pre if pre is not None else pb.conv(x, blk.conv_a, blk.bn_a, act="relu")
+        if se is None:
+            return pb.dwconv(e, blk.conv_b, blk.bn_b, act=act_b), None
+        return pb.dwconv_se(e, blk.conv_b, blk.bn_b, se.fc1, se.fc2, consumer=consumer)  # stencil + gate in one launch where that pays
+
+    def _back_half(self, pb, x, sc, y, gate, blk, nxt):
+        """Project conv + residual (+ the next block's expand conv where ``nxt`` and the geometry allow) -> (x, pre), most fused form first."""
+        se, in_swish = blk.se, blk.se is not None
+        if sc is None and not isinstance(gate, tuple):  # (the gate-in-prologue launches are different kernels: no fused shortcut there)
+            fused = pb.conv_short(y, blk.conv_c, blk.bn_c, "relu", x, blk.shortcut.conv, blk.shortcut.bn, in_gate=gate, in_swish=in_swish)
+            if fused is not None:  # (else: short_fusable said yes on the same descriptors; kept for safety)
+                return fused, None
+        if sc is None:
+            sc = self._shortcut(pb, x, blk)
+        if isinstance(gate, tuple):  # squeeze-excite gate in the project conv's prologue, chained with the next expand conv where covered
+            pair = pb.conv_pair(y, blk.conv_c, blk.bn_c, "relu", sc, nxt.conv_a, nxt.bn_a, "relu", in_swish=True,
+                                se=(gate[1], se.fc1, se.fc2)) if nxt is not None else None
+            if pair is not None:
+                return pair
+            yc = pb.conv_se(y, blk.conv_c, blk.bn_c, "relu", sc, gate[1], se.fc1, se.fc2)
+            if yc is not None:
+                return yc, None
+            gate = pb.se_gate(gate[1], se.fc1, se.fc2)
+        # project conv; where the geometry allows, chained in ONE launch with the next block's expand conv
+        pair = pb.conv_pair(y, blk.conv_c, blk.bn_c, "relu", sc, nxt.conv_a, nxt.bn_a, "relu", in_gate=gate, in_swish=in_swish) if nxt is not None else None
+        if pair is not None:
+            return pair
+        return pb.conv(y, blk.conv_c, blk.bn_c, act="relu", residual=sc, in_gate=gate, in_swish=in_swish), None
 
 
     def build_train(self, tb, x):

@@ -10,6 +10,14 @@
   of a trunk stays a few of its largest layers instead of the sum of all of them,
 * records one closure per launch with all pointers resolved.
 
+Each operand format the kernels define is packed by ONE module-level function: ``pack_conv_weight`` (dense [rows][taps][kc]),
+``fragment_major`` / ``fragment_view`` (its MFMA fragment order, ``frag_steps`` per dtype; the training pass refreshes through the same
+view), ``se_operands`` (squeeze-excite fc pair), ``pack_dw_taps`` (depthwise [taps][Cp]), ``stencil_operands`` (matrix-core stencil).
+A ``PlanBuilder`` method that may answer "not covered" probes first and allocates after: it asks the library with ``_geom`` (output
+extents, no buffer) and ``_probe_desc`` (a descriptor nobody keeps), and only a launch that will be recorded reserves buffers
+(``_alloc``) and appends to ``keep`` -- a declined launch leaves no trace in the arena plan.  ``conv_kernel_name`` /
+``dwconv_kernel_name`` decode the library's variant codes into the instance names of ``meta``.
+
 Replaying is then a tight loop of ctypes calls on torch's current stream -- no allocation (bar the
 output tensor), no host sync, capturable into a hipGraph.  Packed weights are refreshed automatically
 when a parameter changes (``load_state_dict``, optimizer step, ``.to()``).
@@ -86,8 +94,7 @@ def pack_conv_weight(w: torch.Tensor, cin_p: int, dtype: torch.dtype) -> Tuple[t
         w = w.unsqueeze(2)
     cout, cin = w.shape[0], w.shape[1]
     taps = w.shape[2] * w.shape[3] * w.shape[4]
-    kstep = 16 if dtype == torch.bfloat16 else 8
-    kc = round_up(cin_p, kstep)
+    kc = round_up(cin_p, frag_steps(dtype)[0])
     rows = round_up(round_up(cout, 8), 128)
     packed = torch.zeros(rows, taps, kc, dtype=torch.float32, device=w.device)
     packed[:cout, :, :cin] = w.float().permute(0, 2, 3, 4, 1).reshape(cout, taps, cin)
@@ -118,10 +125,81 @@ def stencil_operands(w: torch.Tensor, c: int, cp: int) -> torch.Tensor:
     return out.view(ct, 64, 2, 8).permute(0, 2, 1, 3).to(torch.int16).contiguous()
 
 
-def _igemm_name(inst: int) -> str:
-    """Kernel instance of ``pasn_conv3d_variant`` - 6000 (igemm.hip / igemm_halo.hip): mode*100 + MT*10 + NT."""
-    mode, mt, nt = inst // 100, (inst // 10) % 10, inst % 10
-    return f"igemm_halo_kernel<{nt},{mt},{mode - 1}>" if mode else f"igemm_glds_kernel<{nt},{mt}>"
+def frag_steps(dtype: torch.dtype) -> Tuple[int, int]:
+    """(K elements per MFMA step, elements per lane and half step) of the fragment-major weight layout."""
+    return (16, 8) if dtype == torch.bfloat16 else (8, 4)
+
+
+def fragment_view(wp: torch.Tensor) -> torch.Tensor:
+    """Packed weights [rows][taps][kc] as the strided view [rows / 32][K / kstep][2][32][ch] (K = taps * kc) that IS the fragment-major order."""
+    kstep, ch = frag_steps(wp.dtype)
+    return wp.view(wp.shape[0] // 32, 32, wp[0].numel() // kstep, 2, ch).permute(0, 2, 3, 1, 4)
+
+
+def fragment_major(wp: torch.Tensor) -> torch.Tensor:
+    """Packed weights stored fragment-major (descriptor ``w_frag = 1``): the kernels that read their weights as MFMA fragments load one
+    contiguous 1 KB run per wave and fragment instead of a 32-row gather (the gather saturated the CU's address unit)."""
+    return fragment_view(wp).contiguous()
+
+
+def se_operands(fc1: nn.Module, fc2: nn.Module) -> List[torch.Tensor]:
+    """Squeeze-excite operands of every gate-computing launch: fp32 [w1 [cse][c], b1 [cse], w2 [c][cse], b2 [c]]."""
+    cse, c = fc1.out_channels, fc1.in_channels
+    return [fc1.weight.detach().float().reshape(cse, c).contiguous(), fc1.bias.detach().float().contiguous(),
+            fc2.weight.detach().float().reshape(c, cse).contiguous(), fc2.bias.detach().float().contiguous()]
+
+
+def pack_dw_taps(w: torch.Tensor, cp: int, device) -> torch.Tensor:
+    """Depthwise weights (C, 1, kt, kh, kw) -> fp32 [taps][cp], zero padded channels."""
+    c, taps = w.shape[0], w[0].numel()
+    wp = torch.zeros(taps, cp, dtype=torch.float32, device=device)
+    wp[:, :c] = w.detach().float().reshape(c, taps).t()
+    return wp
+
+
+def same_extent(a: Act, b: Act) -> bool:
+    """A residual covers exactly the positions and padded channels of the tensor it is added to."""
+    return (a.N, a.T, a.H, a.W, a.Cp) == (b.N, b.T, b.H, b.W, b.Cp)
+
+
+# ---- kernel instance names: the codes of pasn_conv3d_variant / pasn_dwconv3d_variant, tested in the order conv.hip assigns them ---------
+CONV_TCONV_WS, CONV_PW_WS, CONV_PW_TINY, CONV_PW_PERSIST, CONV_PW_XTILE, CONV_IGEMM, CONV_GEMM = 9000, 7000, 2002, 1000, 2500, 6000, 2000
+DW_TEMPORAL, DW_TZ, DW_MFMA, DW_MARCH = 70000, 60000, 50000, 3000
+
+
+def conv_kernel_name(v: int, tname: str, gate: bool, in_swish: bool, res: bool) -> str:
+    tf = lambda b: "true" if b else "false"
+    if v >= CONV_TCONV_WS:
+        return f"tconv_ws_kernel<{v - CONV_TCONV_WS},{tf(res)}>"
+    if v >= CONV_PW_WS:
+        return f"pwconv_ws_kernel<{(v - CONV_PW_WS) // 10},{v % 10},{tf(gate or in_swish)},{tf(res)}>"
+    if v == CONV_PW_TINY:
+        return f"pwconv_tiny_kernel<{tname}>"
+    if CONV_PW_PERSIST <= v < CONV_GEMM:
+        return f"pwconv_persist_kernel<{tname},{(v - CONV_PW_PERSIST) // 10},{v % 10},{tf(res)}>"
+    if CONV_PW_XTILE <= v < CONV_IGEMM:
+        return f"pwconv_xtile_kernel<{tname},{(v - CONV_PW_XTILE) // 2},{tf(gate or v % 2 == 1)}>"
+    if v >= CONV_IGEMM:  # igemm.hip / igemm_halo.hip: mode * 100 + MT * 10 + NT
+        mode, mt, nt = (v - CONV_IGEMM) // 100, (v // 10) % 10, v % 10
+        return f"igemm_halo_kernel<{nt},{mt},{mode - 1}>" if mode else f"igemm_glds_kernel<{nt},{mt}>"
+    if v >= CONV_GEMM:
+        return f"gemm_conv_kernel<{tname},{tf(v == CONV_GEMM)}>"
+    return f"conv3d_mfma_kernel<{tname},{v // 10},{v % 10}>"
+
+
+def dwconv_kernel_name(dv: int, tname: str, act: str, pool: bool, wo: int) -> str:
+    actc = _lib.ACT[act]
+    if dv >= DW_TEMPORAL:  # with pool partial rows the (kt,1,1) layer stays on the generic kernel
+        return f"dwconv3d_kernel<{tname}>" if pool else f"dwconv_t_kernel<{tname},{dv - DW_TEMPORAL}>"
+    if dv >= DW_TZ:
+        return f"dwconv3d_tz_kernel<{actc},{'true' if pool else 'false'}>"
+    if dv >= DW_MFMA:  # the instance as the profiler prints it: <rows per position tile, ablation build, compiled-in activation>
+        return f"dwconv3d_mfma_kernel<{2 if wo <= 8 else 1},false,{actc if actc in (_lib.ACT['none'], _lib.ACT['swish']) else -1}>"
+    if dv >= DW_MARCH:
+        return f"dwconv3d_march_kernel<{dv % 10},{dv // 10 % 100}>"
+    if dv:
+        return f"dwconv3d_strip_kernel<{tname},{dv // 100},{dv // 10 % 10},{dv % 10}>"
+    return f"dwconv3d_kernel<{tname}>"
 
 
 class PlanBuilder:
@@ -167,19 +245,33 @@ class PlanBuilder:
     def _in_name(self) -> str:
         return {torch.bfloat16: "bf16", torch.uint8: "u8"}.get(self.in_dtype, "f32")
 
-    def _out_act(self, x: Act, cout: int, k, s, p) -> Act:
+    # Probe first, allocate after: a method that may answer "not covered" asks the library with _geom() + _probe_desc(), which touch
+    # neither ``bufs`` nor ``keep``, and reserves its outputs (_alloc) and keeps its descriptors only once the launch is certain.
+    @staticmethod
+    def _geom(x: Act, cout: int, k, s, p) -> Act:
+        """Extents of a window sweep's output; no buffer yet (``buf`` = -1)."""
         to = (x.T + 2 * p[0] - k[0]) // s[0] + 1
         ho = (x.H + 2 * p[1] - k[1]) // s[1] + 1
         wo = (x.W + 2 * p[2] - k[2]) // s[2] + 1
-        cp = round_up(cout, 8)
-        return Act(x.N, to, ho, wo, cout, cp, self._new_buf(x.N * to * ho * wo * cp * self.es))
+        return Act(x.N, to, ho, wo, cout, round_up(cout, 8), -1)
 
-    def _desc(self, x: Act, y: Act, k, s, p, act: str, in_swish=False, w_kc=0, w_rows=0) -> ConvDesc:
-        d = ConvDesc(
+    def _alloc(self, y: Act) -> Act:
+        y.buf = self._new_buf(y.N * y.positions * y.Cp * self.es)
+        return y
+
+    def _out_act(self, x: Act, cout: int, k, s, p) -> Act:
+        return self._alloc(self._geom(x, cout, k, s, p))
+
+    @staticmethod
+    def _probe_desc(x: Act, y: Act, k, s, p, act: str, in_swish=False, w_kc=0, w_rows=0, w_frag=0) -> ConvDesc:
+        return ConvDesc(
             N=x.N, Ti=x.T, Hi=x.H, Wi=x.W, Cin=x.C, Cin_p=x.Cp, To=y.T, Ho=y.H, Wo=y.W, Cout=y.C, Cout_p=y.Cp,
             kt=k[0], kh=k[1], kw=k[2], st=s[0], sh=s[1], sw=s[2], pt=p[0], ph=p[1], pw=p[2],
-            act=_lib.ACT[act], in_swish=int(bool(in_swish)), w_kc=w_kc, w_rows=w_rows,
+            act=_lib.ACT[act], in_swish=int(bool(in_swish)), w_kc=w_kc, w_rows=w_rows, w_frag=w_frag,
         )
+
+    def _desc(self, x: Act, y: Act, k, s, p, act: str, in_swish=False, w_kc=0, w_rows=0) -> ConvDesc:
+        d = self._probe_desc(x, y, k, s, p, act, in_swish, w_kc, w_rows)
         self.keep.append(d)
         return d
 
@@ -192,10 +284,11 @@ class PlanBuilder:
         w = x.W if k[2] >= s[2] else y.W * k[2]
         return x.N * min(t, x.T) * min(h, x.H) * min(w, x.W)
 
-    def _note(self, kind: str, name: str, nbytes: int, flops: int) -> None:
+    def _note(self, kind: str, name: str, nbytes: int, flops: int, d: Optional[ConvDesc]) -> None:
+        """``d``: the layer whose shape the launch's row shows.  The fused launches that pass None have an empty ``shape`` in the committed
+        routing snapshot and in the benchmark's JSON (x3d_edp / expand_dw write their own); naming their layers changes both files."""
         shape = ""
-        if any(isinstance(o, ConvDesc) for o in self.keep[-6:]):
-            d = [o for o in self.keep[-6:] if isinstance(o, ConvDesc)][-1]
+        if d is not None:
             shape = (f"{d.Cin}->{d.Cout} k{d.kt}{d.kh}{d.kw} s{d.st}{d.sh}{d.sw} "
                      f"in{d.Ti}x{d.Hi}x{d.Wi} out{d.To}x{d.Ho}x{d.Wo}")
         self.meta.append({"kind": kind, "kernel": name, "bytes": int(nbytes), "flops": int(flops), "shape": shape})
@@ -231,7 +324,7 @@ class PlanBuilder:
             wq = wq.to(torch.bfloat16).contiguous()
             self.keep += [wq, scale, bias, d]
             a = (wq.data_ptr(), scale.data_ptr(), bias.data_ptr())
-            self._note("first_conv", f"first_conv_mfma_kernel<{self._in_name()},{bn // 32},{nq // 2}>" + ("[grey]" if x.C == 1 else ""), nbytes, flops)
+            self._note("first_conv", f"first_conv_mfma_kernel<{self._in_name()},{bn // 32},{nq // 2}>" + ("[grey]" if x.C == 1 else ""), nbytes, flops, d)
             fn = self.lib.pasn_first_conv_mfma_fwd
             self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[yb], dref, code_in, ia, ib, st)))
             return y
@@ -239,7 +332,7 @@ class PlanBuilder:
         wp[:, : y.C] = w.permute(1, 2, 3, 0).reshape(x.C * k[1] * k[2], y.C)
         self.keep += [wp, scale, bias, d]
         a = (wp.data_ptr(), scale.data_ptr(), bias.data_ptr())
-        self._note("first_conv", f"first_conv_kernel<{self._in_name()},{self.tname},{y.Cp}>" + ("[grey]" if x.C == 1 else ""), nbytes, flops)
+        self._note("first_conv", f"first_conv_kernel<{self._in_name()},{self.tname},{y.Cp}>" + ("[grey]" if x.C == 1 else ""), nbytes, flops, d)
         if x.C == 1:
             fn = self.lib.pasn_first_conv_gray_fwd
             self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[yb], dref, code_in, code_out, ia, ib, st)))
@@ -253,14 +346,14 @@ class PlanBuilder:
         k, s, p = _triple(conv_xy.kernel_size, 1), _triple(conv_xy.stride, 1), _triple(conv_xy.padding, 0)
         kt, st_, pt_ = _triple(conv_t.kernel_size, 1), _triple(conv_t.stride, 1), _triple(conv_t.padding, 0)
         c = conv_xy.out_channels
-        y = self._out_act(x, c, k, s, p)
-        d = self._desc(x, y, k, s, p, "relu")
+        y = self._geom(x, c, k, s, p)
+        d = self._probe_desc(x, y, k, s, p, "relu")
         fusable = (x.planar and x.C in (1, 3) and kt == (5, 1, 1) and st_ == (1, 1, 1) and pt_ == (2, 0, 0) and conv_t.groups == c
                    and conv_xy.bias is None and conv_t.bias is None and bool(self.lib.pasn_x3d_stem_supported(ctypes.byref(d))))
         if not fusable:
-            self.bufs[y.buf].nbytes = ALIGN  # the buffer reserved above stays unused
             e = self.first_conv(x, conv_xy, None, act="none")
             return self.dwconv(e, conv_t, norm, act="relu")
+        self._alloc(y)
         wsrc = conv_xy.weight.detach().float()[:, :, 0]
         if x.C == 1:  # grey clip: taps summed over the three identical input channels (9 instead of 27)
             wsrc = wsrc.sum(dim=1, keepdim=True)
@@ -282,7 +375,7 @@ class PlanBuilder:
             self._use(xb, yb)
             out_pos = y.N * y.positions
             self._note("stem", f"x3d_stem_mfma_kernel<{self._in_name()},{x.C}>",
-                       x.N * x.C * x.positions * self._in_es() + out_pos * c * self.es, 2 * out_pos * c * (9 * x.C + 5))
+                       x.N * x.C * x.positions * self._in_es() + out_pos * c * self.es, 2 * out_pos * c * (9 * x.C + 5), d)
             ia, ib = self.in_affine if x.C == 1 else (1.0, 0.0)
             fn = self.lib.pasn_x3d_stem_mfma_fwd
             self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[yb], dref, code_in, ia, ib, st)))
@@ -293,14 +386,13 @@ class PlanBuilder:
         wt[:, :c] = conv_t.weight.detach().float().reshape(c, 5).t()
         scale, bias = fold_norm(norm, None, c, y.Cp, self.device)
         self.keep += [wxy, wt, scale, bias, d]
-        code_in, code_out = _lib.dtype_code(self.in_dtype), self.code
         a = (wxy.data_ptr(), wt.data_ptr(), scale.data_ptr(), bias.data_ptr())
         xb, yb, dref = x.buf, y.buf, ctypes.byref(d)
         self._use(xb, yb)
         in_es = self._in_es()
         out_pos = y.N * y.positions
         self._note("stem", f"x3d_stem_kernel<{self._in_name()},{self.tname},{y.Cp}{',grey' if x.C == 1 else ''}>",
-                   x.N * x.C * x.positions * in_es + out_pos * c * self.es, 2 * out_pos * c * (9 * x.C + 5))
+                   x.N * x.C * x.positions * in_es + out_pos * c * self.es, 2 * out_pos * c * (9 * x.C + 5), d)
         if x.C == 1:
             fn, (ia, ib) = self.lib.pasn_x3d_stem_gray_fwd, self.in_affine
             self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], a[3], ptrs[yb], dref, code_in, code_out, ia, ib, st)))
@@ -318,33 +410,24 @@ class PlanBuilder:
         scale, bias = fold_norm(norm, conv.bias, y.C, rows, self.device)
         d = self._desc(x, y, k, s, p, act, in_swish, kc, rows)
         self.keep += [wp, scale, bias]
-        if residual is not None:
-            assert (residual.N, residual.T, residual.H, residual.W, residual.Cp) == (y.N, y.T, y.H, y.W, y.Cp)
+        assert residual is None or same_extent(residual, y)
         fn, code = self.lib.pasn_conv3d_fwd, self.code
         a = (wp.data_ptr(), scale.data_ptr(), bias.data_ptr())
         xb, yb, rb, gb, dref = x.buf, y.buf, (residual.buf if residual is not None else None), in_gate, ctypes.byref(d)
         self._use(xb, yb, rb, gb)
         variant = int(self.lib.pasn_conv3d_variant(dref, self.code, int(in_gate is not None) | (2 if residual is not None else 0)))
-        if 2500 <= variant < 6000 or variant >= 7000:
-            # pwconv_xtile_kernel reads its weights as MFMA fragments: store them fragment-major, so a wave's fragment
-            # load is one contiguous 1 KB run instead of a 32-row gather (the gather saturated the CU's address unit)
-            # (variant >= 9000, tconv_ws_kernel: the K axis is (tap, channel) -- the packed rows are [taps][kc] already)
-            kstep, ch = (16, 8) if self.dtype == torch.bfloat16 else (8, 4)
-            wf = wp.view(rows // 32, 32, (k[0] * k[1] * k[2] * kc) // kstep, 2, ch).permute(0, 2, 3, 1, 4).contiguous()
+        if CONV_PW_XTILE <= variant < CONV_IGEMM or variant >= CONV_PW_WS:
+            # the X-tile and the weight-stationary kernels read fragment-major weights (tconv_ws_kernel: the K axis is (tap, channel) -- the
+            # packed rows are [taps][kc] already)
+            wf = fragment_major(wp)
             self.keep.append(wf)
             a = (wf.data_ptr(), a[1], a[2])
             d.w_frag = 1
         taps, out_pos = k[0] * k[1] * k[2], y.N * y.positions
-        self._note("conv", f"tconv_ws_kernel<{variant - 9000},{'true' if residual is not None else 'false'}>" if variant >= 9000 else
-                   f"pwconv_ws_kernel<{(variant - 7000) // 10},{variant % 10},{'true' if (in_gate is not None or in_swish) else 'false'},{'true' if residual is not None else 'false'}>" if variant >= 7000 else
-                   _igemm_name(variant - 6000) if variant >= 6000 else f"pwconv_xtile_kernel<{self.tname},{(variant - 2500) // 2},{'true' if (in_gate is not None or variant % 2 == 1) else 'false'}>" if 2500 <= variant < 6000 else
-                   f"pwconv_tiny_kernel<{self.tname}>" if variant == 2002 else
-                   f"gemm_conv_kernel<{self.tname},{'true' if variant == 2000 else 'false'}>" if variant >= 2000 else
-                   f"pwconv_persist_kernel<{self.tname},{(variant - 1000) // 10},{variant % 10},{'true' if residual is not None else 'false'}>" if variant >= 1000 else
-                   f"conv3d_mfma_kernel<{self.tname},{variant // 10},{variant % 10}>",
+        self._note("conv", conv_kernel_name(variant, self.tname, in_gate is not None, in_swish, residual is not None),
                    (self._touched(x, y, k, s) * x.C + out_pos * y.C * (2 if residual is not None else 1)
                     + y.C * x.C * taps) * self.es + (x.N * x.C * 4 if in_gate is not None else 0),
-                   2 * out_pos * y.C * x.C * taps)
+                   2 * out_pos * y.C * x.C * taps, d)
         self.ops.append(
             lambda ptrs, st: _lib.check(
                 fn(ptrs[xb], a[0], a[1], a[2], ptrs[rb] if rb is not None else 0, ptrs[gb] if gb is not None else 0,
@@ -361,25 +444,20 @@ class PlanBuilder:
         if x.planar or self.dtype != torch.bfloat16 or conv.groups != 1 or _triple(conv.kernel_size, 1) != one or _triple(conv.stride, 1) != one:
             return None
         pool_buf, pool_blocks, py = pooled
-        cse = fc1.out_channels
-        y = self._out_act(x, conv.out_channels, one, one, (0, 0, 0))
+        c, cse = x.C, fc1.out_channels
+        y = self._geom(x, conv.out_channels, one, one, (0, 0, 0))
         wp, kc, rows = pack_conv_weight(conv.weight, x.Cp, self.dtype)
-        d = self._desc(x, y, one, one, (0, 0, 0), act, True, kc, rows)
+        d = self._probe_desc(x, y, one, one, (0, 0, 0), act, True, kc, rows)
         if (py.N, py.positions, py.Cp) != (x.N, x.positions, x.Cp) or \
                 not int(self.lib.pasn_conv3d_se_supported(ctypes.byref(d), self.code, cse, int(residual is not None))):
-            self.bufs[y.buf].nbytes = ALIGN  # never used
             return None
-        wf = wp.view(rows // 32, 32, kc // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
+        assert residual is None or same_extent(residual, y)
+        self._alloc(y)
+        wf = fragment_major(wp)
         d.w_frag = 1
         scale, bias = fold_norm(norm, conv.bias, y.C, rows, self.device)
-        c = x.C
-        w1 = fc1.weight.detach().float().reshape(cse, c).contiguous()
-        b1 = fc1.bias.detach().float().contiguous()
-        w2 = fc2.weight.detach().float().reshape(c, cse).contiguous()
-        b2 = fc2.bias.detach().float().contiguous()
-        self.keep += [wf, scale, bias, w1, b1, w2, b2]
-        if residual is not None:
-            assert (residual.N, residual.T, residual.H, residual.W, residual.Cp) == (y.N, y.T, y.H, y.W, y.Cp)
+        w1, b1, w2, b2 = se_operands(fc1, fc2)
+        self.keep += [d, wf, scale, bias, w1, b1, w2, b2]
         fn, code = self.lib.pasn_conv3d_se_fwd, self.code
         a = tuple(t.data_ptr() for t in (wf, scale, bias, w1, b1, w2, b2))
         xb, yb, rb, pbuf, dref, pos = x.buf, y.buf, (residual.buf if residual is not None else None), pool_buf, ctypes.byref(d), x.positions
@@ -387,7 +465,7 @@ class PlanBuilder:
         out_pos = y.N * y.positions
         self._note("conv+se", f"pwconv_ws_kernel<{max(4, kc // 16 + kc // 16 % 2) if kc // 16 <= 16 else 28},1,true,{'true' if residual is not None else 'false'}>[se]",
                    (out_pos * (x.C + y.C * (2 if residual is not None else 1)) + y.C * x.C) * self.es + (x.N * pool_blocks * c + 2 * c * cse) * 4,
-                   2 * out_pos * y.C * x.C + 4 * x.N * c * cse)
+                   2 * out_pos * y.C * x.C + 4 * x.N * c * cse, None)
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[rb] if rb is not None else 0, ptrs[pbuf], pool_blocks, pos,
                                                        a[3], a[4], a[5], a[6], cse, ptrs[yb], dref, code, st)))
         return y
@@ -403,14 +481,12 @@ class PlanBuilder:
         s2 = _triple(sc.stride, 1)
         if s2[0] != 1:
             return False
-        T, H, W = x.T, (x.H - 1) // s2[1] + 1, (x.W - 1) // s2[2] + 1
-        inner, cout = pc.in_channels, pc.out_channels
-        cip, cop = round_up(inner, 8), round_up(cout, 8)
-        rows = round_up(cop, 128)
-        d = ConvDesc(N=x.N, Ti=T, Hi=H, Wi=W, Cin=inner, Cin_p=cip, To=T, Ho=H, Wo=W, Cout=cout, Cout_p=cop, kt=1, kh=1, kw=1, st=1, sh=1, sw=1,
-                     pt=0, ph=0, pw=0, act=_lib.ACT["relu"], in_swish=int(blk.se is not None), w_kc=round_up(cip, 16), w_rows=rows)
-        d2 = ConvDesc(N=x.N, Ti=x.T, Hi=x.H, Wi=x.W, Cin=x.C, Cin_p=x.Cp, To=T, Ho=H, Wo=W, Cout=cout, Cout_p=cop, kt=1, kh=1, kw=1, st=1,
-                      sh=s2[1], sw=s2[2], pt=0, ph=0, pw=0, act=_lib.ACT["none"], in_swish=0, w_kc=round_up(x.Cp, 16), w_rows=rows)
+        one, zero = (1, 1, 1), (0, 0, 0)
+        mid = self._geom(x, pc.in_channels, one, s2, zero)  # the block's stencil output: the project conv's input
+        y = self._geom(mid, pc.out_channels, one, one, zero)
+        rows = round_up(y.Cp, 128)
+        d = self._probe_desc(mid, y, one, one, zero, "relu", blk.se is not None, round_up(mid.Cp, 16), rows)
+        d2 = self._probe_desc(x, y, one, s2, zero, "none", False, round_up(x.Cp, 16), rows)
         return bool(self.lib.pasn_conv3d_short_supported(ctypes.byref(d), ctypes.byref(d2), self.code))
 
     def conv_short(self, x: Act, conv: nn.Module, norm: Optional[nn.Module], act: str, x2: Act, conv2: nn.Module, norm2: Optional[nn.Module],
@@ -424,20 +500,19 @@ class PlanBuilder:
         if _triple(conv.kernel_size, 1) != one or _triple(conv.stride, 1) != one or _triple(conv2.kernel_size, 1) != one:
             return None
         s2 = _triple(conv2.stride, 1)
-        y = self._out_act(x, conv.out_channels, one, one, (0, 0, 0))
+        y = self._geom(x, conv.out_channels, one, one, (0, 0, 0))
         wp, kc, rows = pack_conv_weight(conv.weight, x.Cp, self.dtype)
-        d = self._desc(x, y, one, one, (0, 0, 0), act, in_swish, kc, rows)
+        d = self._probe_desc(x, y, one, one, (0, 0, 0), act, in_swish, kc, rows)
         w2, kc2, rows2 = pack_conv_weight(conv2.weight, x2.Cp, self.dtype)
-        y2 = Act(y.N, y.T, y.H, y.W, y.C, y.Cp, -1)
-        d2 = self._desc(x2, y2, one, s2, (0, 0, 0), "none", False, kc2, rows2)
+        d2 = self._probe_desc(x2, y, one, s2, (0, 0, 0), "none", False, kc2, rows2)
         if (x2.T, (x2.H - 1) // s2[1] + 1, (x2.W - 1) // s2[2] + 1) != (y.T, y.H, y.W) or conv2.out_channels != conv.out_channels or \
                 not int(self.lib.pasn_conv3d_short_supported(ctypes.byref(d), ctypes.byref(d2), self.code)):
-            self.bufs[y.buf].nbytes = ALIGN  # never used
             return None
+        self._alloc(y)
         scale, bias = fold_norm(norm, conv.bias, y.C, rows, self.device)
         scale2, bias2 = fold_norm(norm2, conv2.bias, y.C, rows2, self.device)
         bias = (bias + bias2[: bias.numel()]).contiguous()
-        self.keep += [wp, w2, scale, bias, scale2]
+        self.keep += [d, d2, wp, w2, scale, bias, scale2]
         fn, code = self.lib.pasn_conv3d_short_fwd, self.code
         a = tuple(t.data_ptr() for t in (wp, scale, bias, w2, scale2))
         xb, x2b, gb, yb, r1, r2 = x.buf, x2.buf, in_gate, y.buf, ctypes.byref(d), ctypes.byref(d2)
@@ -446,7 +521,7 @@ class PlanBuilder:
         self._note("conv+shortcut", f"pwconv_persist_kernel<{self.tname},{max(2, 1 << (kc // 16 - 1).bit_length()) if kc // 16 > 2 else 2},{(y.Cp + 31) // 32},false,"
                                     f"{2 if kc2 // 16 <= 2 else 4}>",
                    (pos * (x.C + x2.C + y.C) + y.C * (x.C + x2.C)) * self.es + (x.N * x.C * 4 if in_gate is not None else 0),
-                   2 * pos * y.C * (x.C + x2.C))
+                   2 * pos * y.C * (x.C + x2.C), d2)  # (the row shows the shortcut conv's shape: it carries the block's stride)
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[gb] if gb is not None else 0, ptrs[x2b], a[3], a[4],
                                                        ptrs[yb], r1, r2, code, st)))
         return y
@@ -464,93 +539,66 @@ class PlanBuilder:
         for cv in (conv1, conv2):
             if _triple(cv.kernel_size, 1) != one or _triple(cv.stride, 1) != one or _triple(cv.padding, 0) != (0, 0, 0):
                 return None
-        y1 = self._out_act(x, conv1.out_channels, one, one, (0, 0, 0))
+        zero = (0, 0, 0)
+        y1 = self._geom(x, conv1.out_channels, one, one, zero)
         w1, kc1, rows1 = pack_conv_weight(conv1.weight, x.Cp, self.dtype)
-        d1 = self._desc(x, y1, one, one, (0, 0, 0), act1, in_swish, kc1, rows1)
-        mid = Act(y1.N, y1.T, y1.H, y1.W, y1.C, y1.Cp, -1)
-        y2 = self._out_act(mid, conv2.out_channels, one, one, (0, 0, 0))
+        d1 = self._probe_desc(x, y1, one, one, zero, act1, in_swish, kc1, rows1)
+        y2 = self._geom(y1, conv2.out_channels, one, one, zero)
         w2, kc2, rows2 = pack_conv_weight(conv2.weight, y1.Cp, self.dtype)
-        d2 = self._desc(mid, y2, one, one, (0, 0, 0), act2, False, kc2, rows2)
+        d2 = self._probe_desc(y1, y2, one, one, zero, act2, False, kc2, rows2)
+        r1, r2 = ctypes.byref(d1), ctypes.byref(d2)
+        (pool_buf, pool_blocks, py), fc1, fc2 = se if se is not None else ((None, 0, None), None, None)
+        cse = fc1.out_channels if se is not None else 0
+        pool_ok = se is None or (py.N, py.positions, py.Cp) == (x.N, x.positions, x.Cp)
         if se is not None:
-            supported = (se[0][2].N, se[0][2].positions, se[0][2].Cp) == (x.N, x.positions, x.Cp) and \
-                int(self.lib.pasn_conv3d_pair_se_supported(ctypes.byref(d1), ctypes.byref(d2), self.code, se[1].out_channels))
+            supported = pool_ok and int(self.lib.pasn_conv3d_pair_se_supported(r1, r2, self.code, cse))
         else:
-            supported = int(self.lib.pasn_conv3d_pair_supported(ctypes.byref(d1), ctypes.byref(d2), self.code))
-        frag = lambda wp, rows, kc: wp.view(rows // 32, 32, kc // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
-        if not supported:
+            supported = int(self.lib.pasn_conv3d_pair_supported(r1, r2, self.code))
+        pe = not supported
+        if pe:
             # the 432-channel stage: both weight sets do not fit a wave's registers; x3d_pe.hip streams them per row tile instead (same contract,
             # bit-identical results).  Its weights are fragment-major with K zero-padded to an EVEN number of 16-wide steps
-            cse = se[1].out_channels if se is not None else 0
             w1, kc1, rows1 = pack_conv_weight(conv1.weight, round_up(x.Cp, 32), self.dtype)
             w2, kc2, rows2 = pack_conv_weight(conv2.weight, round_up(y1.Cp, 32), self.dtype)
             d1.w_kc, d1.w_rows, d2.w_kc, d2.w_rows = kc1, rows1, kc2, rows2
             d1.w_frag = d2.w_frag = 1
-            pe_ok = in_gate is None and (se is None or (se[0][2].N, se[0][2].positions, se[0][2].Cp) == (x.N, x.positions, x.Cp)) and \
-                (residual.N, residual.T, residual.H, residual.W, residual.Cp) == (y1.N, y1.T, y1.H, y1.W, y1.Cp) and \
-                int(self.lib.pasn_x3d_pe_supported(ctypes.byref(d1), ctypes.byref(d2), self.code, cse))
-            if not pe_ok:
-                self.bufs[y1.buf].nbytes = ALIGN  # never used
-                self.bufs[y2.buf].nbytes = ALIGN
+            if not (in_gate is None and pool_ok and same_extent(residual, y1) and int(self.lib.pasn_x3d_pe_supported(r1, r2, self.code, cse))):
                 return None
-            w1f, w2f = frag(w1, rows1, kc1), frag(w2, rows2, kc2)
-            s1, b1 = fold_norm(norm1, conv1.bias, y1.C, rows1, self.device)
-            s2, b2 = fold_norm(norm2, conv2.bias, y2.C, rows2, self.device)
-            keep = [w1f, w2f, s1, b1, s2, b2]
-            sa = (0, 0, 0, 0)
-            pool_buf, pool_blocks = None, 0
-            if se is not None:
-                (pool_buf, pool_blocks, _), fc1, fc2 = se
-                c = x.C
-                sw = [fc1.weight.detach().float().reshape(cse, c).contiguous(), fc1.bias.detach().float().contiguous(),
-                      fc2.weight.detach().float().reshape(c, cse).contiguous(), fc2.bias.detach().float().contiguous()]
-                keep += sw
-                sa = tuple(t.data_ptr() for t in sw)
-            self.keep += keep
-            a = tuple(t.data_ptr() for t in (w1f, s1, b1, w2f, s2, b2))
-            xb, rb, y1b, y2b = x.buf, residual.buf, y1.buf, y2.buf
-            r1, r2 = ctypes.byref(d1), ctypes.byref(d2)
-            self._use(xb, rb, y1b, y2b, pool_buf)
-            pos, npos = y1.N * y1.positions, x.positions
-            self._note("conv_pair+se" if se is not None else "conv_pair", f"x3d_pe_kernel<{kc1 // 16},{kc2 // 16},{'true' if se is not None else 'false'}>",
-                       (pos * (x.C + 2 * y1.C + y2.C) + y1.C * x.C + y2.C * y1.C) * self.es + ((x.N * pool_blocks * x.C + 2 * x.C * cse) * 4 if se is not None else 0),
-                       2 * pos * (y1.C * x.C + y2.C * y1.C))
-            fpe, code = self.lib.pasn_x3d_pe_fwd, self.code
-            self.ops.append(lambda ptrs, st: _lib.check(fpe(ptrs[xb], a[0], a[1], a[2], ptrs[rb], ptrs[pool_buf] if pool_buf is not None else 0, pool_blocks, npos,
-                                                            sa[0], sa[1], sa[2], sa[3], cse, ptrs[y1b], r1, a[3], a[4], a[5], ptrs[y2b], r2, code, st)))
-            return y1, y2
-        assert (residual.N, residual.T, residual.H, residual.W, residual.Cp) == (y1.N, y1.T, y1.H, y1.W, y1.Cp)
-        w1f, w2f = frag(w1, rows1, kc1), frag(w2, rows2, kc2)
+        assert same_extent(residual, y1)
         d1.w_frag = d2.w_frag = 1
+        self._alloc(y1)
+        self._alloc(y2)
+        w1f, w2f = fragment_major(w1), fragment_major(w2)
         s1, b1 = fold_norm(norm1, conv1.bias, y1.C, rows1, self.device)
         s2, b2 = fold_norm(norm2, conv2.bias, y2.C, rows2, self.device)
-        self.keep += [w1f, w2f, s1, b1, s2, b2]
-        fn, code = self.lib.pasn_conv3d_pair_fwd, self.code
+        sw = se_operands(fc1, fc2) if se is not None else []
+        self.keep += [d1, d2, w1f, w2f, s1, b1, s2, b2] + sw
         a = tuple(t.data_ptr() for t in (w1f, s1, b1, w2f, s2, b2))
-        xb, rb, gb, y1b, y2b = x.buf, residual.buf, in_gate, y1.buf, y2.buf
-        r1, r2 = ctypes.byref(d1), ctypes.byref(d2)
-        self._use(xb, rb, gb, y1b, y2b)
-        pos = y1.N * y1.positions
-        if se is not None:
-            (pool_buf, pool_blocks, py), fc1, fc2 = se
-            c, cse = x.C, fc1.out_channels
-            sw = [fc1.weight.detach().float().reshape(cse, c).contiguous(), fc1.bias.detach().float().contiguous(),
-                  fc2.weight.detach().float().reshape(c, cse).contiguous(), fc2.bias.detach().float().contiguous()]
-            self.keep += sw
-            sa = tuple(t.data_ptr() for t in sw)
-            self._use(pool_buf)
-            fse, npos = self.lib.pasn_conv3d_pair_se_fwd, x.positions
-            self._note("conv_pair+se", f"pwconv_ws_kernel<{max(8, kc1 // 16 + kc1 // 16 % 2)},1,true,true,{4 if kc2 // 16 <= 4 else 6}>[se]",
-                       (pos * (x.C + 2 * y1.C + y2.C) + y1.C * x.C + y2.C * y1.C) * self.es + (x.N * pool_blocks * c + 2 * c * cse) * 4,
-                       2 * pos * (y1.C * x.C + y2.C * y1.C) + 4 * x.N * c * cse)
-            self.ops.append(lambda ptrs, st: _lib.check(fse(ptrs[xb], a[0], a[1], a[2], ptrs[rb], ptrs[pool_buf], pool_blocks, npos, sa[0], sa[1],
-                                                            sa[2], sa[3], cse, ptrs[y1b], r1, a[3], a[4], a[5], ptrs[y2b], r2, code, st)))
+        sa = tuple(t.data_ptr() for t in sw) or (0, 0, 0, 0)
+        xb, rb, gb, y1b, y2b, code = x.buf, residual.buf, in_gate, y1.buf, y2.buf, self.code
+        self._use(xb, rb, gb, y1b, y2b, pool_buf)
+        pos, npos = y1.N * y1.positions, x.positions
+        nbytes = (pos * (x.C + 2 * y1.C + y2.C) + y1.C * x.C + y2.C * y1.C) * self.es
+        flops = 2 * pos * (y1.C * x.C + y2.C * y1.C)
+        if pe or se is not None:  # the two launches that can compute the gate in their prologue share one argument list
+            nbytes += (x.N * pool_blocks * x.C + 2 * x.C * cse) * 4 if se is not None else 0
+            if pe:
+                fn = self.lib.pasn_x3d_pe_fwd
+                self._note("conv_pair+se" if se is not None else "conv_pair",
+                           f"x3d_pe_kernel<{kc1 // 16},{kc2 // 16},{'true' if se is not None else 'false'}>", nbytes, flops, None)
+            else:
+                fn = self.lib.pasn_conv3d_pair_se_fwd
+                self._note("conv_pair+se", f"pwconv_ws_kernel<{max(8, kc1 // 16 + kc1 // 16 % 2)},1,true,true,{4 if kc2 // 16 <= 4 else 6}>[se]",
+                           nbytes, flops + 4 * x.N * x.C * cse, None)
+            self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[rb], ptrs[pool_buf] if pool_buf is not None else 0, pool_blocks, npos,
+                                                           sa[0], sa[1], sa[2], sa[3], cse, ptrs[y1b], r1, a[3], a[4], a[5], ptrs[y2b], r2, code, st)))
             return y1, y2
+        fn = self.lib.pasn_conv3d_pair_fwd
         pv = int(self.lib.pasn_conv3d_pair_variant(r1, r2, self.code, int(in_gate is not None)))
         xf_name = 'true' if (in_gate is not None or in_swish) else 'false'
         self._note("conv_pair", f"pwconv_ws_kernel<{max(8, kc1 // 16 + kc1 // 16 % 2)},1,{xf_name},true,{4 if kc2 // 16 <= 4 else 6}>" if pv == 2 else
                                 f"pwconv_xpair_kernel<{max(8, kc1 // 16 + kc1 // 16 % 2)},{kc2 // 16 + kc2 // 16 % 2},{xf_name}>",
-                   (pos * (x.C + 2 * y1.C + y2.C) + y1.C * x.C + y2.C * y1.C) * self.es + (x.N * x.C * 4 if in_gate is not None else 0),
-                   2 * pos * (y1.C * x.C + y2.C * y1.C))
+                   nbytes + (x.N * x.C * 4 if in_gate is not None else 0), flops, None)
         self.ops.append(
             lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[rb], ptrs[gb] if gb is not None else 0, ptrs[y1b], r1,
                                            a[3], a[4], a[5], ptrs[y2b], r2, code, st))
@@ -562,8 +610,7 @@ class PlanBuilder:
         k, s, p = _triple(conv.kernel_size, 1), _triple(conv.stride, 1), _triple(conv.padding, 0)
         y = self._out_act(x, x.C, k, s, p)
         taps = k[0] * k[1] * k[2]
-        wp = torch.zeros(taps, y.Cp, dtype=torch.float32, device=self.device)
-        wp[:, : y.C] = conv.weight.detach().float().reshape(y.C, taps).t()
+        wp = pack_dw_taps(conv.weight, y.Cp, self.device)
         scale, bias = fold_norm(norm, conv.bias, y.C, y.Cp, self.device)
         d = self._desc(x, y, k, s, p, act)
         self.keep += [wp, scale, bias]
@@ -577,30 +624,13 @@ class PlanBuilder:
         self._use(xb, yb, pb)
         out_pos = y.N * y.positions
         dv = int(self.lib.pasn_dwconv3d_variant(dref, self.code))
-        if dv >= 70000 and not pool:
-            kname = f"dwconv_t_kernel<{self.tname},{dv - 70000}>"
-        elif dv >= 70000:  # with pool partial rows the (kt,1,1) layer stays on the generic kernel
-            kname = f"dwconv3d_kernel<{self.tname}>"
-        elif dv >= 60000:
-            kname = f"dwconv3d_tz_kernel<{_lib.ACT[act]},{'true' if pool else 'false'}>"
-        elif dv >= 50000:  # the instance as the profiler prints it: <rows per position tile, ablation build, compiled-in activation>
-            actc = _lib.ACT[act]
-            kname = f"dwconv3d_mfma_kernel<{2 if y.W <= 8 else 1},false,{actc if actc in (_lib.ACT['none'], _lib.ACT['swish']) else -1}>"
-        elif dv >= 3000:
-            kname = f"dwconv3d_march_kernel<{dv % 10},{dv // 10 % 100}>"
-        elif dv:
-            kname = f"dwconv3d_strip_kernel<{self.tname},{dv // 100},{dv // 10 % 10},{dv % 10}>"
-        else:
-            kname = f"dwconv3d_kernel<{self.tname}>"
-        self._note("dwconv", kname,
+        self._note("dwconv", dwconv_kernel_name(dv, self.tname, act, pool, y.W),
                    (self._touched(x, y, k, s) + out_pos) * y.C * self.es + (y.N * pool_blocks * y.C * 4 if pool else 0),
-                   2 * out_pos * y.C * taps)
+                   2 * out_pos * y.C * taps, d)
         self.ops.append(
             lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[yb], ptrs[pb] if pb is not None else 0, dref, code, st))
         )
-        if pool:
-            return y, (pool_buf, pool_blocks, y)
-        return y
+        return (y, (pool_buf, pool_blocks, y)) if pool else y
 
     def x3d_edp(self, x: Act, conv_a: nn.Module, norm_a, conv_b: nn.Module, norm_b, conv_c: nn.Module, norm_c, conv_n: Optional[nn.Module] = None,
                 norm_n=None, probe: bool = False):
@@ -617,29 +647,19 @@ class PlanBuilder:
         if not ok or (conv_n is not None and conv_n.in_channels != conv_c.out_channels):
             return False if probe else None
         cm = conv_a.out_channels
-        mid = Act(x.N, x.T, x.H, x.W, cm, round_up(cm, 8), -1)   # expanded activation / stencil output: never materialised
-
-        def desc(src, dst, k, s, p, act, kc, rows):
-            d = ConvDesc(N=src.N, Ti=src.T, Hi=src.H, Wi=src.W, Cin=src.C, Cin_p=src.Cp, To=dst.T, Ho=dst.H, Wo=dst.W, Cout=dst.C, Cout_p=dst.Cp,
-                         kt=k[0], kh=k[1], kw=k[2], st=s[0], sh=s[1], sw=s[2], pt=p[0], ph=p[1], pw=p[2], act=_lib.ACT[act], in_swish=0,
-                         w_kc=kc, w_rows=rows, w_frag=1)
-            return d
-
-        rows_a, rows_c = round_up(mid.Cp, 128), round_up(x.Cp, 128)
-        yv = Act(x.N, x.T, x.H, x.W, x.C, x.Cp, -1)
-        da = desc(x, mid, one, one, zero, "relu", round_up(x.Cp, 16), rows_a)
-        dd = desc(mid, mid, (3, 3, 3), one, (1, 1, 1), "swish", 0, 0)
-        dd.w_frag = 0
-        dc = desc(mid, yv, one, one, zero, "relu", round_up(mid.Cp, 32), rows_c)
-        dn = None
+        mid = self._geom(x, cm, one, one, zero)   # expanded activation / stencil output: never materialised
+        y = self._geom(mid, conv_c.out_channels, one, one, zero)
+        da = self._probe_desc(x, mid, one, one, zero, "relu", False, round_up(x.Cp, 16), round_up(mid.Cp, 128), w_frag=1)
+        dd = self._probe_desc(mid, mid, (3, 3, 3), one, (1, 1, 1), "swish")
+        dc = self._probe_desc(mid, y, one, one, zero, "relu", False, round_up(mid.Cp, 32), round_up(y.Cp, 128), w_frag=1)
+        dn = en = None
         if conv_n is not None:
-            nv = Act(x.N, x.T, x.H, x.W, conv_n.out_channels, round_up(conv_n.out_channels, 8), -1)
-            dn = desc(yv, nv, one, one, zero, "relu", round_up(x.Cp, 16), round_up(nv.Cp, 128))
+            en = self._geom(y, conv_n.out_channels, one, one, zero)
+            dn = self._probe_desc(y, en, one, one, zero, "relu", False, round_up(y.Cp, 16), round_up(en.Cp, 128), w_frag=1)
         if not int(self.lib.pasn_x3d_edp_supported(ctypes.byref(da), ctypes.byref(dd), ctypes.byref(dc), ctypes.byref(dn) if dn is not None else None, self.code)):
             return False if probe else None
         if probe:
             return True
-        frag = lambda wp, rows, kc: wp.view(rows // 32, 32, kc // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
         wa, kca, ra = pack_conv_weight(conv_a.weight, x.Cp, self.dtype)
         wc, kcc, rc = pack_conv_weight(conv_c.weight, round_up(mid.Cp, 32), self.dtype)
         assert (kca, ra, kcc, rc) == (da.w_kc, da.w_rows, dc.w_kc, dc.w_rows)
@@ -647,14 +667,13 @@ class PlanBuilder:
         wd = stencil_operands(conv_b.weight.to(self.device), cm, mid.Cp)
         sd, bd = fold_norm(norm_b, None, cm, mid.Cp, self.device)
         sc, bc = fold_norm(norm_c, conv_c.bias, x.C, rc, self.device)
-        keep = [frag(wa, ra, kca), sa, ba, wd, sd, bd, frag(wc, rc, kcc), sc, bc]
-        y = self._out_act(mid, conv_c.out_channels, one, one, zero)
-        en = None
+        keep = [fragment_major(wa), sa, ba, wd, sd, bd, fragment_major(wc), sc, bc]
+        self._alloc(y)
         if conv_n is not None:
-            en = self._out_act(y, conv_n.out_channels, one, one, zero)
+            self._alloc(en)
             wn, kcn, rn = pack_conv_weight(conv_n.weight, y.Cp, self.dtype)
             sn, bn = fold_norm(norm_n, conv_n.bias, en.C, rn, self.device)
-            keep += [frag(wn, rn, kcn), sn, bn]
+            keep += [fragment_major(wn), sn, bn]
         self.keep += keep + [da, dd, dc] + ([dn] if dn is not None else [])
         a = tuple(t.data_ptr() for t in keep) + ((0, 0, 0) if conv_n is None else ())
         xb, yb, nb = x.buf, y.buf, (en.buf if en is not None else None)
@@ -662,7 +681,7 @@ class PlanBuilder:
         self._use(xb, yb, nb)
         pos, cn = y.N * y.positions, (en.C if en is not None else 0)
         self._note("block" if en is None else "block+expand", f"x3d_edp_kernel<{kca // 16},{kcc // 16},{'true' if en is not None else 'false'}>",
-                   (pos * (2 * x.C + y.C + cn) + cm * x.C + 27 * cm + y.C * cm + cn * y.C) * self.es, 2 * pos * (cm * x.C + 27 * cm + y.C * cm + cn * y.C))
+                   (pos * (2 * x.C + y.C + cn) + cm * x.C + 27 * cm + y.C * cm + cn * y.C) * self.es, 2 * pos * (cm * x.C + 27 * cm + y.C * cm + cn * y.C), None)
         self.meta[-1]["shape"] = f"{x.C}->{cm} k111 -> dw k333 -> {cm}->{y.C}" + (f" -> {y.C}->{cn}" if cn else "") + f" k111 in{x.T}x{x.H}x{x.W}"
         fn, code = self.lib.pasn_x3d_edp_fwd, self.code
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], ptrs[yb], a[9], a[10], a[11],
@@ -683,7 +702,7 @@ class PlanBuilder:
         if k != (3, 3, 3) or s not in ((1, 1, 1), (1, 2, 2)) or p != (1, 1, 1) or conv_b.in_channels != conv_a.out_channels:
             return None
         cm = conv_a.out_channels
-        mid = Act(x.N, x.T, x.H, x.W, cm, round_up(cm, 8), -1)  # the expanded activation: never materialised
+        mid = self._geom(x, cm, one, one, zero)  # the expanded activation: never materialised
         # norm_a's scale goes INTO the expand weights (W * scale, rounded to bf16 once) and its bias becomes the accumulator's initial
         # value: the fused kernel's expand epilogue is then swap + ReLU + rounding (PASN_EXPDW_FOLD=0: scale and bias applied in fp32
         # after the MFMAs, the rounding points of the two separate launches)
@@ -691,20 +710,18 @@ class PlanBuilder:
         sa_full, _ = fold_norm(norm_a, conv_a.bias, cm, cm, self.device)
         w_src = conv_a.weight.detach().float() * sa_full.to(conv_a.weight.device).view(-1, 1, 1, 1, 1) if fold else conv_a.weight
         wa, kca, rowsa = pack_conv_weight(w_src, x.Cp, self.dtype)
-        de = self._desc(x, mid, one, one, zero, "relu", False, kca, rowsa)
-        probe = ConvDesc(N=x.N, Ti=x.T, Hi=x.H, Wi=x.W, Cin=cm, Cin_p=mid.Cp, To=x.T, Ho=(x.H - 1) // s[1] + 1, Wo=(x.W - 1) // s[2] + 1, Cout=cm,
-                         Cout_p=mid.Cp, kt=3, kh=3, kw=3, st=1, sh=s[1], sw=s[2], pt=1, ph=1, pw=1, act=_lib.ACT[act_b])
-        if not int(self.lib.pasn_x3d_expdw_supported(ctypes.byref(de), ctypes.byref(probe), self.code)):
+        de = self._probe_desc(x, mid, one, one, zero, "relu", False, kca, rowsa)
+        y = self._geom(mid, cm, k, s, p)
+        d = self._probe_desc(mid, y, k, s, p, act_b)
+        if not int(self.lib.pasn_x3d_expdw_supported(ctypes.byref(de), ctypes.byref(d), self.code)):
             return None
-        y = self._out_act(mid, cm, k, s, p)
-        d = self._desc(mid, y, k, s, p, act_b)
-        waf = wa.view(rowsa // 32, 32, kca // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
+        self._alloc(y)
+        waf = fragment_major(wa)
         de.w_frag = 1
         sa, ba = fold_norm(norm_a, conv_a.bias, cm, rowsa, self.device)
-        wp = torch.zeros(27, y.Cp, dtype=torch.float32, device=self.device)
-        wp[:, : y.C] = conv_b.weight.detach().float().reshape(y.C, 27).t()
+        wp = pack_dw_taps(conv_b.weight, y.Cp, self.device)
         sb, bb = fold_norm(norm_b, conv_b.bias, y.C, y.Cp, self.device)
-        self.keep += [waf, sa, ba, wp, sb, bb]
+        self.keep += [de, d, waf, sa, ba, wp, sb, bb]
         pool_buf, pool_blocks = None, 0
         if pool:
             pool_blocks = int(self.lib.pasn_x3d_expdw_pool_blocks(ctypes.byref(de), ctypes.byref(d), self.code))
@@ -721,26 +738,28 @@ class PlanBuilder:
         self._note("expand+dwconv", f"x3d_expdw_tz_kernel<1,{actc},{'true' if pool else 'false'}>" if tz else
                    f"x3d_expdw_kernel<{2 if kca // 16 <= 2 else 3},{actc if actc in (_lib.ACT['none'], _lib.ACT['swish']) else -1},{s[1]}>",
                    (in_pos * x.C + out_pos * y.C + cm * x.C) * self.es + (y.N * pool_blocks * y.C * 4 if pool else 0),
-                   2 * in_pos * cm * x.C + 2 * out_pos * y.C * 27)
+                   2 * in_pos * cm * x.C + 2 * out_pos * y.C * 27, None)
         self.meta[-1]["shape"] = f"{x.C}->{cm} k111 + dw k333 s1{s[1]}{s[2]} in{x.T}x{x.H}x{x.W} out{y.T}x{y.H}x{y.W}"
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], a[3], a[4], a[5], ptrs[yb],
                                                        ptrs[pb_] if pb_ is not None else 0, re_, rd_, code, st)))
-        if pool:
-            return y, (pool_buf, pool_blocks, y)
-        return y
+        return (y, (pool_buf, pool_blocks, y)) if pool else y
+
+    def _gate_in_prologue(self, y: Act, fc1: nn.Module, consumer) -> bool:
+        """Whether the project conv (``consumer`` = (conv_c, has residual), or None) of the SE block whose stencil output is ``y`` computes
+        the gate in its own prologue (``pasn_conv3d_se_fwd`` and the chained launches built on it)."""
+        if consumer is None or self.dtype != torch.bfloat16:
+            return False
+        cc, has_res = consumer
+        one, zero = (1, 1, 1), (0, 0, 0)
+        out = self._geom(y, cc.out_channels, one, one, zero)
+        dc = self._probe_desc(y, out, one, one, zero, "relu", True, round_up(y.Cp, 16), round_up(out.Cp, 128))
+        return bool(self.lib.pasn_conv3d_se_supported(ctypes.byref(dc), self.code, fc1.out_channels, int(has_res)))
 
     def se_gate_or_prologue(self, y: Act, pooled, fc1: nn.Module, fc2: nn.Module, consumer=None):
         """The gate of an SE block whose stencil produced pool partial rows: ("pooled", pooled) where the project conv (``consumer`` =
         (conv_c, has residual)) computes it in its own prologue, else the stand-alone gate launch's buffer."""
-        cse = fc1.out_channels
-        if consumer is not None:
-            cc, has_res = consumer
-            cop = round_up(cc.out_channels, 8)
-            dc = ConvDesc(N=y.N, Ti=y.T, Hi=y.H, Wi=y.W, Cin=y.C, Cin_p=y.Cp, To=y.T, Ho=y.H, Wo=y.W, Cout=cc.out_channels, Cout_p=cop,
-                          kt=1, kh=1, kw=1, st=1, sh=1, sw=1, pt=0, ph=0, pw=0, act=_lib.ACT["relu"], in_swish=1,
-                          w_kc=round_up(y.Cp, 16), w_rows=round_up(cop, 128))
-            if self.dtype == torch.bfloat16 and int(self.lib.pasn_conv3d_se_supported(ctypes.byref(dc), self.code, cse, int(has_res))):
-                return ("pooled", pooled)
+        if self._gate_in_prologue(y, fc1, consumer):
+            return ("pooled", pooled)
         return self.se_gate(pooled, fc1, fc2)
 
     def dwconv_se(self, x: Act, conv: nn.Module, norm: Optional[nn.Module], fc1: nn.Module, fc2: nn.Module, consumer=None):
@@ -749,39 +768,24 @@ class PlanBuilder:
         by the stand-alone gate launch.  Returns (y, gate buffer id)."""
         assert not x.planar and conv.groups == conv.in_channels == conv.out_channels == x.C
         k, s, p = _triple(conv.kernel_size, 1), _triple(conv.stride, 1), _triple(conv.padding, 0)
-        probe = ConvDesc(N=x.N, Ti=x.T, Hi=x.H, Wi=x.W, Cin=x.C, Cin_p=x.Cp, To=(x.T + 2 * p[0] - k[0]) // s[0] + 1,
-                         Ho=(x.H + 2 * p[1] - k[1]) // s[1] + 1, Wo=(x.W + 2 * p[2] - k[2]) // s[2] + 1, Cout=x.C, Cout_p=x.Cp,
-                         kt=k[0], kh=k[1], kw=k[2], st=s[0], sh=s[1], sw=s[2], pt=p[0], ph=p[1], pw=p[2], act=_lib.ACT["none"])
-        cse = fc1.out_channels
-        if not int(self.lib.pasn_dwconv3d_se_supported(ctypes.byref(probe), self.code, cse)):
+        y = self._geom(x, x.C, k, s, p)
+        d = self._probe_desc(x, y, k, s, p, "none")
+        c, cse = y.C, fc1.out_channels
+        if not int(self.lib.pasn_dwconv3d_se_supported(ctypes.byref(d), self.code, cse)):
             y, pooled = self.dwconv(x, conv, norm, act="none", pool=True)
-            if consumer is not None:
-                # the project conv may compute the gate in its own prologue (pasn_conv3d_se_fwd): ``consumer`` = (conv_c, has residual)
-                cc, has_res = consumer
-                cop = round_up(cc.out_channels, 8)
-                dc = ConvDesc(N=y.N, Ti=y.T, Hi=y.H, Wi=y.W, Cin=y.C, Cin_p=y.Cp, To=y.T, Ho=y.H, Wo=y.W, Cout=cc.out_channels, Cout_p=cop,
-                              kt=1, kh=1, kw=1, st=1, sh=1, sw=1, pt=0, ph=0, pw=0, act=_lib.ACT["relu"], in_swish=1,
-                              w_kc=round_up(y.Cp, 16), w_rows=round_up(cop, 128))
-                if self.dtype == torch.bfloat16 and int(self.lib.pasn_conv3d_se_supported(ctypes.byref(dc), self.code, cse, int(has_res))):
-                    return y, ("pooled", pooled)
-            return y, self.se_gate(pooled, fc1, fc2)
-        y = self._out_act(x, x.C, k, s, p)
+            # the project conv may compute the gate in its own prologue: then only the pool partial rows are produced here
+            return y, (("pooled", pooled) if self._gate_in_prologue(y, fc1, consumer) else self.se_gate(pooled, fc1, fc2))
+        self._alloc(y)
         taps = k[0] * k[1] * k[2]
-        wp = torch.zeros(taps, y.Cp, dtype=torch.float32, device=self.device)
-        wp[:, : y.C] = conv.weight.detach().float().reshape(y.C, taps).t()
+        wp = pack_dw_taps(conv.weight, y.Cp, self.device)
         scale, bias = fold_norm(norm, conv.bias, y.C, y.Cp, self.device)
-        d = self._desc(x, y, k, s, p, "none")
-        c = y.C
-        w1 = fc1.weight.detach().float().reshape(cse, c).contiguous()
-        b1 = fc1.bias.detach().float().contiguous()
-        w2 = fc2.weight.detach().float().reshape(c, cse).contiguous()
-        b2 = fc2.bias.detach().float().contiguous()
+        w1, b1, w2, b2 = se_operands(fc1, fc2)
         if self.se_counters is None:
             self.se_counters = torch.zeros(4096, dtype=torch.int32, device=self.device)
         assert self.se_counters_used + y.N <= self.se_counters.numel(), "too many fused SE-gate launches for the counter block"
         counter = self.se_counters[self.se_counters_used: self.se_counters_used + y.N]  # the kernel leaves it zero; Plan.run clears it anyway
         self.se_counters_used += (y.N + 3) // 4 * 4
-        self.keep += [wp, scale, bias, w1, b1, w2, b2, counter]
+        self.keep += [d, wp, scale, bias, w1, b1, w2, b2, counter]
         pool_blocks = int(self.lib.pasn_dwconv3d_se_pool_blocks(ctypes.byref(d), self.code))
         pool_buf = self._new_buf(y.N * pool_blocks * y.Cp * 4)
         gate = self._new_buf(y.N * y.Cp * 4)
@@ -792,10 +796,10 @@ class PlanBuilder:
         out_pos = y.N * y.positions
         dv = int(self.lib.pasn_dwconv3d_variant(dref, self.code))
         # the T-marching VALU stencil's instance (the layer's plain launch may be routed elsewhere: then only the stride is known here)
-        kname = f"dwconv3d_march_kernel<{dv % 10},{dv // 10 % 100}>" if 3000 <= dv < 50000 else f"dwconv3d_march_kernel<{s[2]},se>"
+        kname = dwconv_kernel_name(dv, self.tname, "none", True, y.W) if DW_MARCH <= dv < DW_MFMA else f"dwconv3d_march_kernel<{s[2]},se>"
         self._note("dwconv+se", kname,
                    (self._touched(x, y, k, s) + out_pos) * y.C * self.es + (y.N * pool_blocks * y.C * 8 + y.N * c * 4 + 2 * c * cse * 4),
-                   2 * out_pos * y.C * taps + 4 * y.N * c * cse)
+                   2 * out_pos * y.C * taps + 4 * y.N * c * cse, None)
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[yb], ptrs[pb_], dref, code, a[3], a[4], a[5], a[6],
                                                        cse, ptrs[gate], a[7], st)))
         return y, gate
@@ -803,17 +807,14 @@ class PlanBuilder:
     def se_gate(self, pooled, fc1: nn.Module, fc2: nn.Module) -> int:
         pool_buf, pool_blocks, y = pooled
         c, cse = y.C, fc1.out_channels
-        w1 = fc1.weight.detach().float().reshape(cse, c).contiguous()
-        b1 = fc1.bias.detach().float().contiguous()
-        w2 = fc2.weight.detach().float().reshape(c, cse).contiguous()
-        b2 = fc2.bias.detach().float().contiguous()
+        w1, b1, w2, b2 = se_operands(fc1, fc2)
         self.keep += [w1, b1, w2, b2]
         gate = self._new_buf(y.N * y.Cp * 4)
         fn = self.lib.pasn_se_gate_fwd
         a = (w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr())
         n, cp, pos = y.N, y.Cp, y.positions
         self._use(pool_buf, gate)
-        self._note("se_gate", "se_gate_kernel", (y.N * pool_blocks * c + y.N * c + 2 * c * cse) * 4, 4 * y.N * c * cse)
+        self._note("se_gate", "se_gate_kernel", (y.N * pool_blocks * c + y.N * c + 2 * c * cse) * 4, 4 * y.N * c * cse, None)
         self.ops.append(
             lambda ptrs, st: _lib.check(fn(ptrs[pool_buf], pool_blocks, pos, a[0], a[1], a[2], a[3], ptrs[gate], n, c, cp, cse, st))
         )
@@ -825,7 +826,7 @@ class PlanBuilder:
         fn, code = self.lib.pasn_maxpool3d_fwd, self.code
         xb, yb, dref = x.buf, y.buf, ctypes.byref(d)
         self._use(xb, yb)
-        self._note("maxpool", f"maxpool3d_kernel<{self.tname}>", (self._touched(x, y, k, s) + y.N * y.positions) * y.C * self.es, 0)
+        self._note("maxpool", f"maxpool3d_kernel<{self.tname}>", (self._touched(x, y, k, s) + y.N * y.positions) * y.C * self.es, 0, d)
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], ptrs[yb], dref, code, st)))
         return y
 

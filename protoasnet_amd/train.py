@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import ConvDesc, XProtoDesc
-from .plan import ALIGN, Act, PlanBuilder, _triple, round_up
+from .plan import ALIGN, Act, PlanBuilder, _triple, frag_steps, fragment_view, round_up
 
 
 def _need_fp32_param(p: torch.Tensor, what: str) -> None:
@@ -173,7 +173,7 @@ class TrainBuilder(PlanBuilder):
                residual: Optional[Act] = None, pack: Optional[Tuple[torch.Tensor, int]] = None) -> ConvDesc:
         """``pack`` = (parameter [cout][cin][taps...] fp32, mode 0 forward / 1 input gradient): what ``weight_fn`` computes, for the native packer."""
         taps = k[0] * k[1] * k[2]
-        kstep, ch = (16, 8) if self.dtype == torch.bfloat16 else (8, 4)
+        kstep, ch = frag_steps(self.dtype)
         kc, rows = round_up(x.Cp, kstep), round_up(round_up(cout, 8), 128)
         wp = torch.zeros(rows, taps, kc, dtype=self.dtype, device=self.device)
         d = self._desc(x, y, k, s, p, "none", False, kc, rows)
@@ -186,7 +186,8 @@ class TrainBuilder(PlanBuilder):
         def refresh():
             wp[:cout, :, :cin] = weight_fn().reshape(cout, cin, taps).permute(0, 2, 1)
             if frag:
-                wf.view(rows // 32, kc // kstep, 2, 32, ch).copy_(wp.view(rows // 32, 32, kc // kstep, 2, ch).permute(0, 2, 3, 1, 4))
+                src = fragment_view(wp)
+                wf.view(src.shape).copy_(src)
 
         if pack is not None and self.native_pack and pack[0].is_contiguous() and (not frag or taps == 1):
             param, mode = pack

@@ -83,3 +83,28 @@ def test_default_routing_of_the_benchmarked_configuration_is_the_committed_snaps
     # and a switch really moves it (the comparison is not vacuous)
     monkeypatch.setenv("PASN_EXPDW", "0")
     assert [r["kernel"] for r in make_routing_snapshot.routing()] != [r["kernel"] for r in want["rows"]]
+
+
+sys.path.insert(0, GOLDEN)
+import make_routing_snapshot  # noqa: E402
+
+
+@pytest.mark.parametrize("case", make_routing_snapshot.CASES, ids=[c[0] for c in make_routing_snapshot.CASES])
+def test_call_stream_of_every_launch_is_the_committed_one(case, monkeypatch):
+    """What every launch of a compiled plan hands to the library -- entry point, scalar arguments, descriptor fields, buffer dataflow
+    (buffers numbered in order of first use), the bytes of every packed operand, and its ``meta`` row -- equals the digests recorded in
+    tests/golden/call_stream_digests.json, for the four trunks in both compute types and for X3D-S under every switch that reaches a
+    fallback arm of the plan builder.  Runs no kernel: the plan's ops are replayed against a recording stand-in of the library."""
+    for k in [k for k in os.environ if k.startswith("PASN_")]:
+        monkeypatch.delenv(k)
+    _lib.tuning_reload()
+    golden = json.load(open(os.path.join(GOLDEN, "call_stream_digests.json")))
+    fields, want = golden["fields"], golden["cases"][case[0]]
+    assert fields == list(make_routing_snapshot.FIELDS)
+    got, n_ops, arena, naive = make_routing_snapshot.call_stream(case)
+    print(f"{case[0]}: len(ops)={n_ops} arena_bytes={arena} naive_bytes={naive}")
+    for i, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            diff = [f for j, f in enumerate(fields) if g[6 * j: 6 * j + 6] != w[6 * j: 6 * j + 6]]
+            pytest.fail(f"launch {i}: first differing field {diff[0]!r} (all differing: {diff})")
+    assert len(got) == len(want), f"{len(got)} launches, recorded {len(want)}"
