@@ -650,6 +650,43 @@ size_t pasn_roc_auc_workspace_bytes(long M, int K_real);
 int pasn_roc_auc_ovr(const float* probs, const int32_t* labels, long M, int K_real, double* auc, double* auc_per_class, void* workspace,
                      void* stream);
 
+/* Global explanations: the k nearest clips of a split per prototype, kept on the device while a loader is swept (global_explain.py).
+ * The reference ships only the raw material, the whole (clips, P) similarity matrix "for ranking prototypes"
+ * (XProtoNet_Base.py:613-656 get_sim_scores / load_sim_scores; explain_global is a stub); the selection rule per batch is the push's
+ * (push_abs_revision.py:288-307: the clips of the prototype's class, or all clips), kept for k winners instead of one.
+ *
+ * pasn_topk_xproto_update: one launch per batch, no host synchronisation, one wave per prototype.  Per prototype j the batch's eligible
+ * clips (labels[b] == proto_class[j] where class_mask[j] != 0, every clip otherwise) are merged into row j of the caller's state:
+ *   proto_dist [B][P] fp32, labels [B] int64, proto_class [P] int32, class_mask [P] int32
+ *   top_dist  [P][k] fp32   (init +inf)   ascending
+ *   top_index [P][k] int64  (init -1)     global clip index = index_base + b
+ *   top_slot  [P][k] int32  (init 0 .. k-1 per row): the payload slot of each entry; a new entry takes over the slot of the entry it
+ *                           evicts, so every row stays a permutation of 0 .. k-1 and payload rows never move
+ * Order: ascending (distance, global index) -- equal distances put the LOWER global index first, whatever the batch boundaries (the
+ * push keeps the LATER clip on a tie; the two rules differ by design).  Fewer than k eligible clips leave the tail at (+inf, -1).
+ * A clip index must be fed once per sweep.  NaN distances give an unspecified row.
+ * 1 <= k <= 64, 1 <= P <= 4096, B >= 1; anything else, or a NULL pointer, returns PASN_ERR_ARG before any launch (no slow path). */
+int pasn_topk_xproto_update(const float* proto_dist, const int64_t* labels, const int32_t* proto_class, const int32_t* class_mask,
+                            float* top_dist, int64_t* top_index, int32_t* top_slot, int B, int P, int k, int64_t index_base,
+                            void* stream);
+
+/* The winners' payload follows them without a host round trip: called once per payload kind after pasn_topk_xproto_update of the same
+ * batch (the records push_abs_revision.py:300-307 keeps for one winner, for k).  Every (j, e) with
+ * index_base <= top_index[j][e] < index_base + B copies row b = top_index[j][e] - index_base of `payload` to store[j][top_slot[j][e]]
+ * (every entry of the updated row whose index lies in this batch arrived in this batch, so no "fresh" flag is needed).
+ *   payload : per_proto != 0: [B][P][row_elems] (occurrence maps), row (b, j);  per_proto == 0: [B][row_elems] (logits, labels), row b
+ *   store   : [P][k][row_elems];  elem_bytes in {1, 2, 4, 8}: the copy is bitwise, in 16-byte accesses where row size and both base
+ *             addresses allow, else 8 / 4 / elem_bytes.  Same argument limits as the update. */
+int pasn_topk_gather(const int64_t* top_index, const int32_t* top_slot, const void* payload, void* store, int B, int P, int k,
+                     long row_elems, int elem_bytes, int per_proto, int64_t index_base, void* stream);
+
+/* Ranking statistics of one batch (what a consumer of the reference's saved sim_scores / targets, XProtoNet_Base.py:613-656, computes
+ * from the whole matrix): class_sim_sum [P][K] fp64 += (double)(1.0f - proto_dist[b][p]) grouped by labels[b]; class_count [K] int64 +=
+ * the rows per label.  One thread per prototype adds the rows in index order (as sim_sums of pasn_eval_batch_stats): two sweeps over the
+ * same batches are bitwise equal.  Labels outside [0, K) are skipped.  1 <= K <= 64, 1 <= P <= 4096, B >= 1. */
+int pasn_proto_class_stats(const float* proto_dist, const int64_t* labels, int B, int P, int K, double* class_sim_sum,
+                           int64_t* class_count, void* stream);
+
 /* The reference dataset's clip resize on the device (as_dataloader.py:204-207, skimage.transform.resize(window, (T, H, W)) of
  * scikit-image >= 0.19 with its defaults: uint8 / 255, Gaussian anti-aliasing (sigma = max(0, (f - 1) / 2), mode 'mirror', truncate 4)
  * on the shrinking axes, linear zoom with grid_mode (source (o + 0.5) f - 0.5, mode 'mirror')).  That operator is separable,

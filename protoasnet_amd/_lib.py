@@ -142,6 +142,10 @@ SIGNATURES = {
     "pasn_explain_maps_workspace_bytes": (c_size_t, [c_int] * 9),
     "pasn_explain_maps": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                                       c_float, c_float, c_float, c_void_p, c_void_p]),
+    # ---- global explanation (global_explain.py)
+    "pasn_topk_xproto_update": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int64, c_void_p]),
+    "pasn_topk_gather": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_long, c_int, c_int, c_int64, c_void_p]),
+    "pasn_proto_class_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     # ---- evaluation statistics (metrics.py)
     "pasn_eval_batch_stats": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_float, c_long, c_long] + [c_void_p] * 7),
     "pasn_roc_auc_workspace_bytes": (c_size_t, [c_long, c_int]),

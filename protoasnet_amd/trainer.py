@@ -434,6 +434,69 @@ class DPTrainer:
             epoch_number=self.current_epoch, log=self.log, replace_prototypes=replace_prototypes, rank=self.rank, world_size=self.world_size,
             preprocess_input_function=self.prepare_input)
 
+    # ---- global explanations: XProtoNet_Base.py:613-667 and the explain_global stub ----------------------------------------------------
+    def _sim_scores_paths(self, epoch: int, mode: str):
+        d = os.path.join(self.config["save_dir"], "ranking_prototypes")
+        return os.path.join(d, f"sim_scores_{mode}_epoch{epoch}.pth"), os.path.join(d, f"targets_{mode}.pth")
+
+    def get_sim_scores(self, mode: str = "train") -> None:
+        """The reference's ``get_sim_scores``: the (N, P) similarities of ``data_loaders[mode]`` and its targets, saved as CPU float32
+        tensors under ``save_dir/ranking_prototypes/`` with the reference's file names.  Batches are read by ``cine`` / ``target_AS``
+        and go through ``prepare_input``.  Several ranks: every rank sweeps its loader, rank 0 writes the rank-major concatenation.
+        The model is left in the mode it was in; no training state is touched."""
+        epoch = self.current_epoch
+        self.log(f"Epoch: {epoch} generating the sim scores for dataset:{mode}")
+        was_training = self.model.training
+        if self.world_size > 1:
+            self.sync_norm_buffers()
+        self.model.eval()
+        sims, targets = [], []
+        with torch.no_grad():
+            for sample in self.staged(self.data_loaders[mode]):
+                _, similarities, _ = self.model(self.prepare_input(sample["cine"]))
+                sims.append(similarities.float())
+                targets.append(torch.as_tensor(sample["target_AS"]).detach().cpu().to(torch.float32))
+        P = self.model.num_prototypes
+        sim_scores = torch.cat(sims).cpu() if sims else torch.empty((0, P), dtype=torch.float32)
+        y_true_all = torch.cat(targets) if targets else torch.empty((0,), dtype=torch.float32)
+        self.model.train(was_training)
+        if self.world_size > 1:
+            every = [None] * self.world_size
+            dist.all_gather_object(every, (sim_scores, y_true_all))
+            sim_scores, y_true_all = torch.cat([e[0] for e in every]), torch.cat([e[1] for e in every])
+        if self.rank != 0:
+            return
+        sim_path, target_path = self._sim_scores_paths(epoch, mode)
+        os.makedirs(os.path.dirname(sim_path), exist_ok=True)
+        torch.save(sim_scores, sim_path)
+        torch.save(y_true_all, target_path)
+
+    def load_sim_scores(self, epoch: int, mode: str):
+        sim_path, target_path = self._sim_scores_paths(epoch, mode)
+        return torch.load(sim_path), torch.load(target_path)
+
+    def explain_global(self, mode: str = "val", k: int = 10):
+        """What the reference's ``explain_global`` stub leaves open: ``global_explain.nearest_clips`` over ``data_loaders[mode]``; rank 0
+        writes ``save_dir/global/{mode}/epoch-{epoch}/nearest_info.pickle`` (numpy arrays under the ``GlobalExplanation`` field names).
+        Several ranks: the sweep shards the loader itself, as the push does, so ``mode`` must name a FULL sequential loader."""
+        import pickle
+
+        from . import global_explain
+
+        if self.world_size > 1:
+            self.sync_norm_buffers()
+        result = global_explain.nearest_clips(
+            self.data_loaders[mode], self.model, k=k, class_specific=False, abstain_class=bool(self.config.get("abstain_class")),
+            preprocess_input_function=self.prepare_input, rank=self.rank, world_size=self.world_size, log=self.log)
+        if self.rank == 0 and self.config.get("save_dir"):
+            d = os.path.join(self.config["save_dir"], "global", mode, f"epoch-{self.current_epoch}")
+            os.makedirs(d, exist_ok=True)
+            path = os.path.join(d, "nearest_info.pickle")
+            with open(path, "wb") as handle:
+                pickle.dump(result.to_numpy(), handle, protocol=pickle.HIGHEST_PROTOCOL)
+            self.log(f"data successfully saved in {path}")
+        return result
+
     def save_model_w_condition(self, model_name: str, metric_dict: dict, threshold: float) -> None:
         name, metric = next(iter(metric_dict.items()))
         if metric > threshold and self.rank == 0 and self.train_config.get("save", True):
