@@ -149,11 +149,33 @@ def se_operands(fc1: nn.Module, fc2: nn.Module) -> List[torch.Tensor]:
             fc2.weight.detach().float().reshape(c, cse).contiguous(), fc2.bias.detach().float().contiguous()]
 
 
-def pack_dw_taps(w: torch.Tensor, cp: int, device) -> torch.Tensor:
-    """Depthwise weights (C, 1, kt, kh, kw) -> fp32 [taps][cp], zero padded channels."""
+def pack_dw_taps(w: torch.Tensor, cp: int, device, flip: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depthwise weights (C, 1, kt, kh, kw) -> fp32 [taps][cp], zero padded channels.  ``flip``: taps reversed (the stencil of the input
+    gradient).  ``out``: a persistent destination of that shape, whose padding is zero already (the training pass refreshes in place)."""
     c, taps = w.shape[0], w[0].numel()
-    wp = torch.zeros(taps, cp, dtype=torch.float32, device=device)
-    wp[:, :c] = w.detach().float().reshape(c, taps).t()
+    wp = out if out is not None else torch.zeros(taps, cp, dtype=torch.float32, device=device)
+    t = w.detach().float().reshape(c, taps)
+    wp[:, :c] = (t.flip(1) if flip else t).t()
+    return wp
+
+
+def pack_first_mfma(w: torch.Tensor, slot: int, cp: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """First-conv weights (C, Ci, kh, kw) in the matrix-core stem's K order: fp32 [nq][bn][8] -- rows (ci, r) padded to an even count,
+    ``cp`` padded to 32 channels, 8-wide window slots with tap s in slot ``slot`` + s (``pasn_first_conv_mfma_slot``).  The kernel reads
+    the bf16 cast.  ``out`` as in ``pack_dw_taps``."""
+    c, ci, kh, kw = w.shape
+    rows, nq, bn = ci * kh, 2 * ((ci * kh + 1) // 2), 32 * ((cp + 31) // 32)
+    wq = out if out is not None else torch.zeros(nq, bn, 8, dtype=torch.float32, device=device)
+    wq[:rows, :c, slot:slot + kw] = w.permute(1, 2, 0, 3).reshape(rows, c, kw)
+    return wq
+
+
+def pack_first_valu(w: torch.Tensor, cp: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """First-conv weights (C, Ci, kh, kw) -> fp32 [(ci, r, s)][cp], zero padded channels (the VALU first-conv and X3D stem kernels).
+    ``out`` as in ``pack_dw_taps``."""
+    c, ci, kh, kw = w.shape
+    wp = out if out is not None else torch.zeros(ci * kh * kw, cp, dtype=torch.float32, device=device)
+    wp[:, :c] = w.permute(1, 2, 3, 0).reshape(ci * kh * kw, c)
     return wp
 
 
@@ -316,20 +338,15 @@ class PlanBuilder:
         ia, ib = self.in_affine if x.C == 1 else (1.0, 0.0)
         slot = int(self.lib.pasn_first_conv_mfma_slot(dref, code_in, code_out))
         if slot >= 0:
-            # matrix-core stem: weights in the kernel's K order -- rows (ci, r), 8-wide window slots, tap s in slot `slot` + s
-            rows, nq = x.C * k[1], 2 * ((x.C * k[1] + 1) // 2)
-            bn = 32 * ((y.Cp + 31) // 32)
-            wq = torch.zeros(nq, bn, 8, dtype=torch.float32, device=self.device)
-            wq[:rows, : y.C, slot : slot + k[2]] = w.permute(1, 2, 0, 3).reshape(rows, y.C, k[2])
-            wq = wq.to(torch.bfloat16).contiguous()
+            wq = pack_first_mfma(w, slot, y.Cp, self.device).to(torch.bfloat16).contiguous()  # matrix-core stem
+            nq, bn = wq.shape[0], wq.shape[1]
             self.keep += [wq, scale, bias, d]
             a = (wq.data_ptr(), scale.data_ptr(), bias.data_ptr())
             self._note("first_conv", f"first_conv_mfma_kernel<{self._in_name()},{bn // 32},{nq // 2}>" + ("[grey]" if x.C == 1 else ""), nbytes, flops, d)
             fn = self.lib.pasn_first_conv_mfma_fwd
             self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[yb], dref, code_in, ia, ib, st)))
             return y
-        wp = torch.zeros(x.C * k[1] * k[2], y.Cp, dtype=torch.float32, device=self.device)
-        wp[:, : y.C] = w.permute(1, 2, 3, 0).reshape(x.C * k[1] * k[2], y.C)
+        wp = pack_first_valu(w, y.Cp, self.device)
         self.keep += [wp, scale, bias, d]
         a = (wp.data_ptr(), scale.data_ptr(), bias.data_ptr())
         self._note("first_conv", f"first_conv_kernel<{self._in_name()},{self.tname},{y.Cp}>" + ("[grey]" if x.C == 1 else ""), nbytes, flops, d)
@@ -380,10 +397,7 @@ class PlanBuilder:
             fn = self.lib.pasn_x3d_stem_mfma_fwd
             self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[yb], dref, code_in, ia, ib, st)))
             return y
-        wxy = torch.zeros(9 * x.C, y.Cp, dtype=torch.float32, device=self.device)
-        wxy[:, :c] = wsrc.permute(1, 2, 3, 0).reshape(9 * x.C, c)
-        wt = torch.zeros(5, y.Cp, dtype=torch.float32, device=self.device)
-        wt[:, :c] = conv_t.weight.detach().float().reshape(c, 5).t()
+        wxy, wt = pack_first_valu(wsrc, y.Cp, self.device), pack_dw_taps(conv_t.weight, y.Cp, self.device)
         scale, bias = fold_norm(norm, None, c, y.Cp, self.device)
         self.keep += [wxy, wt, scale, bias, d]
         a = (wxy.data_ptr(), wt.data_ptr(), scale.data_ptr(), bias.data_ptr())
@@ -831,11 +845,11 @@ class PlanBuilder:
         return y
 
     # ---- arena planning ---------------------------------------------------------------------------
-    def finish(self, x_in: Act, y_out: Act) -> "Plan":
-        self.bufs[y_out.buf].external = True
+    def _place(self) -> int:
+        """First-fit offset of every internal buffer, in creation order, among the buffers still live then; returns the arena size."""
         live: List[Tuple[int, int, int]] = []  # (offset, size, last)
         total = 0
-        for i, b in enumerate(self.bufs):
+        for b in self.bufs:
             if b.external:
                 continue
             live = [a for a in live if a[2] >= b.first]  # still needed by the op that produces b, or later
@@ -848,7 +862,11 @@ class PlanBuilder:
             b.offset = off
             live.append((off, b.nbytes, b.last))
             total = max(total, off + b.nbytes)
-        return Plan(self, x_in, y_out, total)
+        return total
+
+    def finish(self, x_in: Act, y_out: Act) -> "Plan":
+        self.bufs[y_out.buf].external = True
+        return Plan(self, x_in, y_out, self._place())
 
 
 class Plan:

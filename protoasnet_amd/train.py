@@ -10,29 +10,52 @@ analysis as the inference plan -- an activation stays resident exactly until the
 Parameters stay fp32 ``nn.Parameter``s (the optimizer and the RCCL gradient all-reduce see ordinary ``.grad`` tensors);
 activations and activation gradients are fp32 or bf16 (``set_compute_dtype``); statistics, reductions and parameter
 gradients are fp32.  ``TrainPlan`` is driven by ``_TrainFn`` (a ``torch.autograd.Function``), so the reference's losses
-and optimizers sit on top unchanged.  Kernels: ``csrc/train.hip``, ``csrc/wgrad.hip``, ``csrc/head_train.hip`` plus the
+and optimizers sit on top unchanged.
+
+``TrainBuilder.unit`` drives one ``_Unit`` record through its stages: forward ``_fwd_first`` / ``_fwd_dw`` / ``_dense`` (raw conv), ``_fwd_stats``,
+``_fwd_gate_affine``; backward (``_bwd_unit``, bound to the record on the tape) ``_bwd_pointwise`` (reduce, ``_bwd_se``, apply; returns dy), then
+``_bwd_first``, ``_bwd_dw`` (+ ``_bwd_dw_same``) or ``_bwd_dense_wgrad`` + ``_bwd_dense_dgrad``.  The ORDER of buffer creation, launches, side launches
+and joins decides arena offsets and live ranges: tests/test_cpu_train_stream.py pins it on the CPU.  Kernels: ``csrc/train.hip``, ``csrc/wgrad.hip``, ``csrc/head_train.hip`` plus the
 inference conv kernels (a 1x1x1 conv's input gradient is the same kernel with the transposed weight).
 """
 from __future__ import annotations
 
 import ctypes
-import os
-from typing import Callable, Dict, List, Optional, Tuple
+import functools
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib
 from ._lib import ConvDesc, XProtoDesc
-from .plan import ALIGN, Act, PlanBuilder, _triple, frag_steps, fragment_view, round_up
+from .plan import ALIGN, Act, PlanBuilder, _triple, frag_steps, fragment_view, pack_dw_taps, pack_first_mfma, pack_first_valu, round_up
 
 
-def _need_fp32_param(p: torch.Tensor, what: str) -> None:
-    if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda:
+def _need_fp32_param(p: torch.Tensor, what: str, device) -> None:
+    if p.dtype != torch.float32 or not p.is_contiguous() or p.device.type != torch.device(device).type:
         raise RuntimeError(
             f"training keeps fp32 master parameters on the GPU ({what} is {p.dtype} on {p.device}); "
             "use model.set_compute_dtype(torch.bfloat16) for bf16 activations instead of casting the model"
         )
+
+
+# One weight the native one-launch packer (``pasn_pack_weights``) writes from its live parameter every step.  Source dims as the PARAMETER
+# has them; mode 0 forward / 1 input gradient of a dense conv, 2 depthwise taps, 3 depthwise taps reversed.
+PackJob = NamedTuple("PackJob", [("param", torch.Tensor), ("dst", torch.Tensor), ("mode", int), ("cout", int), ("cin", int), ("taps", int),
+                                 ("rows", int), ("kc", int), ("frag", int), ("kstep", int), ("ch", int)])
+
+
+class _Unit:
+    """What one conv unit's forward stages leave for each other and for its backward stages (the tape entry is ``_bwd_unit`` bound to it)."""
+
+    __slots__ = ("x", "y", "out", "residual", "conv", "norm", "se", "kind", "k", "s", "p", "actc", "d", "dref", "stat", "stat_buf", "pool_buf",
+                 "gate_buf", "dw_w", "dw_rows", "plain", "x_live", "w_live", "res_live")
+
+    @property
+    def dims(self) -> Tuple[int, int, int, int]:
+        """(N, positions, C, Cp) of the conv's output."""
+        return self.y.N, self.y.positions, self.y.C, self.y.Cp
 
 
 class TrainBuilder(PlanBuilder):
@@ -46,9 +69,8 @@ class TrainBuilder(PlanBuilder):
         self.readers: Dict[int, int] = {}      # activation buffer id -> number of ops that consume it (conv input, residual, pool, head)
         self.red_hook: Dict[int, dict] = {}    # activation buffer id -> how its producer unit's backward sums can be taken by a fused dgrad
         self.refresh: List[Callable[[], None]] = []
-        # weights packed by the native one-launch packer (pasn_pack_weights): (parameter, destination, mode, cout, cin, taps, rows, kc,
-        # frag, kstep, ch) -- source dims as the PARAMETER has them.  PASN_NO_PACK=1: torch expressions per parameter (the old path)
-        self.pack_jobs: List[tuple] = []
+        # weights packed by the native one-launch packer.  PASN_NO_PACK=1: torch expressions per parameter (``refresh``, the old path)
+        self.pack_jobs: List[PackJob] = []
         self.native_pack = _lib.tuning_get("PASN_NO_PACK") != "1"
         self.pslots: List[Tuple[torch.Tensor, int, int]] = []
         self._slot_of: Dict[int, int] = {}
@@ -83,11 +105,23 @@ class TrainBuilder(PlanBuilder):
     def slot(self, p: torch.Tensor) -> int:
         """Offset (in floats) of ``p``'s gradient inside the flat fp32 gradient buffer of one backward pass."""
         if id(p) not in self._slot_of:
-            _need_fp32_param(p, "a parameter")
+            _need_fp32_param(p, "a parameter", self.device)
             self._slot_of[id(p)] = self.gsize
             self.pslots.append((p, self.gsize, p.numel()))
             self.gsize += round_up(p.numel(), 64)
         return self._slot_of[id(p)]
+
+    def _reads(self, *acts: Optional[Act]) -> None:
+        """Count one more consumer of each activation (conv input, residual, pool, head)."""
+        for a in acts:
+            if a is not None:
+                self.readers[a.buf] = self.readers.get(a.buf, 0) + 1
+
+    def _ones_zeros(self, rows: int, *kept) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The (scale 1, bias 0) epilogue constants of a raw conv launch; keeps them alive after the launch's own operands ``kept``."""
+        one, zero = self.const(rows, 1.0), self.const(rows, 0.0)
+        self.keep += [*kept, one, zero]
+        return one, zero
 
     def like(self, a: Act) -> Act:
         return Act(a.N, a.T, a.H, a.W, a.C, a.Cp, self._new_buf(a.N * a.positions * a.Cp * self.es))
@@ -193,11 +227,10 @@ class TrainBuilder(PlanBuilder):
             param, mode = pack
             src_cout, src_cin = (cout, cin) if mode == 0 else (cin, cout)
             assert param.numel() == src_cout * src_cin * taps
-            self.pack_jobs.append((param, wf if frag else wp, mode, src_cout, src_cin, taps, rows, kc, int(frag), kstep, ch))
+            self.pack_jobs.append(PackJob(param, wf if frag else wp, mode, src_cout, src_cin, taps, rows, kc, int(frag), kstep, ch))
         else:
             self.refresh.append(refresh)
-        one, zero = self.const(rows, 1.0), self.const(rows, 0.0)
-        self.keep += [wp, wf, one, zero]
+        one, zero = self._ones_zeros(rows, wp, wf)
         rb = residual.buf if residual is not None else None
         self._use(x.buf, y.buf, rb)
         self._op(self.lib.pasn_conv3d_fwd, self.B(x.buf), (wf if frag else wp).data_ptr(), one.data_ptr(), zero.data_ptr(), self.B(rb), 0,
@@ -207,309 +240,349 @@ class TrainBuilder(PlanBuilder):
     # ---- one conv (+ norm) (+ squeeze-excite) (+ residual) + activation unit ---------------------------------------------
     def unit(self, x: Act, conv: nn.Module, norm: Optional[nn.Module], act: str, kind: str = "conv",
              residual: Optional[Act] = None, se: Optional[nn.Module] = None) -> Act:
-        k, s, p = _triple(conv.kernel_size, 1), _triple(conv.stride, 1), _triple(conv.padding, 0)
-        cout, cin = conv.out_channels, conv.in_channels
-        _need_fp32_param(conv.weight, "a conv weight")
-        taps = k[0] * k[1] * k[2]
-        y = self._out_act(x, cout, k, s, p)
-        N, S, C, Cp = y.N, y.positions, y.C, y.Cp
-        code, lib, B, Pm = self.code, self.lib, self.B, self.Pm
-        actc = _lib.ACT[act]
-        dw_w = None
-        self.readers[x.buf] = self.readers.get(x.buf, 0) + 1
-        if residual is not None:
-            self.readers[residual.buf] = self.readers.get(residual.buf, 0) + 1
-        # ---------------- forward conv (raw output) ----------------
+        """Emit the unit's forward launches (raw conv -> statistics -> gate -> affine + activation) and put its backward on the tape."""
+        u = _Unit()
+        u.x, u.conv, u.norm, u.se, u.residual, u.kind, u.actc = x, conv, norm, se, residual, kind, _lib.ACT[act]
+        u.k, u.s, u.p = k, s, p = _triple(conv.kernel_size, 1), _triple(conv.stride, 1), _triple(conv.padding, 0)
+        _need_fp32_param(conv.weight, "a conv weight", self.device)
+        u.y = self._out_act(x, conv.out_channels, k, s, p)
+        u.dw_w, u.dw_rows = None, 0
+        self._reads(x, residual)
         if kind == "first":
-            assert x.planar and x.C in (1, 3) and k[0] == 1 and s[0] == 1 and p[0] == 0
-            Ci = x.C  # 1: a grey clip (already normalised); its three identical channels' taps are summed from the live weight at every refresh
-
-            def wsrc():
-                w = conv.weight.detach().reshape(C, 3, k[1], k[2])
-                return w if Ci == 3 else w.sum(dim=1, keepdim=True)
-
-            d = self._desc(x, y, k, s, p, "none")
-            one, zero = self.const(Cp, 1.0), self.const(Cp, 0.0)
-            slot = int(lib.pasn_first_conv_mfma_slot(ctypes.byref(d), _lib.dtype_code(self.in_dtype), code))
-            self._use(x.buf, y.buf)
-            if slot >= 0:
-                # the 7x7 stride-2 stems with bf16 activations: matrix-core kernel, weights in its K order (rows (ci, r), 8-wide window slots)
-                rows, nq, bn = Ci * k[1], 2 * ((Ci * k[1] + 1) // 2), 32 * ((Cp + 31) // 32)
-                wq32 = torch.zeros(nq, bn, 8, dtype=torch.float32, device=self.device)
-                wq = torch.zeros(nq, bn, 8, dtype=torch.bfloat16, device=self.device)
-
-                def refresh_first():
-                    wq32[:rows, :C, slot:slot + k[2]] = wsrc().permute(1, 2, 0, 3).reshape(rows, C, k[2])
-                    wq.copy_(wq32)
-
-                self.refresh.append(refresh_first)
-                self.keep += [wq32, wq, one, zero]
-                self._op(lib.pasn_first_conv_mfma_fwd, B(x.buf), wq.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf), ctypes.byref(d),
-                         _lib.dtype_code(self.in_dtype), 1.0, 0.0)
-            else:
-                wfirst = torch.zeros(Ci * k[1] * k[2], Cp, dtype=torch.float32, device=self.device)
-                self.refresh.append(lambda: wfirst[:, :C].copy_(wsrc().permute(1, 2, 3, 0).reshape(Ci * k[1] * k[2], C)))
-                self.keep += [wfirst, one, zero]
-                if Ci == 1:
-                    self._op(lib.pasn_first_conv_gray_fwd, B(x.buf), wfirst.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf),
-                             ctypes.byref(d), _lib.dtype_code(self.in_dtype), code, 1.0, 0.0)
-                else:
-                    self._op(lib.pasn_first_conv_fwd, B(x.buf), wfirst.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf), ctypes.byref(d),
-                             _lib.dtype_code(self.in_dtype), code)
+            u.d = self._fwd_first(u)
         elif kind == "dw":
-            assert conv.groups == cin == cout == x.C and not x.planar
-            dw_w = torch.zeros(taps, Cp, dtype=torch.float32, device=self.device)
-            d = self._desc(x, y, k, s, p, "none")
-            if self.native_pack and conv.weight.is_contiguous():
-                self.pack_jobs.append((conv.weight, dw_w, 2, C, 1, taps, taps, Cp, 0, 0, 0))
-            else:
-                self.refresh.append(lambda: dw_w[:, :C].copy_(conv.weight.detach().reshape(C, taps).t()))
-            one, zero = self.const(Cp, 1.0), self.const(Cp, 0.0)
-            self.keep += [dw_w, one, zero]
-            # the stencil can take the unit's batch statistics in the same pass over y (saves the read of y by pasn_bn_stats_fwd)
-            dw_rows = int(lib.pasn_dwconv3d_stats_rows(ctypes.byref(d), code)) if norm is not None and norm.momentum is not None else 0
-            if dw_rows == 0:
-                self._use(x.buf, y.buf)
-                self._op(lib.pasn_dwconv3d_fwd, B(x.buf), dw_w.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf), 0, ctypes.byref(d), code)
+            u.d = self._fwd_dw(u)
         else:
             assert conv.groups == 1 and not x.planar
-            d = self._dense(x, y, k, s, p, cout, cin, lambda: conv.weight.detach(), pack=(conv.weight, 0))
-        dref = ctypes.byref(d)
-        # ---------------- statistics / affine ----------------
-        plain = norm is None and conv.bias is None and act == "none" and residual is None and se is None
-        stat_buf = pool_buf = gate_buf = None
-        stat = 0  # address source of the unit's (mean, invstd, sc, sh) table
+            u.d = self._dense(x, u.y, k, s, p, conv.out_channels, conv.in_channels, lambda: conv.weight.detach(), pack=(conv.weight, 0))
+        u.dref = ctypes.byref(u.d)
+        u.plain = norm is None and conv.bias is None and act == "none" and residual is None and se is None
+        self._fwd_stats(u)
+        self._fwd_gate_affine(u)
+        if norm is not None and se is None and residual is None and not u.plain and self.groups == 1:
+            # a consumer whose input gradient is a stencil launch (stride-1 depthwise dgrad) may take this unit's backward sums in that
+            # launch: it leaves the coefficient buffer in hook["coef"], and _bwd_pointwise then skips its own reduce pass
+            self.red_hook[u.out.buf] = {"y_buf": u.y.buf, "stat": u.stat, "stat_buf": u.stat_buf, "actc": u.actc,
+                                        "dg": lambda: self.Gof(norm.weight), "db": lambda: self.Gof(norm.bias), "coef": None}
+        own = [conv.weight, conv.bias] + ([norm.weight, norm.bias] if norm is not None else []) + \
+              ([se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias] if se is not None else [])
+        own_live = any(t is not None and t.requires_grad for t in own)
+        u.x_live = self.live.get(x.buf, False)
+        u.res_live = residual is not None and self.live.get(residual.buf, False)
+        self.live[u.out.buf] = u.x_live or own_live or u.res_live
+        u.w_live = conv.weight.requires_grad
+        self.tape.append(functools.partial(self._bwd_unit, u))
+        return u.out
+
+    # ---- forward stages of a unit --------------------------------------------------------------------------------------------
+    def _fwd_first(self, u: "_Unit") -> ConvDesc:
+        """The first conv on the planar clip: matrix-core kernel where the library has a slot for the geometry, else the VALU kernels."""
+        x, y, conv, k, lib, B = u.x, u.y, u.conv, u.k, self.lib, self.B
+        assert x.planar and x.C in (1, 3) and k[0] == 1 and u.s[0] == 1 and u.p[0] == 0
+        Ci, C, Cp = x.C, y.C, y.Cp  # Ci 1: a grey clip (already normalised); its three identical channels' taps are summed from the live weight at every refresh
+
+        def wsrc():
+            w = conv.weight.detach().reshape(C, 3, k[1], k[2])
+            return w if Ci == 3 else w.sum(dim=1, keepdim=True)
+
+        d = self._desc(x, y, k, u.s, u.p, "none")
+        code_in = _lib.dtype_code(self.in_dtype)
+        slot = int(lib.pasn_first_conv_mfma_slot(ctypes.byref(d), code_in, self.code))
+        self._use(x.buf, y.buf)
+        if slot >= 0:
+            # the 7x7 stride-2 stems with bf16 activations: matrix-core kernel, weights in its K order (plan.pack_first_mfma)
+            wq32 = pack_first_mfma(wsrc(), slot, Cp, self.device)
+            wq = torch.zeros_like(wq32, dtype=torch.bfloat16)
+            self.refresh.append(lambda: wq.copy_(pack_first_mfma(wsrc(), slot, Cp, self.device, out=wq32)))
+            one, zero = self._ones_zeros(Cp, wq32, wq)
+            self._op(lib.pasn_first_conv_mfma_fwd, B(x.buf), wq.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf), ctypes.byref(d),
+                     code_in, 1.0, 0.0)
+            return d
+        wfirst = torch.zeros(Ci * k[1] * k[2], Cp, dtype=torch.float32, device=self.device)
+        self.refresh.append(lambda: pack_first_valu(wsrc(), Cp, self.device, out=wfirst))
+        one, zero = self._ones_zeros(Cp, wfirst)
+        if Ci == 1:
+            self._op(lib.pasn_first_conv_gray_fwd, B(x.buf), wfirst.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf),
+                     ctypes.byref(d), code_in, self.code, 1.0, 0.0)
+        else:
+            self._op(lib.pasn_first_conv_fwd, B(x.buf), wfirst.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf), ctypes.byref(d),
+                     code_in, self.code)
+        return d
+
+    def _dw_taps(self, conv: nn.Module, cp: int, flip: bool) -> torch.Tensor:
+        """Persistent fp32 [taps][cp] copy of a depthwise weight (``flip``: taps reversed), refreshed by the native packer or by torch."""
+        c, taps = conv.out_channels, conv.weight[0].numel()
+        w = torch.zeros(taps, cp, dtype=torch.float32, device=self.device)
+        if self.native_pack and conv.weight.is_contiguous():
+            self.pack_jobs.append(PackJob(conv.weight, w, 3 if flip else 2, c, 1, taps, taps, cp, 0, 0, 0))
+        else:
+            self.refresh.append(lambda: pack_dw_taps(conv.weight, cp, self.device, flip=flip, out=w))
+        return w
+
+    def _fwd_dw(self, u: "_Unit") -> ConvDesc:
+        """Depthwise stencil; where it can take the unit's batch statistics in the same pass, its launch is left to ``_fwd_stats``."""
+        x, y, conv, norm = u.x, u.y, u.conv, u.norm
+        assert conv.groups == conv.in_channels == conv.out_channels == x.C and not x.planar
+        u.dw_w = self._dw_taps(conv, y.Cp, flip=False)
+        d = self._desc(x, y, u.k, u.s, u.p, "none")
+        one, zero = self._ones_zeros(y.Cp, u.dw_w)
+        # the stencil can take the unit's batch statistics in the same pass over y (saves the read of y by pasn_bn_stats_fwd)
+        if norm is not None and norm.momentum is not None:
+            u.dw_rows = int(self.lib.pasn_dwconv3d_stats_rows(ctypes.byref(d), self.code))
+        if u.dw_rows == 0:
+            self._use(x.buf, y.buf)
+            self._op(self.lib.pasn_dwconv3d_fwd, self.B(x.buf), u.dw_w.data_ptr(), one.data_ptr(), zero.data_ptr(), self.B(y.buf), 0,
+                     ctypes.byref(d), self.code)
+        return d
+
+    def _fwd_stats(self, u: "_Unit") -> None:
+        """The unit's per-group (mean, invstd, sc, sh) table: batch statistics of a norm layer, or the constant table of a bare bias."""
+        conv, norm, x, y, lib, B, Pm, code = u.conv, u.norm, u.x, u.y, self.lib, self.B, self.Pm, self.code
+        N, S, C, Cp = u.dims
+        u.stat_buf = u.pool_buf = u.gate_buf = None
+        u.stat = 0  # address source of the table
         if norm is not None:
             assert conv.bias is None, "a conv followed by a norm layer carries no bias in the trunks built here"
             for t in (norm.weight, norm.bias):
-                _need_fp32_param(t, "a norm parameter")
+                _need_fp32_param(t, "a norm parameter", self.device)
             if norm.momentum is None:
                 raise NotImplementedError("cumulative-average BatchNorm (momentum=None) is not built")
-            fused_dw = kind == "dw" and dw_rows > 0
-            chunks = dw_rows if fused_dw else int(lib.pasn_train_chunks(N, S, Cp))
+            chunks = u.dw_rows or int(lib.pasn_train_chunks(N, S, Cp))
             ws = self._new_buf(N * chunks * 2 * Cp * 4)
-            stat_buf = self._new_buf(self.groups * 4 * Cp * 4)
-            pool_buf = self._new_buf(N * Cp * 4) if se is not None else None
+            u.stat_buf = self._new_buf(self.groups * 4 * Cp * 4)
+            u.pool_buf = self._new_buf(N * Cp * 4) if u.se is not None else None
             track = bool(norm.track_running_stats and norm.running_mean is not None)
             if track:
                 self.nbt.append(norm.num_batches_tracked)
-            if fused_dw:
-                self._use(x.buf, y.buf, ws, stat_buf, pool_buf)
-                self._op(lib.pasn_dwconv3d_stats_fwd_g, B(x.buf), dw_w.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf), B(ws), Pm(norm.weight),
-                         Pm(norm.bias), Pm(norm.running_mean if track else None), Pm(norm.running_var if track else None), float(norm.momentum),
-                         float(norm.eps), B(stat_buf), B(pool_buf), dref, code, self.groups)
+            tail = (B(ws), Pm(norm.weight), Pm(norm.bias), Pm(norm.running_mean if track else None), Pm(norm.running_var if track else None),
+                    float(norm.momentum), float(norm.eps), B(u.stat_buf), B(u.pool_buf))
+            if u.dw_rows > 0:
+                one, zero = self.const(Cp, 1.0), self.const(Cp, 0.0)
+                self._use(x.buf, y.buf, ws, u.stat_buf, u.pool_buf)
+                self._op(lib.pasn_dwconv3d_stats_fwd_g, B(x.buf), u.dw_w.data_ptr(), one.data_ptr(), zero.data_ptr(), B(y.buf), *tail,
+                         u.dref, code, self.groups)
             else:
-                self._use(y.buf, ws, stat_buf, pool_buf)
-                self._op(lib.pasn_bn_stats_fwd_g, B(y.buf), B(ws), Pm(norm.weight), Pm(norm.bias), Pm(norm.running_mean if track else None),
-                         Pm(norm.running_var if track else None), float(norm.momentum), float(norm.eps), B(stat_buf), B(pool_buf), N, S, C, Cp, code,
-                         self.groups)
-            stat = B(stat_buf)
-        elif not plain:
+                self._use(y.buf, ws, u.stat_buf, u.pool_buf)
+                self._op(lib.pasn_bn_stats_fwd_g, B(y.buf), *tail, N, S, C, Cp, code, self.groups)
+            u.stat = B(u.stat_buf)
+        elif not u.plain:
             stat_t = torch.zeros(self.groups, 4, Cp, dtype=torch.float32, device=self.device)  # per group (mean 0, invstd 1, sc 1, sh = bias)
             stat_t[:, 1, :C] = 1.0
             stat_t[:, 2, :C] = 1.0
             if conv.bias is not None:
-                _need_fp32_param(conv.bias, "a conv bias")
+                _need_fp32_param(conv.bias, "a conv bias", self.device)
                 self.refresh.append(lambda: stat_t[:, 3, :C].copy_(conv.bias.detach().expand(self.groups, C)))
             self.keep.append(stat_t)
-            stat = stat_t.data_ptr()
+            u.stat = stat_t.data_ptr()
+
+    def _fwd_gate_affine(self, u: "_Unit") -> None:
+        """Squeeze-excite gate from the pooled statistics, then out = act(affine(y) * gate + residual); a plain unit's output is y itself."""
+        se, residual, y, lib, B, Pm = u.se, u.residual, u.y, self.lib, self.B, self.Pm
+        N, S, C, Cp = u.dims
         if se is not None:
-            assert norm is not None
-            cse = se.fc1.out_channels
+            assert u.norm is not None
             for t in (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias):
-                _need_fp32_param(t, "a squeeze-excite parameter")
-            gate_buf = self._new_buf(N * Cp * 4)
-            self._use(pool_buf, gate_buf)
-            self._op(lib.pasn_se_gate_fwd, B(pool_buf), 1, 1, Pm(se.fc1.weight), Pm(se.fc1.bias), Pm(se.fc2.weight), Pm(se.fc2.bias), B(gate_buf),
-                     N, C, Cp, cse)
-        if plain:
-            out = y
+                _need_fp32_param(t, "a squeeze-excite parameter", self.device)
+            u.gate_buf = self._new_buf(N * Cp * 4)
+            self._use(u.pool_buf, u.gate_buf)
+            self._op(lib.pasn_se_gate_fwd, B(u.pool_buf), 1, 1, Pm(se.fc1.weight), Pm(se.fc1.bias), Pm(se.fc2.weight), Pm(se.fc2.bias),
+                     B(u.gate_buf), N, C, Cp, se.fc1.out_channels)
+        if u.plain:
+            u.out = y
+            return
+        u.out = self.like(y)
+        if residual is not None:
+            assert (residual.N, residual.positions, residual.Cp) == (N, S, Cp)
+        rb = residual.buf if residual is not None else None
+        self._use(y.buf, u.out.buf, rb, u.stat_buf, u.gate_buf)
+        self._op(lib.pasn_affine_act_fwd_g, B(y.buf), u.stat, B(rb), B(u.gate_buf), B(u.out.buf), N, S, C, Cp, u.actc, self.code, self.groups)
+
+    # ---- backward stages of a unit (run from the tape, last unit first) -------------------------------------------------------------
+    def _bwd_unit(self, u: "_Unit") -> None:
+        g = self.grads.get(u.out.buf)
+        if g is None or not self.live[u.out.buf]:
+            return  # nothing downstream needs this unit's gradient / nothing in or before it is trainable
+        dy = g if u.plain else self._bwd_pointwise(u, g)
+        if dy is None or not (u.x_live or u.w_live):
+            return  # only this unit's norm / bias / SE parameters were trainable: their gradients are out already
+        if u.kind == "first":
+            self._bwd_first(u, dy)
+        elif u.kind == "dw":
+            self._bwd_dw(u, dy)
         else:
-            out = self.like(y)
-            if residual is not None:
-                assert (residual.N, residual.positions, residual.Cp) == (N, S, Cp)
-            rb = residual.buf if residual is not None else None
-            self._use(y.buf, out.buf, rb, stat_buf, gate_buf)
-            self._op(lib.pasn_affine_act_fwd_g, B(y.buf), stat, B(rb), B(gate_buf), B(out.buf), N, S, C, Cp, actc, code, self.groups)
+            self._bwd_dense_wgrad(u, dy)
+            if u.x_live:
+                self._bwd_dense_dgrad(u, dy)
 
-        if norm is not None and se is None and residual is None and not plain and self.groups == 1:
-            # a consumer whose input gradient is a stencil launch (stride-1 depthwise dgrad) may take this unit's backward sums in that
-            # launch: it leaves the coefficient buffer in hook["coef"], and backward() below then skips its own reduce pass
-            self.red_hook[out.buf] = {"y_buf": y.buf, "stat": stat, "stat_buf": stat_buf, "actc": actc,
-                                      "dg": lambda: self.Gof(norm.weight), "db": lambda: self.Gof(norm.bias), "coef": None}
-        own = [conv.weight, conv.bias] + ([norm.weight, norm.bias] if norm is not None else []) + \
-              ([se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias] if se is not None else [])
-        own_live = any(t is not None and t.requires_grad for t in own)
-        x_live = self.live.get(x.buf, False)
-        res_live = residual is not None and self.live.get(residual.buf, False)
-        self.live[out.buf] = x_live or own_live or res_live
-        w_live = conv.weight.requires_grad
+    def _bwd_pointwise(self, u: "_Unit", g: Act) -> Optional[Act]:
+        """Everything between the unit's output gradient and its conv's output gradient: the reduce pass (activation', residual, sums for
+        the norm's coefficients, dgamma / dbeta or the bias gradient), the squeeze-excite gate's backward, the norm's apply pass.  Returns
+        dy, or None when nothing before the pointwise part is trainable."""
+        norm, conv, se, residual, y, lib, B, code = u.norm, u.conv, u.se, u.residual, u.y, self.lib, self.B, self.code
+        N, S, C, Cp = u.dims
+        chunks = int(lib.pasn_train_chunks(N, S, Cp))
+        ws = self._new_buf(N * chunks * 2 * Cp * 4)
+        coef = self._new_buf(self.groups * 2 * Cp * 4)
+        rb = residual.buf if residual is not None else None
+        if norm is not None:
+            dg, db = self.Gof(norm.weight), self.Gof(norm.bias)
+        elif conv.bias is not None:
+            dg, db = 0, self.Gof(conv.bias)
+        else:
+            dg = db = 0
+        addb = None  # set by the analytic squeeze-excite arm: the apply pass then forms d'' = d' gate + add on the fly
+        lazy = se is None and norm is not None and residual is None  # nobody but the apply pass reads the differentiated d
+        hook = self.red_hook.get(u.out.buf)
+        if hook is not None and hook["coef"] is not None:
+            coef = hook["coef"]  # the consumer's fused dgrad already took the sums (and dgamma / dbeta)
+        elif se is None:
+            self._use(g.buf, y.buf, rb, u.stat_buf, ws, coef)
+            self._op(lib.pasn_unit_bwd_reduce_g, 3 if lazy else 0, B(g.buf), B(y.buf), u.stat, B(rb), 0, 0, B(ws), B(coef), dg, db,
+                     N, S, C, Cp, u.actc, code, self.groups)
+        else:
+            addb = self._bwd_se(u, g, ws, coef, dg, db, chunks)
+        if residual is not None and u.res_live:
+            self.add_grad(residual, g)  # after mode 0, g is the gradient of the pre-activation sum
+        if not (u.x_live or u.w_live):
+            return None
+        if norm is not None and addb is not None:
+            self._use(g.buf, y.buf, u.stat_buf, coef, u.gate_buf, addb)
+            self._op(lib.pasn_bn_bwd_apply_se_g, B(g.buf), B(y.buf), u.stat, B(coef), B(u.gate_buf), B(addb), B(g.buf), N, S, C, Cp, code, self.groups)
+            return g
+        if norm is None:
+            return g
+        dy = self.like(y) if residual is not None else g
+        self._use(g.buf, y.buf, u.stat_buf, coef, dy.buf)
+        self._op(lib.pasn_bn_bwd_apply_g, B(g.buf), B(y.buf), u.stat, B(coef), B(dy.buf), N, S, C, Cp, u.actc if lazy else 0, code, self.groups)
+        return dy
 
-        # ---------------- backward emitter ----------------
-        def backward() -> None:
-            g = self.grads.get(out.buf)
-            if g is None or not self.live[out.buf]:
-                return  # nothing downstream needs this unit's gradient / nothing in or before it is trainable
-            dy = g
-            if not plain:
-                chunks = int(lib.pasn_train_chunks(N, S, Cp))
-                ws = self._new_buf(N * chunks * 2 * Cp * 4)
-                coef = self._new_buf(self.groups * 2 * Cp * 4)
-                rb = residual.buf if residual is not None else None
-                red = lib.pasn_unit_bwd_reduce_g
-                if norm is not None:
-                    dg, db = self.Gof(norm.weight), self.Gof(norm.bias)
-                elif conv.bias is not None:
-                    dg, db = 0, self.Gof(conv.bias)
-                else:
-                    dg = db = 0
-                se_analytic = False
-                lazy = se is None and norm is not None and residual is None  # nobody but the apply pass reads the differentiated d
-                hook = self.red_hook.get(out.buf)
-                if hook is not None and hook["coef"] is not None:
-                    coef = hook["coef"]  # the consumer's fused dgrad already took the sums (and dgamma / dbeta)
-                elif se is None:
-                    self._use(g.buf, y.buf, rb, stat_buf, ws, coef)
-                    self._op(red, 3 if lazy else 0, B(g.buf), B(y.buf), stat, B(rb), 0, 0, B(ws), B(coef), dg, db, N, S, C, Cp, actc, code, self.groups)
-                elif residual is None and not _lib.tuning_get("PASN_NO_SE_ANALYTIC"):
-                    # squeeze-excite unit, ONE pass over (d, y): mode 4 leaves d' = d act'(.) and per-clip (sum d', sum d' yhat, sum yhat);
-                    # the gate's gradient, the norm's coefficients and dgamma / dbeta follow from those per clip (d'' = d' gate + add is
-                    # affine in d'), and the apply pass forms d'' on the fly -- the second pass over the tensor (mode 2) is gone
-                    cse = se.fc1.out_channels
-                    se_analytic = True
-                    addb = self._new_buf(N * Cp * 4)
-                    pn = self._new_buf(int(lib.pasn_se_bwd_workspace_floats(N, C, cse)) * 4)
-                    ws3 = self._new_buf(N * chunks * 3 * Cp * 4)
-                    o = [self.Gof(t, nullable=False) for t in (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias)]
-                    self._use(g.buf, y.buf, stat_buf, gate_buf, ws3)
-                    self._op(red, 4, B(g.buf), B(y.buf), stat, 0, B(gate_buf), 0, B(ws3), 0, 0, 0, N, S, C, Cp, actc, code, self.groups)
-                    self._use(ws3, pool_buf, stat_buf, gate_buf, addb, pn, coef)
-                    self._op(lib.pasn_se_gate_bwd_stat_g, B(ws3), B(pool_buf), stat, B(gate_buf), Pm(se.fc1.weight), Pm(se.fc1.bias),
-                             Pm(se.fc2.weight), Pm(se.fc2.bias), B(addb), B(pn), o[0], o[1], o[2], o[3], B(coef), dg, db, N, S, C, Cp, cse, self.groups)
-                else:
-                    cse = se.fc1.out_channels
-                    addb = self._new_buf(N * Cp * 4)
-                    pn = self._new_buf(int(lib.pasn_se_bwd_workspace_floats(N, C, cse)) * 4)
-                    o = [self.Gof(t, nullable=False) for t in (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias)]
-                    self._use(g.buf, y.buf, stat_buf, gate_buf, ws)
-                    self._op(red, 1, B(g.buf), B(y.buf), stat, 0, B(gate_buf), 0, B(ws), 0, 0, 0, N, S, C, Cp, actc, code, self.groups)
-                    self._use(ws, pool_buf, addb, pn)
-                    self._op(lib.pasn_se_gate_bwd, B(ws), B(pool_buf), Pm(se.fc1.weight), Pm(se.fc1.bias), Pm(se.fc2.weight), Pm(se.fc2.bias),
-                             B(addb), B(pn), o[0], o[1], o[2], o[3], N, S, C, Cp, cse)
-                    self._use(g.buf, y.buf, stat_buf, gate_buf, addb, ws, coef)
-                    self._op(red, 2, B(g.buf), B(y.buf), stat, 0, B(gate_buf), B(addb), B(ws), B(coef), dg, db, N, S, C, Cp, actc, code, self.groups)
-                if residual is not None and res_live:
-                    self.add_grad(residual, g)  # after mode 0, g is the gradient of the pre-activation sum
-                if not (x_live or w_live):
-                    return  # only this unit's norm / bias / SE parameters were trainable: their gradients are out already
-                if norm is not None and se_analytic:
-                    self._use(g.buf, y.buf, stat_buf, coef, gate_buf, addb)
-                    self._op(lib.pasn_bn_bwd_apply_se_g, B(g.buf), B(y.buf), stat, B(coef), B(gate_buf), B(addb), B(g.buf), N, S, C, Cp, code, self.groups)
-                elif norm is not None:
-                    dy = self.like(y) if residual is not None else g
-                    self._use(g.buf, y.buf, stat_buf, coef, dy.buf)
-                    self._op(lib.pasn_bn_bwd_apply_g, B(g.buf), B(y.buf), stat, B(coef), B(dy.buf), N, S, C, Cp, actc if lazy else 0, code, self.groups)
-            elif not (x_live or w_live):
-                return
-            # ---- weight gradient
-            dW = self.Gof(conv.weight)
-            if kind == "first":
-                if w_live:
-                    wsz = int(lib.pasn_first_conv_wgrad_workspace_bytes(dref, code))
-                    wsb = self._new_buf(wsz) if wsz else None
-                    self._side_op(lib.pasn_first_conv_wgrad, (x.buf, dy.buf, wsb), B(x.buf), B(dy.buf), dW, dref, _lib.dtype_code(self.in_dtype), code, B(wsb))
-                return
-            if kind == "dw":
-                if w_live:
-                    wsb = self._new_buf(int(lib.pasn_dwconv3d_wgrad_workspace_floats(dref)) * 4)
-                    self._side_op(lib.pasn_dwconv3d_wgrad, (x.buf, dy.buf, wsb), B(x.buf), B(dy.buf), B(wsb), dW, dref, code)
-                if not x_live:
-                    return
+    def _bwd_se(self, u: "_Unit", g: Act, ws: int, coef: int, dg, db, chunks: int) -> Optional[int]:
+        """Reduce + gate backward of a squeeze-excite unit.  Analytic (no residual): ONE pass over (d, y) -- mode 4 leaves d' = d act'(.) and
+        per-clip (sum d', sum d' yhat, sum yhat); the gate's gradient, the norm's coefficients and dgamma / dbeta follow from those per clip
+        (d'' = d' gate + add is affine in d'), and the apply pass forms d'' on the fly: returns the ``add`` buffer.  Otherwise (a residual,
+        or PASN_NO_SE_ANALYTIC): mode 1, the gate's backward, then a second pass over the tensor (mode 2); returns None."""
+        se, y, lib, B, Pm, code, red = u.se, u.y, self.lib, self.B, self.Pm, self.code, self.lib.pasn_unit_bwd_reduce_g
+        N, S, C, Cp = u.dims
+        analytic = u.residual is None and not _lib.tuning_get("PASN_NO_SE_ANALYTIC")
+        cse = se.fc1.out_channels
+        addb = self._new_buf(N * Cp * 4)
+        pn = self._new_buf(int(lib.pasn_se_bwd_workspace_floats(N, C, cse)) * 4)
+        ws3 = self._new_buf(N * chunks * 3 * Cp * 4) if analytic else None
+        fcs = (Pm(se.fc1.weight), Pm(se.fc1.bias), Pm(se.fc2.weight), Pm(se.fc2.bias))
+        o = [self.Gof(t, nullable=False) for t in (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias)]
+        if analytic:
+            self._use(g.buf, y.buf, u.stat_buf, u.gate_buf, ws3)
+            self._op(red, 4, B(g.buf), B(y.buf), u.stat, 0, B(u.gate_buf), 0, B(ws3), 0, 0, 0, N, S, C, Cp, u.actc, code, self.groups)
+            self._use(ws3, u.pool_buf, u.stat_buf, u.gate_buf, addb, pn, coef)
+            self._op(lib.pasn_se_gate_bwd_stat_g, B(ws3), B(u.pool_buf), u.stat, B(u.gate_buf), *fcs, B(addb), B(pn), *o, B(coef), dg, db,
+                     N, S, C, Cp, cse, self.groups)
+            return addb
+        self._use(g.buf, y.buf, u.stat_buf, u.gate_buf, ws)
+        self._op(red, 1, B(g.buf), B(y.buf), u.stat, 0, B(u.gate_buf), 0, B(ws), 0, 0, 0, N, S, C, Cp, u.actc, code, self.groups)
+        self._use(ws, u.pool_buf, addb, pn)
+        self._op(lib.pasn_se_gate_bwd, B(ws), B(u.pool_buf), *fcs, B(addb), B(pn), *o, N, S, C, Cp, cse)
+        self._use(g.buf, y.buf, u.stat_buf, u.gate_buf, addb, ws, coef)
+        self._op(red, 2, B(g.buf), B(y.buf), u.stat, 0, B(u.gate_buf), B(addb), B(ws), B(coef), dg, db, N, S, C, Cp, u.actc, code, self.groups)
+        return None
+
+    def _bwd_first(self, u: "_Unit", dy: Act) -> None:
+        if u.w_live:  # (the clip itself takes no gradient)
+            wsz = int(self.lib.pasn_first_conv_wgrad_workspace_bytes(u.dref, self.code))
+            wsb = self._new_buf(wsz) if wsz else None
+            self._side_op(self.lib.pasn_first_conv_wgrad, (u.x.buf, dy.buf, wsb), self.B(u.x.buf), self.B(dy.buf), self.Gof(u.conv.weight), u.dref,
+                          _lib.dtype_code(self.in_dtype), self.code, self.B(wsb))
+
+    def _bwd_dw(self, u: "_Unit", dy: Act) -> None:
+        x, lib, B, code = u.x, self.lib, self.B, self.code
+        if u.w_live:
+            wsb = self._new_buf(int(lib.pasn_dwconv3d_wgrad_workspace_floats(u.dref)) * 4)
+            self._side_op(lib.pasn_dwconv3d_wgrad, (x.buf, dy.buf, wsb), B(x.buf), B(dy.buf), B(wsb), self.Gof(u.conv.weight), u.dref, code)
+        if not u.x_live:
+            return
+        dx = self.like(x)
+        if u.s == (1, 1, 1) and all(kk % 2 == 1 and pp == kk // 2 for kk, pp in zip(u.k, u.p)):
+            self._bwd_dw_same(u, dy, dx)
+        else:
+            self._use(dy.buf, dx.buf)
+            self._op(lib.pasn_dwconv3d_dgrad, B(dy.buf), u.dw_w.data_ptr(), B(dx.buf), u.dref, code)
+        self.add_grad(x, dx)
+
+    def _bwd_dw_same(self, u: "_Unit", dy: Act, dx: Act) -> None:
+        """Stride-1 "same" depthwise conv: its input gradient is the forward stencil with the taps reversed (the T-marching forward
+        kernel, not the generic gather)."""
+        x, lib, B, code = u.x, self.lib, self.B, self.code
+        wflip = self._dw_taps(u.conv, u.y.Cp, flip=True)
+        one, zero = self.const(u.y.Cp, 1.0), self.const(u.y.Cp, 0.0)
+        dflip = self._desc(dy, dx, u.k, u.s, u.p, "none")
+        self.keep += [wflip]
+        hook = self.red_hook.get(x.buf)
+        rrows = int(lib.pasn_dwconv3d_dgrad_reduce_rows(ctypes.byref(dflip), code)) if hook is not None else 0
+        if rrows > 0 and self.readers.get(x.buf, 0) == 1 and self.grads.get(x.buf) is None:
+            # dx is the WHOLE gradient of the producer unit's output: its backward sums ride in this launch
+            wsr, hcoef = self._new_buf(x.N * rrows * 2 * x.Cp * 4), self._new_buf(2 * x.Cp * 4)
+            self._use(dy.buf, dx.buf, hook["y_buf"], hook["stat_buf"], wsr, hcoef)
+            self._op(lib.pasn_dwconv3d_dgrad_reduce, B(dy.buf), wflip.data_ptr(), one.data_ptr(), zero.data_ptr(), B(dx.buf),
+                     B(hook["y_buf"]), hook["stat"], hook["actc"], B(wsr), B(hcoef), hook["dg"](), hook["db"](),
+                     ctypes.byref(dflip), code)
+            hook["coef"] = hcoef
+        else:
+            self._use(dy.buf, dx.buf)
+            self._op(lib.pasn_dwconv3d_fwd, B(dy.buf), wflip.data_ptr(), one.data_ptr(), zero.data_ptr(), B(dx.buf), 0,
+                     ctypes.byref(dflip), code)
+
+    def _bwd_dense_wgrad(self, u: "_Unit", dy: Act) -> None:
+        if u.w_live:
+            wsz = int(self.lib.pasn_conv3d_wgrad_workspace_bytes(u.dref, self.code))  # windowed stride-1 convs, bf16: partial-buffer path
+            wsb = self._new_buf(wsz) if wsz else None
+            self._side_op(self.lib.pasn_conv3d_wgrad_ws, (u.x.buf, dy.buf, wsb), self.B(u.x.buf), self.B(dy.buf), self.Gof(u.conv.weight), u.dref,
+                          self.code, self.B(wsb))
+
+    def _bwd_dense_dgrad(self, u: "_Unit", dy: Act) -> None:
+        """Input gradient of the dense conv: the forward kernels again, on a re-packed weight."""
+        x, y, conv, k, s, p, B = u.x, u.y, u.conv, u.k, u.s, u.p, self.B
+        cout, cin = conv.out_channels, conv.in_channels
+        one = (1, 1, 1)
+        have = self.grads.get(x.buf)
+        if k == one and p == (0, 0, 0):
+            # 1x1x1: the same pointwise kernel with the transposed weight; strided ones on the compact grid, then scattered
+            wt = lambda: conv.weight.detach().reshape(cout, cin).t()
+            if s == one:
                 dx = self.like(x)
-                same = s == (1, 1, 1) and all(kk % 2 == 1 and pp == kk // 2 for kk, pp in zip(k, p))
-                if same:
-                    # stride-1 "same" depthwise conv: its input gradient is the forward stencil with the taps reversed
-                    # (the T-marching forward kernel, not the generic gather)
-                    wflip = torch.zeros(taps, Cp, dtype=torch.float32, device=self.device)
-                    if self.native_pack and conv.weight.is_contiguous():
-                        self.pack_jobs.append((conv.weight, wflip, 3, C, 1, taps, taps, Cp, 0, 0, 0))
-                    else:
-                        self.refresh.append(lambda: wflip[:, :C].copy_(conv.weight.detach().reshape(C, taps).flip(1).t()))
-                    one_, zero_ = self.const(Cp, 1.0), self.const(Cp, 0.0)
-                    dflip = self._desc(dy, dx, k, s, p, "none")
-                    self.keep += [wflip]
-                    hook = self.red_hook.get(x.buf)
-                    rrows = int(lib.pasn_dwconv3d_dgrad_reduce_rows(ctypes.byref(dflip), code)) if hook is not None else 0
-                    if rrows > 0 and self.readers.get(x.buf, 0) == 1 and self.grads.get(x.buf) is None:
-                        # dx is the WHOLE gradient of the producer unit's output: its backward sums ride in this launch
-                        wsr, hcoef = self._new_buf(x.N * rrows * 2 * x.Cp * 4), self._new_buf(2 * x.Cp * 4)
-                        self._use(dy.buf, dx.buf, hook["y_buf"], hook["stat_buf"], wsr, hcoef)
-                        self._op(lib.pasn_dwconv3d_dgrad_reduce, B(dy.buf), wflip.data_ptr(), one_.data_ptr(), zero_.data_ptr(), B(dx.buf),
-                                 B(hook["y_buf"]), hook["stat"], hook["actc"], B(wsr), B(hcoef), hook["dg"](), hook["db"](),
-                                 ctypes.byref(dflip), code)
-                        hook["coef"] = hcoef
-                    else:
-                        self._use(dy.buf, dx.buf)
-                        self._op(lib.pasn_dwconv3d_fwd, B(dy.buf), wflip.data_ptr(), one_.data_ptr(), zero_.data_ptr(), B(dx.buf), 0,
-                                 ctypes.byref(dflip), code)
-                else:
-                    self._use(dy.buf, dx.buf)
-                    self._op(lib.pasn_dwconv3d_dgrad, B(dy.buf), dw_w.data_ptr(), B(dx.buf), dref, code)
-                self.add_grad(x, dx)
-                return
-            if w_live:
-                wsz = int(lib.pasn_conv3d_wgrad_workspace_bytes(dref, code))  # windowed stride-1 convs, bf16: partial-buffer path
-                wsb = self._new_buf(wsz) if wsz else None
-                self._side_op(lib.pasn_conv3d_wgrad_ws, (x.buf, dy.buf, wsb), B(x.buf), B(dy.buf), dW, dref, code, B(wsb))
-            if not x_live:
-                return
-            # ---- input gradient of the dense conv
-            one = (1, 1, 1)
-            have = self.grads.get(x.buf)
-            if taps == 1 and p == (0, 0, 0):
-                # 1x1x1: the same pointwise kernel with the transposed weight; strided ones on the compact grid, then scattered
-                wt = lambda: conv.weight.detach().reshape(cout, cin).t()
-                if s == one:
-                    dx = self.like(x)
-                    self._dense(dy, dx, one, one, (0, 0, 0), cin, cout, wt, residual=have, pack=(conv.weight, 1))
-                    self.grads[x.buf] = dx
-                else:
-                    compact = Act(y.N, y.T, y.H, y.W, cin, x.Cp, self._new_buf(y.N * y.positions * x.Cp * self.es))
-                    self._dense(dy, compact, one, one, (0, 0, 0), cin, cout, wt, pack=(conv.weight, 1))
-                    dst = have if have is not None else self.like(x)
-                    self._use(compact.buf, dst.buf)
-                    self._op(lib.pasn_scatter_strided, B(compact.buf), B(dst.buf), dref, int(have is not None), code)
-                    self.grads[x.buf] = dst
-                return
-            # windowed conv: correlate the (zero-inserted, for strides > 1) output gradient with the reversed, transposed weight,
-            # padding k-1-p -- the forward implicit-GEMM kernel again.  Extent Z = Ti + 2p - k + 1 covers output_padding.
-            wtf = lambda: (conv.weight.detach() if conv.weight.dim() == 5 else conv.weight.detach().unsqueeze(2)).transpose(0, 1).flip(2, 3, 4)
-            padb = tuple(kk - 1 - pp for kk, pp in zip(k, p))
-            Z = (x.T + 2 * p[0] - k[0] + 1, x.H + 2 * p[1] - k[1] + 1, x.W + 2 * p[2] - k[2] + 1)
-            src = dy
-            if s != one:
-                zi = Act(y.N, Z[0], Z[1], Z[2], cout, y.Cp, self._new_buf(y.N * Z[0] * Z[1] * Z[2] * y.Cp * self.es))
-                zd = ConvDesc(N=y.N, Ti=Z[0], Hi=Z[1], Wi=Z[2], Cin=cout, Cin_p=y.Cp, To=y.T, Ho=y.H, Wo=y.W, Cout=cout, Cout_p=y.Cp,
-                              kt=1, kh=1, kw=1, st=s[0], sh=s[1], sw=s[2])
-                self.keep.append(zd)
-                self._use(dy.buf, zi.buf)
-                self._op(lib.pasn_scatter_strided, B(dy.buf), B(zi.buf), ctypes.byref(zd), 0, code)
-                src = zi
+                self._dense(dy, dx, one, one, (0, 0, 0), cin, cout, wt, residual=have, pack=(conv.weight, 1))
+                self.grads[x.buf] = dx
             else:
-                assert (y.T, y.H, y.W) == Z
-            dx = self.like(x)
-            self._dense(src, dx, k, one, padb, cin, cout, wtf, residual=have, pack=(conv.weight, 1))
-            self.grads[x.buf] = dx
-
-        self.tape.append(backward)
-        return out
+                compact = Act(y.N, y.T, y.H, y.W, cin, x.Cp, self._new_buf(y.N * y.positions * x.Cp * self.es))
+                self._dense(dy, compact, one, one, (0, 0, 0), cin, cout, wt, pack=(conv.weight, 1))
+                dst = have if have is not None else self.like(x)
+                self._use(compact.buf, dst.buf)
+                self._op(self.lib.pasn_scatter_strided, B(compact.buf), B(dst.buf), u.dref, int(have is not None), self.code)
+                self.grads[x.buf] = dst
+            return
+        # windowed conv: correlate the (zero-inserted, for strides > 1) output gradient with the reversed, transposed weight,
+        # padding k-1-p -- the forward implicit-GEMM kernel again.  Extent Z = Ti + 2p - k + 1 covers output_padding.
+        wtf = lambda: (conv.weight.detach() if conv.weight.dim() == 5 else conv.weight.detach().unsqueeze(2)).transpose(0, 1).flip(2, 3, 4)
+        padb = tuple(kk - 1 - pp for kk, pp in zip(k, p))
+        Z = (x.T + 2 * p[0] - k[0] + 1, x.H + 2 * p[1] - k[1] + 1, x.W + 2 * p[2] - k[2] + 1)
+        src = dy
+        if s != one:
+            src = Act(y.N, Z[0], Z[1], Z[2], cout, y.Cp, self._new_buf(y.N * Z[0] * Z[1] * Z[2] * y.Cp * self.es))
+            zd = ConvDesc(N=y.N, Ti=Z[0], Hi=Z[1], Wi=Z[2], Cin=cout, Cin_p=y.Cp, To=y.T, Ho=y.H, Wo=y.W, Cout=cout, Cout_p=y.Cp,
+                          kt=1, kh=1, kw=1, st=s[0], sh=s[1], sw=s[2])
+            self.keep.append(zd)
+            self._use(dy.buf, src.buf)
+            self._op(self.lib.pasn_scatter_strided, B(dy.buf), B(src.buf), ctypes.byref(zd), 0, self.code)
+        else:
+            assert (y.T, y.H, y.W) == Z
+        dx = self.like(x)
+        self._dense(src, dx, k, one, padb, cin, cout, wtf, residual=have, pack=(conv.weight, 1))
+        self.grads[x.buf] = dx
 
     # ---- max pooling (ResNet-18 stem) ----------------------------------------------------------------------------------
     def maxpool_unit(self, x: Act, k, s, p) -> Act:
         y = self._out_act(x, x.C, k, s, p)
         d = self._desc(x, y, k, s, p, "none")
         dref, code, lib, B = ctypes.byref(d), self.code, self.lib, self.B
-        self.readers[x.buf] = self.readers.get(x.buf, 0) + 1
+        self._reads(x)
         self._use(x.buf, y.buf)
         self._op(lib.pasn_maxpool3d_fwd, B(x.buf), B(y.buf), dref, code)
         self.live[y.buf] = self.live.get(x.buf, False)
@@ -534,15 +607,13 @@ class TrainBuilder(PlanBuilder):
         D = model.prototype_shape[1]
         pv, fw = model.prototype_vectors, model.last_layer.weight
         for t in (pv, fw):
-            _need_fp32_param(t, "a head parameter")
+            _need_fp32_param(t, "a head parameter", self.device)
         d = XProtoDesc(N=r.N, S=r.positions, Cb=0, Cbp=0, D=D, Dp=(z.Cp if z is not None else round_up(D, 8)), Hd=D // 2,
                        Hp=round_up(D // 2, 8), P=P, Pp=r.Cp, K=K, mode=0 if z is not None else 1)
         self.keep.append(d)
         dref, code, lib, B, Pm = ctypes.byref(d), self.code, self.lib, self.B, self.Pm
         zb = z.buf if z is not None else None
-        for rb_ in (zb, r.buf):
-            if rb_ is not None:
-                self.readers[rb_] = self.readers.get(rb_, 0) + 1
+        self._reads(z, r)
         e = ext
         wsz = int(lib.pasn_xproto_tail_workspace_bytes(dref))  # split-S pooling on the matrix cores (the inference head's kernels)
         wsb = self._new_buf(wsz) if wsz else None
@@ -572,7 +643,7 @@ class TrainBuilder(PlanBuilder):
         P, K, D = model.num_prototypes, model.num_classes, model.prototype_shape[1]
         pv, fw = model.prototype_vectors, model.last_layer.weight
         for t in (pv, fw):
-            _need_fp32_param(t, "a head parameter")
+            _need_fp32_param(t, "a head parameter", self.device)
         act = model.prototype_activation_function
         if act not in ("log", "linear"):
             raise NotImplementedError("only the 'log' and 'linear' prototype activations run on the HIP path")
@@ -580,7 +651,7 @@ class TrainBuilder(PlanBuilder):
         N, S = z.N, z.positions
         code, lib, B, Pm, e = self.code, self.lib, self.B, self.Pm, ext
         amin = self._new_buf(N * P * 4)
-        self.readers[z.buf] = self.readers.get(z.buf, 0) + 1
+        self._reads(z)
         self._use(z.buf, amin)
         self._op(lib.pasn_l2_head_fwd, B(z.buf), Pm(pv), Pm(fw), 0, B(e["min_d"]), B(amin), B(e["logits"]), N, S, D, z.Cp, P, K, code, actc, eps)
 
@@ -602,27 +673,12 @@ class TrainBuilder(PlanBuilder):
             emit()
         while self._forks:
             self._join()
-        live: List[Tuple[int, int, int]] = []
-        total = 0
-        for b in self.bufs:
-            if b.external:
-                continue
-            live = [a for a in live if a[2] >= b.first]
-            live.sort()
-            off = 0
-            for (o, sz, _) in live:
-                if off + b.nbytes <= o:
-                    break
-                off = max(off, o + sz)
-            b.offset = off
-            live.append((off, b.nbytes, b.last))
-            total = max(total, off + b.nbytes)
-        return TrainPlan(self, x_in, ext, total)
+        return TrainPlan(self, x_in, ext, self._place())
 
 
 def build_pack_tables(jobs: List[tuple], device) -> tuple:
-    """Device tables of ``pasn_pack_weights`` for jobs (parameter, destination, mode, cout, cin, taps, rows, kc, frag, kstep, ch):
-    (job structs as bytes, job of each block, chunk of each block, number of blocks)."""
+    """Device tables of ``pasn_pack_weights`` for ``jobs`` (``PackJob``s, or plain tuples in its field order): (job structs as bytes, job
+    of each block, chunk of each block, number of blocks)."""
     import numpy as np
 
     chunk = int(_lib.lib().pasn_pack_chunk())
@@ -631,11 +687,11 @@ def build_pack_tables(jobs: List[tuple], device) -> tuple:
          ("kc", "i4"), ("frag", "i4"), ("bf16", "i4"), ("kstep", "i4"), ("ch", "i4")], align=True))
     assert jt.dtype.itemsize == 64  # struct pasn_pack_job
     bj, bc = [], []
-    for i, (param, dst, mode, cout, cin, taps, rows, kc, frag, kstep, ch) in enumerate(jobs):
-        assert param.dtype == torch.float32 and param.is_contiguous() and dst.is_contiguous()
-        jt[i] = (param.data_ptr(), dst.data_ptr(), dst.numel(), mode, cout, cin, taps, rows, kc, frag, int(dst.dtype == torch.bfloat16),
-                 kstep, ch)
-        nb = (dst.numel() + chunk - 1) // chunk
+    for i, j in enumerate(PackJob(*job) for job in jobs):
+        assert j.param.dtype == torch.float32 and j.param.is_contiguous() and j.dst.is_contiguous()
+        jt[i] = (j.param.data_ptr(), j.dst.data_ptr(), j.dst.numel(), j.mode, j.cout, j.cin, j.taps, j.rows, j.kc, j.frag,
+                 int(j.dst.dtype == torch.bfloat16), j.kstep, j.ch)
+        nb = (j.dst.numel() + chunk - 1) // chunk
         bj += [i] * nb
         bc += list(range(nb))
     return (torch.from_numpy(jt.view(np.uint8).copy()).to(device), torch.tensor(bj, dtype=torch.int32, device=device),
@@ -662,7 +718,7 @@ class TrainPlan:
         rebuilt when a parameter's storage has moved (``.to()``, ``.data = ...``); in-place optimizer updates keep it."""
         if not self.pack_jobs:
             return
-        key = tuple(j[0].data_ptr() for j in self.pack_jobs)
+        key = tuple(j.param.data_ptr() for j in self.pack_jobs)
         if key != self._pack_key:
             self._pack_tables = build_pack_tables(self.pack_jobs, self.device)
             self._pack_key = key

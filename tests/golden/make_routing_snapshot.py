@@ -68,6 +68,7 @@ class _LibProxy:
             self.calls.append((name, args))
             return 0
 
+        call.__name__ = name  # what the real entry point answers (the training tape names its ops by it)
         return call
 
 
