@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import oracle
+import train_kernel_cases as tk
 from conftest import assert_close
 from protoasnet_amd import _lib, synth
 from protoasnet_amd._lib import ConvDesc, XProtoDesc
@@ -52,172 +53,214 @@ def _desc(x, y, k, s, p):
 
 
 # ------------------------------------------------------------------------------------------------- kernels
-@pytest.mark.parametrize("c,shape,offset", [(54, (3, 4, 9, 7), 0.0), (24, (2, 3, 16, 16), 300.0), (432, (2, 2, 3, 3), -5.0)])
-def test_bn_unit_forward_backward(c, shape, offset):
-    """stats -> affine+act forward; mode-0 reduce + apply backward; vs autograd of relu(batch_norm(y) + residual)."""
-    lib = _lib.lib()
-    n, t, h, w = shape
-    g = torch.Generator().manual_seed(c)
-    y = (torch.randn(n, c, t, h, w, generator=g) * 2 + offset).requires_grad_()
-    res = torch.randn(n, c, t, h, w, generator=g).requires_grad_()
-    gamma = (torch.rand(c, generator=g) + 0.5).requires_grad_()
-    beta = torch.randn(c, generator=g).requires_grad_()
-    rm, rv = torch.zeros(c), torch.ones(c)
-    out = F.relu(F.batch_norm(y, rm, rv, gamma, beta, True, 0.1, 1e-5) + res)
-    da = torch.randn(out.shape, generator=g)
-    out.backward(da)
-    cp, S = (c + 7) // 8 * 8, t * h * w
-    yd, rd, dd = _cl(y.detach()), _cl(res.detach()), _cl(da)
+# The cases (inputs, fp64 references) come from tests/train_kernel_cases.py; tests/test_cpu_train_kernel_cases.py checks them without a GPU.
+# Bounds: fp32 as ever (1e-5 ... 2e-4 of a tensor's scale).  bf16: the activations are rounded BEFORE the reference is taken, so sums the
+# kernels take in fp32 keep the fp32 bound, and an elementwise output behind k stores in bf16 gets k * 2^-8 of its scale on top
+# (tk.tol_stores; round-to-nearest is within 2^-9, the factor 2 is the margin).
+FP32, BF = torch.float32, torch.bfloat16
+
+
+def _variants(cases, ids):
+    """cases x {fp32, bf16} x PASN_TRAIN_ROWS_CONTIG {unset, 1}; the fp32 run with the switch unset carries the bare id of its case."""
+    return [pytest.param(case, dtype, contig, id=cid + ("" if dtype == FP32 and not contig else f"-{dname}-{lname}"))
+            for case, cid in zip(cases, ids) for dtype, dname in ((FP32, "fp32"), (BF, "bf16")) for contig, lname in ((False, "default"), (True, "rows-contig"))]
+
+
+UNIT_IDS = ["54-shape0-0.0", "24-shape1-300.0", "432-shape2--5.0", "432-2x3x7x7", "54-3x3x21x19", "24-2x3x31x31"]
+GROUP_IDS = ["54-shape0-2", "24-shape1-3", "216-shape2-2", "54-4x3x21x19-2"]
+SE_IDS = ["54-8-2x5x6", "432-32-3x7x7", "54-8-3x21x19"]
+
+
+def _rows_switch(monkeypatch, contig):
+    if contig:
+        monkeypatch.setenv("PASN_TRAIN_ROWS_CONTIG", "1")
+    else:
+        monkeypatch.delenv("PASN_TRAIN_ROWS_CONTIG", raising=False)
+
+
+def _chunks(lib, n, S, cp, contig, multi):
+    """The library's chunk count under the switch setting of this run (== the CPU replica); a multi-chunk case has a ragged last chunk."""
     chunks = lib.pasn_train_chunks(n, S, cp)
+    assert chunks == tk.row_geom(n, S, cp, contig)["chunks"]
+    if multi:
+        assert chunks >= 2 and S % chunks != 0, (chunks, S)
+    return chunks
+
+
+def _nan_like(t):
+    return torch.full_like(t, float("nan"))  # an output buffer: every element must have been written
+
+
+def _pad_zero(t, c, name):
+    if t.shape[-1] > c:
+        assert float(t[..., c:].float().abs().max()) == 0.0, f"{name}: padded channels must stay zero"
+
+
+@pytest.mark.parametrize("case,dtype,contig", _variants(tk.UNIT_CASES, UNIT_IDS))
+def test_bn_unit_forward_backward(case, dtype, contig, monkeypatch):
+    """stats -> affine+act forward; mode-0 reduce + apply backward; vs the fp64 gradient of relu(batch_norm(y) + residual).  The last three
+    shapes cut every clip into two chunks with a ragged end (S = 147 / 1197 / 2883: rows past a chunk read as zeros, their stores are dropped),
+    each in fp32 and bf16 and under both thread layouts of a block (PASN_TRAIN_ROWS_CONTIG)."""
+    _rows_switch(monkeypatch, contig)
+    lib = _lib.lib()
+    c, shape, offset = case
+    k = tk.unit_case(c, shape, offset, dtype)
+    n, cp, S, code = k["n"], k["cp"], k["S"], _lib.dtype_code(dtype)
+    yd, rd, dd = _cl(k["y"], dtype=dtype), _cl(k["res"], dtype=dtype), _cl(k["da"], dtype=dtype)
+    chunks = _chunks(lib, n, S, cp, contig, case in tk.UNIT_MULTI_CHUNK)
     ws = torch.zeros(n * chunks * 2 * cp, device=DEV)
     stat, coef = torch.zeros(4 * cp, device=DEV), torch.zeros(2 * cp, device=DEV)
-    gm, bt = gamma.detach().to(DEV), beta.detach().to(DEV)
+    gm, bt = k["gamma"].to(DEV), k["beta"].to(DEV)
     rmd, rvd = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
     _lib.check(lib.pasn_bn_stats_fwd(yd.data_ptr(), ws.data_ptr(), gm.data_ptr(), bt.data_ptr(), rmd.data_ptr(), rvd.data_ptr(), 0.1, 1e-5,
-                                     stat.data_ptr(), 0, n, S, c, cp, F32, _st()))
-    a = torch.empty_like(yd)
-    _lib.check(lib.pasn_affine_act_fwd(yd.data_ptr(), stat.data_ptr(), rd.data_ptr(), 0, a.data_ptr(), n, S, c, cp, 1, F32, _st()))
-    _rel(_ncl(a, c), out, 1e-4, "unit output")
-    _rel(rmd, rm, 1e-5, "running_mean")
-    _rel(rvd, rv, 1e-4, "running_var")
+                                     stat.data_ptr(), 0, n, S, c, cp, code, _st()))
+    a = _nan_like(yd)
+    _lib.check(lib.pasn_affine_act_fwd(yd.data_ptr(), stat.data_ptr(), rd.data_ptr(), 0, a.data_ptr(), n, S, c, cp, 1, code, _st()))
+    _rel(_ncl(a, c), k["out"], tk.tol_stores(1e-4, 1, dtype), "unit output")
+    _pad_zero(a, c, "unit output")
+    _rel(rmd, k["running_mean"], 1e-5, "running_mean")
+    _rel(rvd, k["running_var"], 1e-4, "running_var")
+    _rel(stat.view(4, cp)[0, :c], k["mean"][0], 1e-5, "batch mean")
+    _rel(stat.view(4, cp)[1, :c], k["invstd"][0], 1e-4, "batch invstd")
     dg, db = torch.zeros(c, device=DEV), torch.zeros(c, device=DEV)
     _lib.check(lib.pasn_unit_bwd_reduce(0, dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), rd.data_ptr(), 0, 0, ws.data_ptr(), coef.data_ptr(),
-                                        dg.data_ptr(), db.data_ptr(), n, S, c, cp, 1, F32, _st()))
-    _rel(_ncl(dd, c), res.grad, 1e-5, "residual gradient")
-    dy = torch.empty_like(yd)
-    _lib.check(lib.pasn_bn_bwd_apply(dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dy.data_ptr(), n, S, c, cp, 0, F32, _st()))
-    _rel(dg, gamma.grad, 1e-4, "dgamma")
-    _rel(db, beta.grad, 1e-4, "dbeta")
-    _rel(_ncl(dy, c), y.grad, 2e-4, "dy")
-    assert float(dy[..., c:].abs().max() if cp > c else 0.0) == 0.0, "padded channels must stay zero"
+                                        dg.data_ptr(), db.data_ptr(), n, S, c, cp, 1, code, _st()))
+    _rel(_ncl(dd, c), k["dres"], tk.tol_stores(1e-5, 1, dtype), "residual gradient")
+    _pad_zero(dd, c, "residual gradient")
+    dy = _nan_like(yd)
+    _lib.check(lib.pasn_bn_bwd_apply(dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dy.data_ptr(), n, S, c, cp, 0, code, _st()))
+    _rel(dg, k["dgamma"], 1e-4, "dgamma")
+    _rel(db, k["dbeta"], 1e-4, "dbeta")
+    _rel(coef.view(2, cp)[:, :c], k["coef"][0], 1e-4, "coef")
+    _rel(_ncl(dy, c), k["dy"], tk.tol_stores(2e-4, 2, dtype), "dy")  # behind the stored d' and its own store
+    _pad_zero(dy, c, "dy")
     # mode 3 (sums only, d untouched) + apply differentiating on the fly == mode 0 + plain apply, for a unit without residual.
     # (Not for the large-mean case: u = y*sc + sh carries ~ulp(mean) of absolute error there, enough to flip one ReLU mask
     # against torch's (y - mean) * invstd form, and one flipped element shifts its whole channel's dy by d/R.)
     if offset != 0.0:
         return
-    y2 = y.detach().clone().requires_grad_()
-    out2 = F.relu(F.batch_norm(y2, None, None, gamma.detach(), beta.detach(), True, 0.1, 1e-5))
-    out2.backward(da)
-    d2 = _cl(da)
+    d2 = _cl(k["da"], dtype=dtype)
     keep = d2.clone()
     _lib.check(lib.pasn_unit_bwd_reduce(3, d2.data_ptr(), yd.data_ptr(), stat.data_ptr(), 0, 0, 0, ws.data_ptr(), coef.data_ptr(), dg.data_ptr(),
-                                        db.data_ptr(), n, S, c, cp, 1, F32, _st()))
+                                        db.data_ptr(), n, S, c, cp, 1, code, _st()))
     assert torch.equal(d2, keep), "mode 3 must not write d"
-    _lib.check(lib.pasn_bn_bwd_apply(d2.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dy.data_ptr(), n, S, c, cp, 1, F32, _st()))
-    _rel(_ncl(dy, c), y2.grad, 2e-4, "dy (lazy differentiation)")
+    _rel(dg, k["dgamma_plain"], 1e-4, "dgamma (no residual)")
+    _rel(db, k["dbeta_plain"], 1e-4, "dbeta (no residual)")
+    dy = _nan_like(yd)
+    _lib.check(lib.pasn_bn_bwd_apply(d2.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dy.data_ptr(), n, S, c, cp, 1, code, _st()))
+    _rel(_ncl(dy, c), k["dy_plain"], tk.tol_stores(2e-4, 1, dtype), "dy (lazy differentiation)")
+    _pad_zero(dy, c, "dy (lazy differentiation)")
 
 
-@pytest.mark.parametrize("c,shape,groups", [(54, (4, 3, 9, 7), 2), (24, (6, 2, 8, 8), 3), (216, (2, 2, 5, 4), 2)])
-def test_bn_unit_statistics_groups(c, shape, groups):
+@pytest.mark.parametrize("case,dtype,contig", _variants(tk.GROUP_CASES, GROUP_IDS))
+def test_bn_unit_statistics_groups(case, dtype, contig, monkeypatch):
     """The `_g` entry points: `groups` runs of N / groups clips, each normalised with its own batch statistics (stat [groups][4][Cp],
-    coef [groups][2][Cp]), the running estimates updated group by group, dgamma / dbeta summed over the groups -- against autograd of `groups`
-    separate relu(batch_norm(.) + residual) calls on the sub-batches sharing gamma / beta / running buffers (what the reference's two trunk
-    passes do to a norm layer)."""
+    coef [groups][2][Cp]), the running estimates updated group by group, dgamma / dbeta summed over the groups -- against the fp64 gradient of
+    `groups` separate relu(batch_norm(.) + residual) calls on the sub-batches sharing gamma / beta / running buffers (what the reference's two
+    trunk passes do to a norm layer).  The last shape: two chunks per clip, ragged."""
+    _rows_switch(monkeypatch, contig)
     lib = _lib.lib()
-    n, t, h, w = shape
-    gd = n // groups
-    g = torch.Generator().manual_seed(c + groups)
-    y = torch.randn(n, c, t, h, w, generator=g) * 2
-    y = (y + torch.arange(n).view(n, 1, 1, 1, 1) // gd * 1.5).requires_grad_()  # groups with different means
-    res = torch.randn(n, c, t, h, w, generator=g).requires_grad_()
-    gamma = (torch.rand(c, generator=g) + 0.5).requires_grad_()
-    beta = torch.randn(c, generator=g).requires_grad_()
-    rm, rv = torch.zeros(c), torch.ones(c)
-    out = torch.cat([F.relu(F.batch_norm(y[k * gd:(k + 1) * gd], rm, rv, gamma, beta, True, 0.1, 1e-5) + res[k * gd:(k + 1) * gd]) for k in range(groups)])
-    da = torch.randn(out.shape, generator=g)
-    out.backward(da)
-    cp, S = (c + 7) // 8 * 8, t * h * w
-    yd, rd, dd = _cl(y.detach()), _cl(res.detach()), _cl(da)
-    chunks = lib.pasn_train_chunks(n, S, cp)
+    c, shape, groups = case
+    k = tk.unit_case(c, shape, 0.0, dtype, groups)
+    n, cp, S, code = k["n"], k["cp"], k["S"], _lib.dtype_code(dtype)
+    yd, rd, dd = _cl(k["y"], dtype=dtype), _cl(k["res"], dtype=dtype), _cl(k["da"], dtype=dtype)
+    chunks = _chunks(lib, n, S, cp, contig, case in tk.GROUP_MULTI_CHUNK)
     ws = torch.zeros(n * chunks * 2 * cp, device=DEV)
     stat, coef = torch.zeros(groups * 4 * cp, device=DEV), torch.zeros(groups * 2 * cp, device=DEV)
-    gm, bt = gamma.detach().to(DEV), beta.detach().to(DEV)
+    gm, bt = k["gamma"].to(DEV), k["beta"].to(DEV)
     rmd, rvd = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
     _lib.check(lib.pasn_bn_stats_fwd_g(yd.data_ptr(), ws.data_ptr(), gm.data_ptr(), bt.data_ptr(), rmd.data_ptr(), rvd.data_ptr(), 0.1, 1e-5,
-                                       stat.data_ptr(), 0, n, S, c, cp, F32, groups, _st()))
-    a = torch.empty_like(yd)
-    _lib.check(lib.pasn_affine_act_fwd_g(yd.data_ptr(), stat.data_ptr(), rd.data_ptr(), 0, a.data_ptr(), n, S, c, cp, 1, F32, groups, _st()))
-    _rel(_ncl(a, c), out, 1e-4, "unit output")
-    _rel(rmd, rm, 1e-5, "running_mean after the groups' updates, in order")
-    _rel(rvd, rv, 1e-4, "running_var")
+                                       stat.data_ptr(), 0, n, S, c, cp, code, groups, _st()))
+    a = _nan_like(yd)
+    _lib.check(lib.pasn_affine_act_fwd_g(yd.data_ptr(), stat.data_ptr(), rd.data_ptr(), 0, a.data_ptr(), n, S, c, cp, 1, code, groups, _st()))
+    _rel(_ncl(a, c), k["out"], tk.tol_stores(1e-4, 1, dtype), "unit output")
+    _pad_zero(a, c, "unit output")
+    _rel(rmd, k["running_mean"], 1e-5, "running_mean after the groups' updates, in order")
+    _rel(rvd, k["running_var"], 1e-4, "running_var")
     means = stat.view(groups, 4, cp)[:, 0, :c].cpu()
-    for k in range(groups):
-        _rel(means[k], y.detach()[k * gd:(k + 1) * gd].mean(dim=(0, 2, 3, 4)), 1e-5, f"mean of group {k}")
+    for g in range(groups):
+        _rel(means[g], k["mean"][g], 1e-5, f"mean of group {g}")
     dg, db = torch.zeros(c, device=DEV), torch.zeros(c, device=DEV)
     _lib.check(lib.pasn_unit_bwd_reduce_g(0, dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), rd.data_ptr(), 0, 0, ws.data_ptr(), coef.data_ptr(),
-                                          dg.data_ptr(), db.data_ptr(), n, S, c, cp, 1, F32, groups, _st()))
-    _rel(_ncl(dd, c), res.grad, 1e-5, "residual gradient")
-    dy = torch.empty_like(yd)
-    _lib.check(lib.pasn_bn_bwd_apply_g(dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dy.data_ptr(), n, S, c, cp, 0, F32, groups, _st()))
-    _rel(dg, gamma.grad, 1e-4, "dgamma (summed over the groups)")
-    _rel(db, beta.grad, 1e-4, "dbeta")
-    _rel(_ncl(dy, c), y.grad, 2e-4, "dy")
+                                          dg.data_ptr(), db.data_ptr(), n, S, c, cp, 1, code, groups, _st()))
+    _rel(_ncl(dd, c), k["dres"], tk.tol_stores(1e-5, 1, dtype), "residual gradient")
+    dy = _nan_like(yd)
+    _lib.check(lib.pasn_bn_bwd_apply_g(dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dy.data_ptr(), n, S, c, cp, 0, code, groups, _st()))
+    _rel(dg, k["dgamma"], 1e-4, "dgamma (summed over the groups)")
+    _rel(db, k["dbeta"], 1e-4, "dbeta")
+    _rel(coef.view(groups, 2, cp)[:, :, :c], k["coef"], 1e-4, "coef of each group")
+    _rel(_ncl(dy, c), k["dy"], tk.tol_stores(2e-4, 2, dtype), "dy")
+    _pad_zero(dy, c, "dy")
     # an indivisible batch is refused
-    assert lib.pasn_affine_act_fwd_g(yd.data_ptr(), stat.data_ptr(), 0, 0, a.data_ptr(), n, S, c, cp, 1, F32, n + 1, _st()) != 0
+    assert lib.pasn_affine_act_fwd_g(yd.data_ptr(), stat.data_ptr(), 0, 0, a.data_ptr(), n, S, c, cp, 1, code, n + 1, _st()) != 0
 
 
-def test_se_unit_forward_backward():
-    """BN -> squeeze-excite gate -> Swish (X3D block with SE): forward and the three backward passes vs autograd."""
+@pytest.mark.parametrize("spec,dtype,contig", _variants(tk.SE_CASES, SE_IDS))
+def test_se_unit_forward_backward(spec, dtype, contig, monkeypatch):
+    """BN -> squeeze-excite gate -> Swish (X3D block with SE): forward and the three backward passes vs the fp64 gradient -- in fp32 and bf16,
+    under both thread layouts, and at two shapes that cut a clip into two ragged chunks: bn_finalize's per-clip pool over several chunks,
+    se_mlp_bwd folding the mode-4 partials into chunk 0, se_bn_coef, the `ok ? .. : 0` guards of modes 2 and 4."""
+    _rows_switch(monkeypatch, contig)
     lib = _lib.lib()
-    n, c, cse, t, h, w = 3, 54, 8, 2, 5, 6
-    g = torch.Generator().manual_seed(7)
-    y = torch.randn(n, c, t, h, w, generator=g).requires_grad_()
-    gamma, beta = (torch.rand(c, generator=g) + 0.5).requires_grad_(), torch.randn(c, generator=g).requires_grad_()
-    w1, b1 = (torch.randn(cse, c, generator=g) * 0.3).requires_grad_(), torch.randn(cse, generator=g).requires_grad_()
-    w2, b2 = (torch.randn(c, cse, generator=g) * 0.3).requires_grad_(), torch.randn(c, generator=g).requires_grad_()
-    u = F.batch_norm(y, None, None, gamma, beta, True, 0.1, 1e-5)
-    pool = u.mean(dim=(2, 3, 4))
-    gate = torch.sigmoid(F.linear(F.relu(F.linear(pool, w1, b1)), w2, b2))
-    v = u * gate[:, :, None, None, None]
-    out = v * torch.sigmoid(v)
-    da = torch.randn(out.shape, generator=g)
-    out.backward(da)
-    cp, S = 56, t * h * w
-    yd, dd = _cl(y.detach()), _cl(da)
-    chunks = lib.pasn_train_chunks(n, S, cp)
+    k = tk.se_case(*spec, dtype=dtype)
+    n, c, cp, cse, S, code = k["n"], k["c"], k["cp"], k["cse"], k["S"], _lib.dtype_code(dtype)
+    yd, dd = _cl(k["y"], dtype=dtype), _cl(k["da"], dtype=dtype)
+    chunks = _chunks(lib, n, S, cp, contig, spec in tk.SE_MULTI_CHUNK)
     ws = torch.zeros(n * chunks * 2 * cp, device=DEV)
-    stat, coef, pool_u, gated = (torch.zeros(k, device=DEV) for k in (4 * cp, 2 * cp, n * cp, n * cp))
-    P = [t_.detach().to(DEV).contiguous() for t_ in (gamma, beta, w1, b1, w2, b2)]
+    stat, coef, pool_u, gated = (torch.zeros(m, device=DEV) for m in (4 * cp, 2 * cp, n * cp, n * cp))
+    P = [t_.to(DEV).contiguous() for t_ in k["params"]]
+    names = ("dgamma", "dbeta", "dw1", "db1", "dw2", "db2")
+    labels = ("dgamma", "dbeta", "dfc1.w", "dfc1.b", "dfc2.w", "dfc2.b")
     _lib.check(lib.pasn_bn_stats_fwd(yd.data_ptr(), ws.data_ptr(), P[0].data_ptr(), P[1].data_ptr(), 0, 0, 0.1, 1e-5, stat.data_ptr(),
-                                     pool_u.data_ptr(), n, S, c, cp, F32, _st()))
+                                     pool_u.data_ptr(), n, S, c, cp, code, _st()))
+    _rel(pool_u.view(n, cp)[:, :c], k["pool"], 1e-5, "per-clip pool of the normalised rows (summed over the chunks)")
     _lib.check(lib.pasn_se_gate_fwd(pool_u.data_ptr(), 1, 1, P[2].data_ptr(), P[3].data_ptr(), P[4].data_ptr(), P[5].data_ptr(),
                                     gated.data_ptr(), n, c, cp, cse, _st()))
-    _rel(gated.view(n, cp)[:, :c], gate, 1e-5, "gate")
-    a = torch.empty_like(yd)
-    _lib.check(lib.pasn_affine_act_fwd(yd.data_ptr(), stat.data_ptr(), 0, gated.data_ptr(), a.data_ptr(), n, S, c, cp, 3, F32, _st()))
-    _rel(_ncl(a, c), out, 1e-4, "unit output")
+    _rel(gated.view(n, cp)[:, :c], k["gate"], 1e-5, "gate")
+    a = _nan_like(yd)
+    _lib.check(lib.pasn_affine_act_fwd(yd.data_ptr(), stat.data_ptr(), 0, gated.data_ptr(), a.data_ptr(), n, S, c, cp, 3, code, _st()))
+    _rel(_ncl(a, c), k["out"], tk.tol_stores(1e-4, 1, dtype), "unit output")
+    _pad_zero(a, c, "unit output")
     add = torch.zeros(n * cp, device=DEV)
     pn = torch.zeros(lib.pasn_se_bwd_workspace_floats(n, c, cse), device=DEV)
     G = [torch.zeros_like(t_) for t_ in P]
     _lib.check(lib.pasn_unit_bwd_reduce(1, dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), 0, gated.data_ptr(), 0, ws.data_ptr(), 0, 0, 0, n, S, c,
-                                        cp, 3, F32, _st()))
+                                        cp, 3, code, _st()))
+    _rel(_ncl(dd, c), k["dv"], tk.tol_stores(2e-4, 1, dtype), "d' = d swish'(.)")
     _lib.check(lib.pasn_se_gate_bwd(ws.data_ptr(), pool_u.data_ptr(), P[2].data_ptr(), P[3].data_ptr(), P[4].data_ptr(), P[5].data_ptr(),
                                     add.data_ptr(), pn.data_ptr(), G[2].data_ptr(), G[3].data_ptr(), G[4].data_ptr(), G[5].data_ptr(), n, S, c, cp,
                                     cse, _st()))
+    _rel(add.view(n, cp)[:, :c], k["add"], 2e-4, "add = dL/dpool / S")
     _lib.check(lib.pasn_unit_bwd_reduce(2, dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), 0, gated.data_ptr(), add.data_ptr(), ws.data_ptr(),
-                                        coef.data_ptr(), G[0].data_ptr(), G[1].data_ptr(), n, S, c, cp, 3, F32, _st()))
-    _lib.check(lib.pasn_bn_bwd_apply(dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dd.data_ptr(), n, S, c, cp, 0, F32, _st()))
-    for got, ref, name in zip(G, (gamma, beta, w1, b1, w2, b2), ("dgamma", "dbeta", "dfc1.w", "dfc1.b", "dfc2.w", "dfc2.b")):
-        _rel(got, ref.grad, 2e-4, name)
-    _rel(_ncl(dd, c), y.grad, 2e-4, "dy")
+                                        coef.data_ptr(), G[0].data_ptr(), G[1].data_ptr(), n, S, c, cp, 3, code, _st()))
+    _lib.check(lib.pasn_bn_bwd_apply(dd.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef.data_ptr(), dd.data_ptr(), n, S, c, cp, 0, code, _st()))
+    ref = k["two_pass"]  # (mode 2 sums the d' that mode 1 STORED: the reference rounds at the same store)
+    for got, name, label in zip(G, names, labels):
+        _rel(got, ref[name], 2e-4, label)
+    _rel(_ncl(dd, c), ref["dy"], tk.tol_stores(2e-4, 3, dtype), "dy")  # behind the stored d', the stored d'' and its own store
     # the analytic form: ONE pass over (d, y) (mode 4), everything else from per-clip sums, d'' formed inside the apply pass
-    d4 = _cl(da)
+    d4 = _cl(k["da"], dtype=dtype)
     ws3 = torch.zeros(n * chunks * 3 * cp, device=DEV)
     add4, coef4 = torch.zeros(n * cp, device=DEV), torch.zeros(2 * cp, device=DEV)
     G4 = [torch.zeros_like(t_) for t_ in P]
     _lib.check(lib.pasn_unit_bwd_reduce(4, d4.data_ptr(), yd.data_ptr(), stat.data_ptr(), 0, gated.data_ptr(), 0, ws3.data_ptr(), 0, 0, 0, n, S, c,
-                                        cp, 3, F32, _st()))
+                                        cp, 3, code, _st()))
     _lib.check(lib.pasn_se_gate_bwd_stat(ws3.data_ptr(), pool_u.data_ptr(), stat.data_ptr(), gated.data_ptr(), P[2].data_ptr(), P[3].data_ptr(),
                                          P[4].data_ptr(), P[5].data_ptr(), add4.data_ptr(), pn.data_ptr(), G4[2].data_ptr(), G4[3].data_ptr(),
                                          G4[4].data_ptr(), G4[5].data_ptr(), coef4.data_ptr(), G4[0].data_ptr(), G4[1].data_ptr(), n, S, c, cp, cse,
                                          _st()))
     _lib.check(lib.pasn_bn_bwd_apply_se(d4.data_ptr(), yd.data_ptr(), stat.data_ptr(), coef4.data_ptr(), gated.data_ptr(), add4.data_ptr(),
-                                        d4.data_ptr(), n, S, c, cp, F32, _st()))
-    for got, ref, name in zip(G4, (gamma, beta, w1, b1, w2, b2), ("dgamma", "dbeta", "dfc1.w", "dfc1.b", "dfc2.w", "dfc2.b")):
-        _rel(got, ref.grad, 2e-4, name + " (analytic)")
-    _rel(coef4.view(2, cp)[:, :c], coef.view(2, cp)[:, :c], 1e-4, "coef, analytic vs two passes")
-    _rel(_ncl(d4, c), y.grad, 2e-4, "dy (analytic)")
-    assert float(d4[..., c:].abs().max()) == 0.0, "padded channels must stay zero"
+                                        d4.data_ptr(), n, S, c, cp, code, _st()))
+    ref4 = k["analytic"]  # (mode 4 sums the unrounded d': autograd's sums)
+    for got, name, label in zip(G4, names, labels):
+        _rel(got, ref4[name], 2e-4, label + " (analytic)")
+    if dtype == FP32:  # (in bf16 the two-pass sums see the rounded d', the analytic ones do not: each is held to its own reference)
+        _rel(coef4.view(2, cp)[:, :c], coef.view(2, cp)[:, :c], 1e-4, "coef, analytic vs two passes")
+    _rel(coef.view(2, cp)[:, :c], ref["coef"], 1e-4, "coef (two passes)")
+    _rel(coef4.view(2, cp)[:, :c], ref4["coef"], 1e-4, "coef (analytic)")
+    _rel(_ncl(d4, c), ref4["dy"], tk.tol_stores(2e-4, 2, dtype), "dy (analytic)")  # behind the stored d' and its own store
+    _pad_zero(d4, c, "dy (analytic)")
+    _pad_zero(dd, c, "dy")
 
 
 WGRAD_CASES = [
@@ -746,69 +789,163 @@ def test_pack_weights_one_launch(dtype):
 
 
 def test_scatter_strided_and_add():
+    """fp32 and bf16; the stride-(1,2,2) shortcut scatter, and the zero-insertion use of _bwd_dense_dgrad: a temporal stride into an extent
+    larger than (To - 1) * st + 1, whose trailing planes / rows / columns must be zeroed; Cp = 16 and 24.  Overwrite is exact; accumulate is
+    exact in fp32 and within one rounding (2^-8 of the element) in bf16."""
     lib = _lib.lib()
-    src = torch.randn(2, 2, 4, 5, 16, device=DEV)
-    dst = torch.randn(2, 2, 8, 9, 16, device=DEV)
-    d = ConvDesc(N=2, Ti=2, Hi=8, Wi=9, Cin=16, Cin_p=16, To=2, Ho=4, Wo=5, Cout=16, Cout_p=16, kt=1, kh=1, kw=1, st=1, sh=2, sw=2)
-    ref = dst.clone()
-    ref[:, :, ::2, ::2][:, :, :4, :5] += src
-    _lib.check(lib.pasn_scatter_strided(src.data_ptr(), dst.data_ptr(), ctypes.byref(d), 1, F32, _st()))
-    assert torch.equal(dst, ref)
-    _lib.check(lib.pasn_scatter_strided(src.data_ptr(), dst.data_ptr(), ctypes.byref(d), 0, F32, _st()))
-    ref.zero_()
-    ref[:, :, ::2, ::2][:, :, :4, :5] = src
-    assert torch.equal(dst, ref)
-    a, b = torch.randn(4096, device=DEV), torch.randn(4096, device=DEV)
-    want = a + b
-    _lib.check(lib.pasn_add_inplace(a.data_ptr(), b.data_ptr(), 4096, F32, _st()))
-    assert torch.equal(a, want)
+    g = torch.Generator().manual_seed(5)
+    for dtype in (FP32, BF):
+        code = _lib.dtype_code(dtype)
+        for cp, (to, ho, wo), (ti, hi, wi), (st, sh, sw) in [(16, (2, 4, 5), (2, 8, 9), (1, 2, 2)), (24, (2, 3, 4), (5, 7, 8), (2, 2, 2)),
+                                                             (16, (3, 2, 2), (6, 4, 5), (2, 2, 2))]:
+            src = torch.randn(2, to, ho, wo, cp, generator=g).to(dtype).to(DEV)
+            dst = torch.randn(2, ti, hi, wi, cp, generator=g).to(dtype).to(DEV)
+            d = ConvDesc(N=2, Ti=ti, Hi=hi, Wi=wi, Cin=cp, Cin_p=cp, To=to, Ho=ho, Wo=wo, Cout=cp, Cout_p=cp, kt=1, kh=1, kw=1, st=st, sh=sh, sw=sw)
+            ref = dst.double()
+            ref[:, ::st, ::sh, ::sw][:, :to, :ho, :wo] += src.double()
+            _lib.check(lib.pasn_scatter_strided(src.data_ptr(), dst.data_ptr(), ctypes.byref(d), 1, code, _st()))
+            if dtype == FP32:
+                assert torch.equal(dst, ref.float())
+            else:
+                assert_close(dst, ref, 0.0, tk.BF16_STORE, "accumulate: the sum, rounded once to bf16")
+            _lib.check(lib.pasn_scatter_strided(src.data_ptr(), dst.data_ptr(), ctypes.byref(d), 0, code, _st()))
+            ref = torch.zeros_like(dst)
+            ref[:, ::st, ::sh, ::sw][:, :to, :ho, :wo] = src
+            assert torch.equal(dst, ref), "overwrite: the source values on the strided lattice, zeros everywhere else"
+        a, b = torch.randn(4096 + 8, generator=g).to(dtype).to(DEV), torch.randn(4096 + 8, generator=g).to(dtype).to(DEV)
+        want = a.double() + b.double()
+        _lib.check(lib.pasn_add_inplace(a.data_ptr(), b.data_ptr(), 4096 + 8, code, _st()))
+        if dtype == FP32:
+            assert torch.equal(a, want.float())
+        else:
+            assert_close(a, want, 0.0, tk.BF16_STORE, "a + b, rounded once to bf16")
 
 
-@pytest.mark.parametrize("occ_only", [False, True])
-def test_xproto_tail_forward_backward(occ_only):
+@pytest.mark.parametrize("i,occ_only,dtype", [pytest.param(0, False, FP32, id="False"), pytest.param(0, True, FP32, id="True")]
+                         + [pytest.param(i, o, dt, id=f"case{i}-{'occ_only' if o else 'full'}-{'bf16' if dt == BF else 'fp32'}")
+                            for i in (0, 1) for o in (False, True) for dt in (FP32, BF) if (i, dt) != (0, FP32)])
+def test_xproto_tail_forward_backward(i, occ_only, dtype):
+    """Head B's tail against fp64 autograd.  Case 1: D = 12 in rows of Dp = 16, P = 30 in rows of Pp = 32, S = 300 (19 row tiles of the pool
+    kernels, the last one ragged).  bf16: z, r, dz, dr in bf16 -- the forward outputs and the parameter gradients are fp32 sums over the
+    rounded operands (fp32 bounds), dz and dr are stored once."""
     lib = _lib.lib()
-    n, s, dch, p, k = 3, 37, 64, 30, 3
-    g = torch.Generator().manual_seed(11)
-    z = torch.randn(n, dch, s, generator=g).requires_grad_()
-    r = torch.randn(n, p, s, generator=g).requires_grad_()
-    protos = torch.rand(p, dch, generator=g).requires_grad_()
-    fcw = torch.randn(k, p, generator=g).requires_grad_()
-    occ = r.abs()
-    feat = torch.einsum("nps,nds->npd", occ, z)
-    sim = (F.cosine_similarity(feat, protos.unsqueeze(0), dim=2, eps=1e-8) + 1) / 2
-    logits = F.linear(sim, fcw)
-    dl, dsm, doc = torch.randn(n, k, generator=g), torch.randn(n, p, generator=g), torch.randn(n, p, s, generator=g)
-    if occ_only:
-        (occ * doc).sum().backward()
-    else:
-        ((logits * dl).sum() + (sim * dsm).sum() + (occ * doc).sum()).backward()
-    pp = (p + 7) // 8 * 8
-    zd = torch.zeros(n, s, dch, device=DEV)
-    zd.copy_(z.detach().permute(0, 2, 1))
-    rd = torch.zeros(n, s, pp, device=DEV)
-    rd[..., :p] = r.detach().permute(0, 2, 1)
-    d = XProtoDesc(N=n, S=s, Cb=0, Cbp=0, D=dch, Dp=dch, Hd=dch // 2, Hp=dch // 2, P=p, Pp=pp, K=k, mode=int(occ_only))
-    pv, fw = protos.detach().to(DEV), fcw.detach().to(DEV)
-    o_occ, o_feat, o_sim, o_log = (torch.zeros(sh, device=DEV) for sh in ((n, p, s), (n, p, dch), (n, p), (n, k)))
+    k = tk.xproto_case(i, occ_only, dtype)
+    n, s, dch, dp, p, pp, kk, code = k["n"], k["S"], k["D"], k["Dp"], k["P"], k["Pp"], k["K"], _lib.dtype_code(dtype)
+    zd = torch.zeros(n, s, dp, dtype=dtype, device=DEV)
+    zd[..., :dch] = k["z"].permute(0, 2, 1)
+    rd = torch.zeros(n, s, pp, dtype=dtype, device=DEV)
+    rd[..., :p] = k["r"].permute(0, 2, 1)
+    d = XProtoDesc(N=n, S=s, Cb=0, Cbp=0, D=dch, Dp=dp, Hd=dch // 2, Hp=(dch // 2 + 7) // 8 * 8, P=p, Pp=pp, K=kk, mode=int(occ_only))
+    pv, fw = k["protos"].to(DEV), k["fcw"].to(DEV)
+    o_occ, o_feat, o_sim, o_log = (torch.zeros(sh, device=DEV) for sh in ((n, p, s), (n, p, dch), (n, p), (n, kk)))
     zp = 0 if occ_only else zd.data_ptr()
     _lib.check(lib.pasn_xproto_tail_fwd(zp, rd.data_ptr(), pv.data_ptr(), fw.data_ptr(), o_occ.data_ptr(), o_feat.data_ptr(), o_sim.data_ptr(),
-                                        o_log.data_ptr(), ctypes.byref(d), F32, _st()))
-    _rel(o_occ, occ, 1e-6, "occ")
+                                        o_log.data_ptr(), ctypes.byref(d), code, _st()))
+    _rel(o_occ, k["occ"], 1e-6, "occ")
     if not occ_only:
-        _rel(o_feat, feat, 1e-5, "feat")
-        _rel(o_sim, sim, 1e-5, "sim")
-        _rel(o_log, logits, 1e-5, "logits")
-    dz, dr = torch.zeros_like(zd), torch.zeros_like(rd)
+        _rel(o_feat, k["feat"], 1e-5, "feat")
+        _rel(o_sim, k["sim"], 1e-5, "sim")
+        _rel(o_log, k["logits"], 1e-5, "logits")
+    dz, dr = _nan_like(zd), _nan_like(rd)
     dfeat, dpv, dfw = torch.zeros(n, p, dch, device=DEV), torch.zeros_like(pv), torch.zeros_like(fw)
-    gl, gs, go = dl.to(DEV), dsm.to(DEV), doc.to(DEV).contiguous()
+    gl, gs, go = k["dl"].to(DEV), k["dsm"].to(DEV), k["doc"].to(DEV).contiguous()
     _lib.check(lib.pasn_xproto_tail_bwd(zp, rd.data_ptr(), pv.data_ptr(), fw.data_ptr(), o_feat.data_ptr(), o_sim.data_ptr(), gl.data_ptr(),
                                         0 if occ_only else gs.data_ptr(), go.data_ptr(), dfeat.data_ptr(), dz.data_ptr(), dr.data_ptr(),
-                                        dpv.data_ptr(), dfw.data_ptr(), ctypes.byref(d), F32, _st()))
-    _rel(dr[..., :p].permute(0, 2, 1), r.grad, 1e-4, "dr")
+                                        dpv.data_ptr(), dfw.data_ptr(), ctypes.byref(d), code, _st()))
+    _rel(dr[..., :p].permute(0, 2, 1), k["dr"], tk.tol_stores(1e-4, 1, dtype), "dr")
+    _pad_zero(dr, p, "dr")
     if not occ_only:
-        _rel(dz.permute(0, 2, 1), z.grad, 1e-4, "dz")
-        _rel(dpv, protos.grad, 1e-4, "dprototypes")
-        _rel(dfw, fcw.grad, 1e-4, "dlast_layer")
+        _rel(dz[..., :dch].permute(0, 2, 1), k["dz"], tk.tol_stores(1e-4, 1, dtype), "dz")
+        _pad_zero(dz, dch, "dz")
+        _rel(dpv, k["dprotos"], 1e-4, "dprototypes")
+        _rel(dfw, k["dfcw"], 1e-4, "dlast_layer")
+
+
+@pytest.mark.parametrize("dtype", [FP32, BF], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("i", range(len(tk.MAXPOOL_CASES)))
+def test_maxpool_forward_backward_with_tied_windows(i, dtype):
+    """pasn_maxpool3d_fwd / _bwd called directly against F.max_pool3d and its autograd (fp64, on the rounded input), on post-ReLU inputs: a
+    quarter to two thirds of the windows have a tied (zero) maximum, one channel group is all zeros, a bf16 plane holds four values.  The
+    window's gradient goes to its FIRST maximum in scan order -- in a padded border window that is the first in-range slot.  dx is a sum of
+    at most 8 routed dy values per element (fp32: 1e-5; bf16: one store on top), and every window routes to exactly one element, so
+    the sums of dx and dy agree per (clip, channel)."""
+    lib = _lib.lib()
+    k = tk.maxpool_case(i, dtype)
+    n, c, cp, code = k["n"], k["c"], k["cp"], _lib.dtype_code(dtype)
+    d = _desc(k["x"], k["y"], k["k"], k["s"], k["p"])
+    xd, dyd = _cl(k["x"], dtype=dtype), _cl(k["dy"], dtype=dtype)
+    yd = _nan_like(dyd)
+    _lib.check(lib.pasn_maxpool3d_fwd(xd.data_ptr(), yd.data_ptr(), ctypes.byref(d), code, _st()))
+    assert_close(_ncl(yd, c), k["y"], 0, 0, "maxpool is exact")
+    _pad_zero(yd, c, "y")
+    dx = _nan_like(xd)
+    _lib.check(lib.pasn_maxpool3d_bwd(xd.data_ptr(), dyd.data_ptr(), dx.data_ptr(), ctypes.byref(d), code, _st()))
+    tol = tk.tol_stores(1e-5, 1, dtype)
+    _rel(_ncl(dx, c), k["dx"], tol, "dx")
+    _pad_zero(dx, c, "dx")
+    _rel(_ncl(dx, c).double().sum(dim=(2, 3, 4)), k["dy"].double().sum(dim=(2, 3, 4)), tol, "sum of dx per (clip, channel) == sum of dy")
+
+
+HEAD_PARAMS = [pytest.param(tag, act, dt, True, id=f"{tag}-{'log' if act == 0 else 'linear'}-{'bf16' if dt == BF else 'fp32'}")
+               for tag in tk.HEAD_CASES for act in (0, 1) for dt in (FP32, BF)]
+HEAD_PARAMS += [pytest.param("r128", act, dt, False, id=f"r128-{'log' if act == 0 else 'linear'}-{'bf16' if dt == BF else 'fp32'}-no_dmin")
+                for act in (0, 1) for dt in (FP32, BF)]
+
+
+@pytest.mark.parametrize("tag,activation,dtype,with_dmin", HEAD_PARAMS)
+def test_l2_head_backward(tag, activation, dtype, with_dmin):
+    """pasn_l2_head_fwd then pasn_l2_head_bwd, called directly, against fp64 autograd of oracle.heads.ppnet_head's expression (l2_convolution ->
+    min over positions -> distance_2_similarity -> linear) with loss weights on both outputs; once with dmin == NULL.  Shapes: D = 512 (two
+    rounds of the 256-thread channel loop), S = 1, D = 12 in rows of Dp = 16 (the pad stays zero), and two constructed cases: five
+    prototypes around ONE latent row of a clip (the ordered accumulation of l2_head_bwd_z_kernel), and a prototype EQUAL to a latent row
+    (the state right after a push): d == 0 exactly, everything finite, dfc_w takes sim(0), the row's contribution 2 g (z - p) is 0.
+    The kernel differentiates the UNCLAMPED distance |z|^2 - 2 z.p + |p|^2: the gradient of the true, non-negative distance -- the relu of
+    the reference only clips rounding noise, and where it clips (d == 0) both gradients are 0 because z == p there.
+
+    Bounds.  min_dist, fp32 and bf16 alike (bf16 products are exact in the fp32 accumulator): three fp32 sums of D terms of size ~D/3 cancel
+    to ~D/6, each off by ~sqrt(D) * 6e-8 of its value -- 6 sqrt(D) * 6e-8 = 8e-6 of the result at D = 512: 1e-4 of the scale.  logits, coef,
+    dprotos, dfc_w: fp32 sums, 1e-4.  dz: 1e-4, plus in bf16 one store per prototype that shares the row (read-modify-write in bf16);
+    rows that are nobody's arg-min are exactly zero."""
+    lib = _lib.lib()
+    k = tk.head_case(tag, dtype, activation, with_dmin)
+    n, S, D, Dp, P, K, code = k["n"], k["S"], k["D"], k["Dp"], k["P"], k["K"], _lib.dtype_code(dtype)
+    zd = torch.zeros(n, S, Dp, dtype=dtype, device=DEV)
+    zd[..., :D] = k["z"]
+    pv, fw, gl = k["protos"].to(DEV), k["fcw"].to(DEV), k["dlogits"].to(DEV)
+    gm = k["dmin"].to(DEV) if with_dmin else None
+    mind, logits = torch.full((n, P), float("nan"), device=DEV), torch.full((n, K), float("nan"), device=DEV)
+    amin = torch.full((n, P), -1, dtype=torch.int32, device=DEV)
+    _lib.check(lib.pasn_l2_head_fwd(zd.data_ptr(), pv.data_ptr(), fw.data_ptr(), 0, mind.data_ptr(), amin.data_ptr(), logits.data_ptr(), n, S, D, Dp,
+                                    P, K, code, activation, 1e-4, _st()))
+    _rel(mind, k["min_dist"], 1e-4, "min_dist")
+    assert torch.equal(amin.cpu().long(), k["argmin"]), "arg-min positions (every gap is above 1e-3 of the minimum)"
+    _rel(logits, k["logits"], 1e-4, "logits")
+    if tag == "exact":
+        assert float(mind[1, 4]) == 0.0, "a prototype equal to a latent row: d == 0 exactly"
+    outs = []
+    for _ in range(2):
+        dz, coef = _nan_like(zd), torch.full((n, P), float("nan"), device=DEV)
+        dpv, dfw = _nan_like(pv), _nan_like(fw)
+        _lib.check(lib.pasn_l2_head_bwd(zd.data_ptr(), pv.data_ptr(), fw.data_ptr(), mind.data_ptr(), amin.data_ptr(), gl.data_ptr(), _lib.ptr(gm),
+                                        dz.data_ptr(), coef.data_ptr(), dpv.data_ptr(), dfw.data_ptr(), n, S, D, Dp, P, K, code, activation, 1e-4,
+                                        _st()))
+        torch.cuda.synchronize()
+        outs.append((dz, coef, dpv, dfw))
+    for a, b in zip(*outs):
+        assert torch.equal(a, b), "fixed accumulation order: two calls are bitwise equal"
+    dz, coef, dpv, dfw = outs[0]
+    assert all(bool(torch.isfinite(t).all()) for t in outs[0])
+    _rel(coef, k["coef"], 1e-4, "coef")
+    _rel(dpv, k["dprotos"], 1e-4, "dprototypes")
+    _rel(dfw, k["dfc_w"], 1e-4, "dlast_layer")
+    _pad_zero(dz, D, "dz")
+    got, ref, scale = dz[..., :D].float().cpu(), k["dz"], float(k["dz"].abs().max()) + 1e-12
+    for share in k["shared"].unique().tolist():
+        rows = k["shared"] == share
+        if share == 0:
+            assert float(got[rows].abs().max()) == 0.0, "a row that is nobody's arg-min carries no gradient"
+        else:
+            assert_close(got[rows], ref[rows], tk.tol_stores(1e-4, share, dtype) * scale, 0.0, f"dz, rows shared by {share} prototype(s) (scale {scale:.3g})")
 
 
 # ------------------------------------------------------------------------------------------------- whole model
