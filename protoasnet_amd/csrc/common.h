@@ -94,7 +94,6 @@ struct WsPair {
     int Cout2, Cout2_p, nks2, act2;
 };
 WsGeom pw_ws_geom(const pasn_conv_desc& d, int dtype, bool has_gate, bool has_res, bool se_prologue = false, const pasn_conv_desc* d2 = nullptr);
-int pw_ws_variant(const pasn_conv_desc& d, int dtype, bool has_gate, bool has_res);  // 7000 + KS * 10 + MT, or 0
 int launch_pw_ws(const void* x, const void* w, const float* scale, const float* bias, const void* res, const float* gate, void* y,
                  const pasn_conv_desc& d, const WsGeom& g, hipStream_t s, const WsSe* se = nullptr, const WsPair* pair = nullptr);
 // pwconv_xpair.hip: project conv of block i chained with the expand conv of block i+1 (bf16); 0 = not covered
@@ -223,6 +222,38 @@ int launch_igemm(const void* x, const void* w, const float* scale, const float* 
 template <typename T>
 int launch_gemm_pw(const void* x, const void* w, const float* scale, const float* bias, const void* res, const float* gate,
                    void* y, const pasn_conv_desc& d, hipStream_t s);
+
+// ---- routes (DESIGN.md "Routes"): which kernel a launch takes and the geometry it needs, decided by ONE function per family; probes,
+// sizing and launches read a route and nothing else.  (The weight-gradient routes are private to wgrad.hip.)
+inline pasn_conv_desc frag_major(pasn_conv_desc d) { return d.w_frag = 1, d; }  // the layer with its weights packed fragment-major
+// `unpacked`: asked before the host has packed the weights (it packs what the answer needs): the fragment-major kernels are open whatever
+// d.w_frag says.  The fields after arm are those of the arm taken.
+struct ConvRoute {
+    enum Arm { TCONV_WS, PW_WS, PW_TINY, PW_PERSIST, PW_XTILE, IGEMM, GEMM_PW, GENERIC } arm;
+    TcGeom tc;
+    WsGeom ws;
+    PwGeom pw;
+    int nt, NT, MT;  // igemm; conv3d_mfma_kernel's tiles per wave
+};
+ConvRoute conv_route(const pasn_conv_desc& d, int dtype, bool has_gate, bool has_res, bool unpacked);
+struct DwGeom {  // the VALU depthwise kernels; WT = 0 means "use the generic kernel" (window / stride outside the specialised set)
+    int WT, CG, R, strips, blocks;
+};
+// wants_pool: the launch also writes squeeze-excite pool partial rows (pool_rows per clip), which the (kt,1,1) kernel cannot
+struct DwRoute {
+    enum Arm { TEMPORAL, TZ, MFMA, MARCH, STRIP } arm;
+    DtGeom tz;
+    DwMfmaGeom mf;
+    DwMarchGeom m;
+    DwGeom g;
+    int pool_rows;
+};
+DwRoute dw_route(const pasn_conv_desc& d, int dtype, bool wants_pool);
+struct PairRoute {  // the chained pair of pointwise convs; the arm's value is pasn_conv3d_pair_variant's answer
+    enum Arm { NONE = 0, XPAIR = 1, WS = 2 } arm;
+    WsGeom ws;
+};
+PairRoute pair_route(const pasn_conv_desc& d1, const pasn_conv_desc& d2, int dtype, bool has_gate);
 
 // head_chain.hip: head B with the intermediate maps resident in LDS (bf16, D = 256)
 bool xproto_chain_supported(const pasn_xproto_desc& d, int dtype);

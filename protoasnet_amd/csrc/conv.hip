@@ -254,11 +254,9 @@ static void conv_variant(const pasn_conv_desc& d, int& NT, int& MT) {
 
 template <typename T>
 static int launch_conv3d(const void* x, const void* w, const float* scale, const float* bias, const void* res,
-                         const float* gate, void* y, const pasn_conv_desc& d, hipStream_t s) {
+                         const float* gate, void* y, const pasn_conv_desc& d, int NT, int MT, hipStream_t s) {
     const long M = (long)d.N * d.To * d.Ho * d.Wo;
     const int tiles = ceil_div(d.Cout_p, 32);
-    int NT, MT;
-    conv_variant(d, NT, MT);
     const dim3 grid(ceil_div(M, 4 * 32 * MT), ceil_div(tiles, NT)), block(256);
     PASN_REQUIRE((long)grid.y * NT * 32 <= d.w_rows, "packed weight has too few rows for the chosen tiling");
 #define PASN_CV(NT_, MT_)                                                                                     \
@@ -521,10 +519,7 @@ static void dw_block_shape(int Cp, int& bx, int& by) {
     by = 256 / bx;
 }
 
-// Strip geometry; WT = 0 means "use the generic kernel" (window / stride outside the specialised set).
-struct DwGeom {
-    int WT, CG, R, strips, blocks;
-};
+// Strip geometry (DwGeom, common.h)
 static DwGeom dw_geom(const pasn_conv_desc& d) {
     DwGeom g = {0, d.Cout_p / 8, 0, 0, 0};
     const bool special = (d.kw == 3 && (d.sw == 1 || d.sw == 2)) || (d.kw == 1 && d.sw == 1);
@@ -548,10 +543,9 @@ static DwGeom dw_geom(const pasn_conv_desc& d) {
 
 template <typename T>
 static int launch_dwconv3d(const void* x, const float* w, const float* scale, const float* bias, void* y, float* pool,
-                           const pasn_conv_desc& d, hipStream_t s) {
+                           const pasn_conv_desc& d, const DwGeom& g, hipStream_t s) {
     PASN_REQUIRE(d.Cout_p / 8 <= 256, "depthwise conv supports at most 2048 channels");
     const int taps = d.kt * d.kh * d.kw;
-    const DwGeom g = dw_geom(d);
     if (g.WT == 0) {
         int bx, by;
         dw_block_shape(d.Cout_p, bx, by);
@@ -733,14 +727,81 @@ static bool conv_desc_ok(const pasn_conv_desc* d) {
 // stage-3 layers: 48->108 29 vs 37 us, 108->48 33 vs 36.5 us).
 static bool prefer_xtile(const pasn_conv_desc& d, int dtype, bool has_gate) {
     if (!pw_xtile_applicable(d, dtype)) return false;
-    if (has_gate || d.in_swish) {  // PASN_XTILE_GATED=1: the X-tile kernel on gated layers too.  Re-measured after its gate reads became whole
-        // pieces (round 2): still behind the persistent kernel on the three gated 108 -> 48 layers (9.00 k vs 9.04 k clips/s end to end)
-        const char* e = tune("PASN_XTILE_GATED");
-        if (!(e && e[0] == '1')) return false;
-    }
+    // PASN_XTILE_GATED=1: the X-tile kernel on gated layers too.  Re-measured after its gate reads became whole pieces (round 2): still
+    // behind the persistent kernel on the three gated 108 -> 48 layers (9.00 k vs 9.04 k clips/s end to end)
+    if ((has_gate || d.in_swish) && !tune_is("PASN_XTILE_GATED", '1')) return false;
     if (d.st != 1 || d.sh != 1 || d.sw != 1) return true;  // strided 1x1x1 (shortcut convs): the only specialised kernel
     return (d.Cout_p + 31) / 32 >= 2;
 }
+
+ConvRoute pasn::conv_route(const pasn_conv_desc& d, int dtype, bool has_gate, bool has_res, bool unpacked) {
+    ConvRoute r{};
+    const bool frag = unpacked || d.w_frag == 1;  // the weight-stationary kernels read fragment-major weights (bf16)
+    const pasn_conv_desc f = frag_major(d);
+    if (frag && (r.tc = tconv_geom(f, dtype, has_gate)).ok) r.arm = ConvRoute::TCONV_WS;              // temporal (3,1,1) conv, T-marching
+    else if (frag && (r.ws = pw_ws_geom(f, dtype, has_gate, has_res)).ok) r.arm = ConvRoute::PW_WS;  // persistent blocks
+    else if (pw_tiny_applicable(d, dtype, has_gate)) r.arm = ConvRoute::PW_TINY;  // fp32, few positions (the image heads): one wave per 32 x 32 output tile
+    else if (!prefer_xtile(d, dtype, has_gate) && (r.pw = pw_geom(d, dtype)).TM) r.arm = ConvRoute::PW_PERSIST;  // 1x1x1 stride-1 convs: the row-streaming kernel
+    else if (pw_xtile_applicable(d, dtype)) r.arm = ConvRoute::PW_XTILE;  // wide pointwise layers: whole-K X tiles in LDS, weights streamed from L2
+    else if (!has_gate && (r.nt = igemm_nt(d, dtype))) r.arm = ConvRoute::IGEMM;  // windowed dense convs, bf16: direct-to-LDS implicit GEMM
+    else if (gemm_pw_applicable(d, dtype)) r.arm = ConvRoute::GEMM_PW;  // large K / N pointwise: LDS-tiled GEMM
+    else r.arm = ConvRoute::GENERIC, conv_variant(d, r.NT, r.MT);
+    return r;
+}
+
+DwRoute pasn::dw_route(const pasn_conv_desc& d, int dtype, bool wants_pool) {
+    DwRoute r{};
+    if (!wants_pool && dw_temporal_applicable(d, dtype)) r.arm = DwRoute::TEMPORAL;  // (kt,1,1): T-marching register ring; writes no pool rows
+    else if ((r.tz = dw_tz_geom(d, dtype)).ok) r.arm = DwRoute::TZ, r.pool_rows = r.tz.nT;          // stride 1, planes 9 .. 14 wide
+    else if ((r.mf = dw_mfma_geom(d, dtype)).ok) r.arm = DwRoute::MFMA, r.pool_rows = r.mf.chunks;  // stride 1, matrix cores
+    else if ((r.m = dw_march_geom(d, dtype)).WT) r.arm = DwRoute::MARCH, r.pool_rows = r.m.bpc;
+    else r.arm = DwRoute::STRIP, r.g = dw_geom(d), r.pool_rows = r.g.blocks;
+    return r;
+}
+
+PairRoute pasn::pair_route(const pasn_conv_desc& d1, const pasn_conv_desc& d2, int dtype, bool has_gate) {
+    PairRoute r{};
+    const pasn_conv_desc f2 = frag_major(d2);
+    if ((r.ws = pw_ws_geom(frag_major(d1), dtype, has_gate, true, false, &f2)).ok) r.arm = PairRoute::WS;  // persistent blocks, both weight sets in registers
+    else if (pw_xpair_ks(d1, d2, dtype, nullptr) != 0) r.arm = PairRoute::XPAIR;  // one block per 64-position tile
+    return r;
+}
+
+// The squeeze-excite gate computed in the weight-stationary kernel's prologue: a single conv (d2 == NULL) or the chained pair; ok = 0: not covered
+static WsGeom ws_se_route(const pasn_conv_desc* d, const pasn_conv_desc* d2, int dtype, int Cse, bool has_res) {
+    if (!conv_desc_ok(d) || (d2 && !conv_desc_ok(d2)) || Cse <= 0 || Cse > 32 || Cse % 4 != 0 || d->Cin > 512) return WsGeom{};
+    if (tune_is("PASN_NO_SE_PROLOGUE", '1')) return WsGeom{};
+    const pasn_conv_desc f2 = frag_major(d2 ? *d2 : *d);
+    return pw_ws_geom(frag_major(*d), dtype, true, d2 || has_res, true, d2 ? &f2 : nullptr);
+}
+static WsSe ws_se(const float* pool, int pool_blocks, int positions, const float* const (&fc)[4], const pasn_conv_desc& d, int Cse) {
+    return {pool, pool_blocks, 1.0f / (float)positions, fc[0], fc[1], fc[2], fc[3], d.Cin, Cse};
+}
+static WsPair ws_pair(const void* w2, const float* scale2, const float* bias2, void* y2, const pasn_conv_desc& d2) {
+    return {(const __bf16*)w2, scale2, bias2, (__bf16*)y2, d2.Cout, d2.Cout_p, d2.w_kc / 16, d2.act};
+}
+// pasn_x3d_expdw_*: de = the 1x1x1 expand conv (its weights are, or will be, fragment-major), d = the depthwise conv on its output
+static XeGeom expdw_geom(const pasn_conv_desc* de, const pasn_conv_desc* d, int dtype) {
+    return conv_desc_ok(de) && conv_desc_ok(d) ? xe_geom(frag_major(*de), *d, dtype) : XeGeom{};
+}
+
+// pasn_dwconv3d_se_fwd always runs the T-marching VALU stencil (m), whatever dw_route takes for the layer's plain launch; max_cse = the
+// widest squeeze the fused gate takes on this layer (0: no fused launch).
+struct DwSe { DwMarchGeom m; int max_cse; };
+static DwSe dw_se_geom(const pasn_conv_desc& d, int dtype) {
+    DwSe r = {dw_march_geom(d, dtype), 0};
+    // (mfma: the matrix-core stencil + the stand-alone gate beat the fused VALU launch, 8669 vs 8623 clips/s)
+    if (r.m.WT == 0 || tune_is("PASN_NO_SE_FUSE", '1') || dw_mfma_geom(d, dtype).ok) return r;
+    // The last block of a clip computes the gate alone, at the END of the launch: atomic + acquire, the partial rows (agent-scope loads:
+    // memory-side round trips), two FCs -- an exposed tail of 5-30 us that grows with the channel count (432 channels: +29 us per launch,
+    // 216: +4..9 us) against ~9 us for the stand-alone gate launch it replaces.  Measured end to end (32 x 16 x 224 x 224, one box): fused
+    // everywhere 8084 clips/s, fused up to 256 channels 8218, up to 128 channels 8250, nowhere 8193.  A version of the tail with every
+    // load batched up front (fc rows in registers) moved 432 channels to +16 us and the narrow stages to +6..9 us: no better.
+    const int max_c = tune("PASN_SE_FUSE_MAXC") ? atoi(tune("PASN_SE_FUSE_MAXC")) : 128;
+    if (d.Cout_p <= max_c) r.max_cse = r.m.R * d.Cout_p - d.Cout_p - 8;  // the gate's LDS scratch (Cout_p + Cse + 8 floats) is the pool scratch
+    return r;
+}
+static bool dw_desc_ok(const pasn_conv_desc* d) { return d && d->Cout_p > 0 && d->Cout_p % 8 == 0; }
 
 static int first_conv_dispatch(const void* x, const float* w, const float* scale, const float* bias, void* y, const pasn_conv_desc* d,
                                int in_dtype, int out_dtype, float in_a, float in_b, void* stream) {
@@ -794,66 +855,43 @@ extern "C" int pasn_conv3d_fwd(const void* x, const void* w, const float* scale,
     PASN_REQUIRE(d->w_rows % 128 == 0 && d->w_rows >= d->Cout_p, "w_rows must be a multiple of 128 covering Cout_p");
     hipStream_t s = (hipStream_t)stream;
     PASN_REQUIRE(dtype == PASN_F32 || dtype == PASN_BF16, "unknown dtype");
-    if (const TcGeom tg = tconv_geom(*d, dtype, gate != nullptr); tg.ok)  // temporal (3,1,1) conv, weight-stationary + T-marching (bf16, fragment-major weights)
-        return launch_tconv_ws(x, w, scale, bias, residual, y, *d, tg, s);
-    if (const WsGeom wg = pw_ws_geom(*d, dtype, gate != nullptr, residual != nullptr); wg.ok)  // weight-stationary persistent blocks (bf16, fragment-major weights)
-        return launch_pw_ws(x, w, scale, bias, residual, gate, y, *d, wg, s);
-    if (pw_tiny_applicable(*d, dtype, gate != nullptr))  // fp32, few positions (the image heads): one wave per 32 x 32 output tile
-        return launch_pw_tiny(x, w, scale, bias, residual, y, *d, dtype, s);
-    const bool xt_first = prefer_xtile(*d, dtype, gate != nullptr);
-    const PwGeom pg = xt_first ? PwGeom{0, 0, 0, 0} : pw_geom(*d, dtype);  // 1x1x1 stride-1 convs: the row-streaming kernel
-    PASN_REQUIRE(d->w_frag == 0 || (pw_xtile_applicable(*d, dtype) && !pg.TM),
+    const bool f32 = dtype == PASN_F32;
+    const ConvRoute r = conv_route(*d, dtype, gate != nullptr, residual != nullptr, false);
+    PASN_REQUIRE(d->w_frag == 0 || r.arm == ConvRoute::TCONV_WS || r.arm == ConvRoute::PW_WS || r.arm == ConvRoute::PW_XTILE,
                  "fragment-major weights are only read by the pwconv_xtile kernel (variant >= 2500)");
-    if (pg.TM) {
-        if (dtype == PASN_F32) return launch_pwconv<float>(x, w, scale, bias, residual, gate, y, *d, pg, s);
-        return launch_pwconv<__bf16>(x, w, scale, bias, residual, gate, y, *d, pg, s);
+    switch (r.arm) {
+        case ConvRoute::TCONV_WS: return launch_tconv_ws(x, w, scale, bias, residual, y, *d, r.tc, s);
+        case ConvRoute::PW_WS: return launch_pw_ws(x, w, scale, bias, residual, gate, y, *d, r.ws, s);
+        case ConvRoute::PW_TINY: return launch_pw_tiny(x, w, scale, bias, residual, y, *d, dtype, s);
+        case ConvRoute::PW_PERSIST: return f32 ? launch_pwconv<float>(x, w, scale, bias, residual, gate, y, *d, r.pw, s) : launch_pwconv<__bf16>(x, w, scale, bias, residual, gate, y, *d, r.pw, s);
+        case ConvRoute::PW_XTILE: return f32 ? launch_pw_xtile<float>(x, w, scale, bias, residual, gate, y, *d, s) : launch_pw_xtile<__bf16>(x, w, scale, bias, residual, gate, y, *d, s);
+        case ConvRoute::IGEMM: return launch_igemm(x, w, scale, bias, residual, y, *d, r.nt, s);
+        case ConvRoute::GEMM_PW: return f32 ? launch_gemm_pw<float>(x, w, scale, bias, residual, gate, y, *d, s) : launch_gemm_pw<__bf16>(x, w, scale, bias, residual, gate, y, *d, s);
+        default: return f32 ? launch_conv3d<float>(x, w, scale, bias, residual, gate, y, *d, r.NT, r.MT, s) : launch_conv3d<__bf16>(x, w, scale, bias, residual, gate, y, *d, r.NT, r.MT, s);
     }
-    if (pw_xtile_applicable(*d, dtype)) {  // wide pointwise layers: whole-K X tiles in LDS, weights streamed from L2
-        if (dtype == PASN_F32) return launch_pw_xtile<float>(x, w, scale, bias, residual, gate, y, *d, s);
-        return launch_pw_xtile<__bf16>(x, w, scale, bias, residual, gate, y, *d, s);
+}
+
+// flags: bit 0: an SE gate tensor is passed, bit 1: a residual is passed
+extern "C" int pasn_conv3d_variant(const pasn_conv_desc* d, int dtype, int flags) {
+    if (!conv_desc_ok(d)) return 0;
+    const ConvRoute r = conv_route(*d, dtype, (flags & 1) != 0, (flags & 2) != 0, true);
+    switch (r.arm) {
+        case ConvRoute::TCONV_WS: return 9000 + r.tc.KSF;                      // tconv_ws_kernel<KSF, residual?> (fragment-major weights)
+        case ConvRoute::PW_WS: return 7000 + r.ws.KS * 10 + r.ws.MT;           // pwconv_ws_kernel<KS, MT> (fragment-major weights)
+        case ConvRoute::PW_TINY: return 2002;                                  // pwconv_tiny_f32_kernel
+        case ConvRoute::PW_PERSIST: return 1000 + r.pw.TM * 10 + r.pw.xrow;    // pwconv_persist_kernel<dtype, KS, NT>
+        case ConvRoute::PW_XTILE: return 2500 + 2 * pw_xtile_ks(*d, dtype) + ((d->in_swish != 0) ? 1 : 0);  // pwconv_xtile_kernel<dtype, input transform?>
+        case ConvRoute::IGEMM: return 6000 + r.nt;                             // igemm_glds_kernel<NT>
+        case ConvRoute::GEMM_PW: return 2000 + ((d->kt * d->kh * d->kw == 1 && d->st * d->sh * d->sw == 1) ? 0 : 1);  // gemm_conv_kernel<dtype, pointwise?>
+        default: return r.NT * 10 + r.MT;                                      // conv3d_mfma_kernel<dtype, NT, MT>
     }
-    if (const int nt = (gate == nullptr && d->w_frag == 0) ? igemm_nt(*d, dtype) : 0)  // windowed dense convs, bf16: direct-to-LDS implicit GEMM
-        return launch_igemm(x, w, scale, bias, residual, y, *d, nt, s);
-    if (gemm_pw_applicable(*d, dtype)) {  // large K / N pointwise: LDS-tiled GEMM
-        if (dtype == PASN_F32) return launch_gemm_pw<float>(x, w, scale, bias, residual, gate, y, *d, s);
-        return launch_gemm_pw<__bf16>(x, w, scale, bias, residual, gate, y, *d, s);
-    }
-    if (dtype == PASN_F32) return launch_conv3d<float>(x, w, scale, bias, residual, gate, y, *d, s);
-    return launch_conv3d<__bf16>(x, w, scale, bias, residual, gate, y, *d, s);
 }
 
 // 0 = not covered, 1 = pwconv_xpair_kernel (one block per 64-position tile), 2 = the weight-stationary persistent kernel in pair mode.
 // flags: bit 0 = a gate tensor (or the squeeze-excite operands) will be passed.
 extern "C" int pasn_conv3d_pair_variant(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int flags) {
     if (!conv_desc_ok(d1) || !conv_desc_ok(d2)) return 0;
-    pasn_conv_desc f1 = *d1, f2 = *d2;
-    f1.w_frag = f2.w_frag = 1;
-    if (pw_ws_geom(f1, dtype, (flags & 1) != 0, true, false, &f2).ok) return 2;
-    return pw_xpair_ks(*d1, *d2, dtype, nullptr) != 0 ? 1 : 0;
-}
-
-// The chained pair with the first conv's squeeze-excite gate computed in the launch's prologue (pasn_conv3d_se_fwd + pasn_conv3d_pair_fwd in one).
-extern "C" int pasn_conv3d_pair_se_supported(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int Cse) {
-    if (!conv_desc_ok(d1) || !conv_desc_ok(d2) || Cse <= 0 || Cse > 32 || Cse % 4 != 0 || d1->Cin > 512) return 0;
-    if (const char* e = tune("PASN_NO_SE_PROLOGUE"))
-        if (e[0] == '1') return 0;
-    pasn_conv_desc f1 = *d1, f2 = *d2;
-    f1.w_frag = f2.w_frag = 1;
-    return pw_ws_geom(f1, dtype, true, true, true, &f2).ok;
-}
-
-extern "C" int pasn_conv3d_pair_se_fwd(const void* x, const void* w1, const float* scale1, const float* bias1, const void* residual,
-                                       const float* pool_partial, int pool_blocks, int positions, const float* fc1_w, const float* fc1_b,
-                                       const float* fc2_w, const float* fc2_b, int Cse, void* y1, const pasn_conv_desc* d1, const void* w2,
-                                       const float* scale2, const float* bias2, void* y2, const pasn_conv_desc* d2, int dtype, void* stream) {
-    PASN_REQUIRE(x && w1 && w2 && y1 && y2 && residual && pool_partial && fc1_w && fc1_b && fc2_w && fc2_b, "null pointer");
-    PASN_REQUIRE(conv_desc_ok(d1) && conv_desc_ok(d2) && pool_blocks > 0 && positions > 0, "bad geometry");
-    PASN_REQUIRE(dtype == PASN_BF16 && d1->w_frag == 1 && d2->w_frag == 1, "bf16 with fragment-major weights only");
-    PASN_REQUIRE(pasn_conv3d_pair_se_supported(d1, d2, dtype, Cse), "pair not covered (pasn_conv3d_pair_se_supported returns 0)");
-    const WsGeom wg = pw_ws_geom(*d1, dtype, true, true, true, d2);
-    const WsSe se = {pool_partial, pool_blocks, 1.0f / (float)positions, fc1_w, fc1_b, fc2_w, fc2_b, d1->Cin, Cse};
-    const WsPair p2 = {(const __bf16*)w2, scale2, bias2, (__bf16*)y2, d2->Cout, d2->Cout_p, d2->w_kc / 16, d2->act};
-    return launch_pw_ws(x, w1, scale1, bias1, residual, nullptr, y1, *d1, wg, (hipStream_t)stream, &se, &p2);
+    return pair_route(*d1, *d2, dtype, (flags & 1) != 0).arm;
 }
 
 extern "C" int pasn_conv3d_pair_supported(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype) {
@@ -866,21 +904,35 @@ extern "C" int pasn_conv3d_pair_fwd(const void* x, const void* w1, const float* 
     PASN_REQUIRE(x && w1 && w2 && y1 && y2 && residual, "null pointer");
     PASN_REQUIRE(conv_desc_ok(d1) && conv_desc_ok(d2), "bad geometry");
     PASN_REQUIRE(dtype == PASN_BF16 && d1->w_frag == 1 && d2->w_frag == 1, "bf16 with fragment-major weights only");
-    if (const WsGeom wg = pw_ws_geom(*d1, dtype, gate != nullptr, true, false, d2); wg.ok) {  // persistent blocks, both weight sets in registers
-        const WsPair p2 = {(const __bf16*)w2, scale2, bias2, (__bf16*)y2, d2->Cout, d2->Cout_p, d2->w_kc / 16, d2->act};
-        return launch_pw_ws(x, w1, scale1, bias1, residual, gate, y1, *d1, wg, (hipStream_t)stream, nullptr, &p2);
-    }
-    PASN_REQUIRE(pw_xpair_ks(*d1, *d2, dtype, nullptr) != 0, "pair not covered (pasn_conv3d_pair_supported returns 0)");
-    return launch_pw_xpair(x, w1, scale1, bias1, residual, gate, y1, *d1, w2, scale2, bias2, y2, *d2, (hipStream_t)stream);
+    const PairRoute r = pair_route(*d1, *d2, dtype, gate != nullptr);
+    PASN_REQUIRE(r.arm != PairRoute::NONE, "pair not covered (pasn_conv3d_pair_supported returns 0)");
+    if (r.arm == PairRoute::XPAIR)
+        return launch_pw_xpair(x, w1, scale1, bias1, residual, gate, y1, *d1, w2, scale2, bias2, y2, *d2, (hipStream_t)stream);
+    const WsPair p2 = ws_pair(w2, scale2, bias2, y2, *d2);
+    return launch_pw_ws(x, w1, scale1, bias1, residual, gate, y1, *d1, r.ws, (hipStream_t)stream, nullptr, &p2);
+}
+
+// The chained pair with the first conv's squeeze-excite gate computed in the launch's prologue (pasn_conv3d_se_fwd + pasn_conv3d_pair_fwd in one).
+extern "C" int pasn_conv3d_pair_se_supported(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int Cse) {
+    return d2 && ws_se_route(d1, d2, dtype, Cse, true).ok;
+}
+
+extern "C" int pasn_conv3d_pair_se_fwd(const void* x, const void* w1, const float* scale1, const float* bias1, const void* residual,
+                                       const float* pool_partial, int pool_blocks, int positions, const float* fc1_w, const float* fc1_b,
+                                       const float* fc2_w, const float* fc2_b, int Cse, void* y1, const pasn_conv_desc* d1, const void* w2,
+                                       const float* scale2, const float* bias2, void* y2, const pasn_conv_desc* d2, int dtype, void* stream) {
+    PASN_REQUIRE(x && w1 && w2 && y1 && y2 && residual && pool_partial && fc1_w && fc1_b && fc2_w && fc2_b, "null pointer");
+    PASN_REQUIRE(conv_desc_ok(d1) && conv_desc_ok(d2) && pool_blocks > 0 && positions > 0, "bad geometry");
+    PASN_REQUIRE(dtype == PASN_BF16 && d1->w_frag == 1 && d2->w_frag == 1, "bf16 with fragment-major weights only");
+    const WsGeom wg = ws_se_route(d1, d2, dtype, Cse, true);
+    PASN_REQUIRE(wg.ok, "pair not covered (pasn_conv3d_pair_se_supported returns 0)");
+    const WsSe se = ws_se(pool_partial, pool_blocks, positions, {fc1_w, fc1_b, fc2_w, fc2_b}, *d1, Cse);
+    const WsPair p2 = ws_pair(w2, scale2, bias2, y2, *d2);
+    return launch_pw_ws(x, w1, scale1, bias1, residual, nullptr, y1, *d1, wg, (hipStream_t)stream, &se, &p2);
 }
 
 extern "C" int pasn_conv3d_se_supported(const pasn_conv_desc* d, int dtype, int Cse, int has_residual) {
-    if (!conv_desc_ok(d) || Cse <= 0 || Cse > 32 || Cse % 4 != 0 || d->Cin > 512) return 0;
-    if (const char* e = tune("PASN_NO_SE_PROLOGUE"))
-        if (e[0] == '1') return 0;
-    pasn_conv_desc df = *d;
-    df.w_frag = 1;
-    return pw_ws_geom(df, dtype, true, has_residual != 0, true).ok;
+    return ws_se_route(d, nullptr, dtype, Cse, has_residual != 0).ok;
 }
 
 extern "C" int pasn_conv3d_se_fwd(const void* x, const void* w, const float* scale, const float* bias, const void* residual,
@@ -888,9 +940,9 @@ extern "C" int pasn_conv3d_se_fwd(const void* x, const void* w, const float* sca
                                   const float* fc2_w, const float* fc2_b, int Cse, void* y, const pasn_conv_desc* d, int dtype, void* stream) {
     PASN_REQUIRE(x && w && y && pool_partial && fc1_w && fc1_b && fc2_w && fc2_b, "null pointer");
     PASN_REQUIRE(conv_desc_ok(d) && pool_blocks > 0 && positions > 0, "bad geometry");
-    PASN_REQUIRE(d->w_frag == 1 && pasn_conv3d_se_supported(d, dtype, Cse, residual != nullptr), "layer not covered (pasn_conv3d_se_supported returns 0)");
-    const WsGeom wg = pw_ws_geom(*d, dtype, true, residual != nullptr, true);
-    const WsSe se = {pool_partial, pool_blocks, 1.0f / (float)positions, fc1_w, fc1_b, fc2_w, fc2_b, d->Cin, Cse};
+    const WsGeom wg = ws_se_route(d, nullptr, dtype, Cse, residual != nullptr);
+    PASN_REQUIRE(d->w_frag == 1 && wg.ok, "layer not covered (pasn_conv3d_se_supported returns 0)");
+    const WsSe se = ws_se(pool_partial, pool_blocks, positions, {fc1_w, fc1_b, fc2_w, fc2_b}, *d, Cse);
     return launch_pw_ws(x, w, scale, bias, residual, nullptr, y, *d, wg, (hipStream_t)stream, &se);
 }
 
@@ -910,53 +962,20 @@ extern "C" int pasn_conv3d_short_fwd(const void* x, const void* w, const float* 
     return launch_pwconv<__bf16>(x, w, scale, bias, nullptr, gate, y, *d, pw_geom(*d, dtype), (hipStream_t)stream, &sc);
 }
 
-extern "C" int pasn_conv3d_variant(const pasn_conv_desc* d, int dtype, int flags) {
-    if (!conv_desc_ok(d)) return 0;
-    const int has_gate = flags & 1, has_res = (flags >> 1) & 1;  // bit 0: an SE gate tensor is passed, bit 1: a residual is passed
-    {  // asked before the host has packed the weights: the weight-stationary kernel reads them fragment-major like the X-tile kernel
-        pasn_conv_desc df = *d;
-        df.w_frag = 1;
-        if (const TcGeom tg = tconv_geom(df, dtype, has_gate != 0); tg.ok) return 9000 + tg.KSF;  // tconv_ws_kernel<KSF, residual?> (fragment-major weights)
-        if (const int v = pw_ws_variant(df, dtype, has_gate != 0, has_res != 0)) return v;
-    }
-    if (pw_tiny_applicable(*d, dtype, has_gate != 0)) return 2002;  // pwconv_tiny_f32_kernel
-    const PwGeom pg = prefer_xtile(*d, dtype, has_gate != 0) ? PwGeom{0, 0, 0, 0} : pw_geom(*d, dtype);
-    if (pg.TM) return 1000 + pg.TM * 10 + pg.xrow;  // pwconv_persist_kernel<dtype, KS, NT>
-    if (pw_xtile_applicable(*d, dtype))               // pwconv_xtile_kernel<dtype, input transform?>
-        return 2500 + 2 * pw_xtile_ks(*d, dtype) + ((d->in_swish != 0) ? 1 : 0);
-    if (const int nt = has_gate ? 0 : igemm_nt(*d, dtype)) return 6000 + nt;  // igemm_glds_kernel<NT>
-    if (gemm_pw_applicable(*d, dtype))                // gemm_conv_kernel<dtype, pointwise?>
-        return 2000 + ((d->kt * d->kh * d->kw == 1 && d->st * d->sh * d->sw == 1) ? 0 : 1);
-    int NT, MT;
-    conv_variant(*d, NT, MT);
-    return NT * 10 + MT;
-}
-
 extern "C" int pasn_dwconv3d_variant(const pasn_conv_desc* d, int dtype) {
-    if (!d || d->Cout_p <= 0 || d->Cout_p % 8 != 0) return 0;
-    if (dw_temporal_applicable(*d, dtype)) return 70000 + d->kt;  // dwconv_t_kernel<dtype, KT> (without pool partial rows; with them the generic kernels)
-    if (dw_tz_geom(*d, dtype).ok) return 60001;  // dwconv3d_tz_kernel (stride 1, planes 9 .. 14 wide)
-    if (const DwMfmaGeom mf = dw_mfma_geom(*d, dtype); mf.ok) return 50001;  // dwconv3d_mfma_kernel (stride 1)
-    const DwMarchGeom m = dw_march_geom(*d, dtype);
-    if (m.WT) return 3000 + m.WT * 10 + d->sw;  // dwconv3d_march_kernel<SW, WT>
-    const DwGeom g = dw_geom(*d);
-    return g.WT ? g.WT * 100 + d->kw * 10 + d->sw : 0;
+    if (!dw_desc_ok(d)) return 0;
+    const DwRoute r = dw_route(*d, dtype, false);  // the launch without pool partial rows
+    switch (r.arm) {
+        case DwRoute::TEMPORAL: return 70000 + d->kt;             // dwconv_t_kernel<dtype, KT>
+        case DwRoute::TZ: return 60001;                           // dwconv3d_tz_kernel
+        case DwRoute::MFMA: return 50001;                         // dwconv3d_mfma_kernel
+        case DwRoute::MARCH: return 3000 + r.m.WT * 10 + d->sw;   // dwconv3d_march_kernel<SW, WT>
+        default: return r.g.WT ? r.g.WT * 100 + d->kw * 10 + d->sw : 0;  // dwconv3d_strip_kernel<dtype, WT, KW, SW>, 0: dwconv3d_kernel
+    }
 }
 
 extern "C" int pasn_dwconv3d_pool_blocks(const pasn_conv_desc* d, int dtype) {
-    if (!d || d->Cout_p <= 0 || d->Cout_p % 8 != 0) return 0;
-    if (const DtGeom tz = dw_tz_geom(*d, dtype); tz.ok) return tz.nT;
-    const DwMfmaGeom mf = dw_mfma_geom(*d, dtype);
-    if (mf.ok) return mf.chunks;
-    const DwMarchGeom m = dw_march_geom(*d, dtype);
-    if (m.WT) return m.bpc;
-    return dw_geom(*d).blocks;
-}
-
-// Partial rows written by pasn_dwconv3d_se_fwd (always the T-marching VALU stencil, whatever pasn_dwconv3d_fwd would take for the layer).
-extern "C" int pasn_dwconv3d_se_pool_blocks(const pasn_conv_desc* d, int dtype) {
-    if (!d || d->Cout_p <= 0 || d->Cout_p % 8 != 0) return 0;
-    return dw_march_geom(*d, dtype).bpc;
+    return dw_desc_ok(d) ? dw_route(*d, dtype, true).pool_rows : 0;
 }
 
 extern "C" int pasn_dwconv3d_fwd(const void* x, const float* w, const float* scale, const float* bias, void* y,
@@ -965,14 +984,16 @@ extern "C" int pasn_dwconv3d_fwd(const void* x, const float* w, const float* sca
     PASN_REQUIRE(conv_desc_ok(d), "bad geometry (channel strides must be multiples of 8)");
     PASN_REQUIRE(d->Cin == d->Cout && d->Cin_p == d->Cout_p, "depthwise conv keeps the channel count");
     hipStream_t s = (hipStream_t)stream;
-    if (!pool_partial && dw_temporal_applicable(*d, dtype)) return launch_dw_temporal(x, w, scale, bias, y, *d, dtype, s);  // (kt,1,1): T-marching register ring
-    if (const DtGeom tz = dw_tz_geom(*d, dtype); tz.ok) return launch_dw_tz(x, w, scale, bias, y, pool_partial, *d, tz, s);
-    const DwMfmaGeom mf = dw_mfma_geom(*d, dtype);
-    if (mf.ok) return launch_dw_mfma(x, w, scale, bias, y, pool_partial, *d, mf, s);
-    const DwMarchGeom m = dw_march_geom(*d, dtype);
-    if (m.WT) return launch_dw_march(x, w, scale, bias, y, pool_partial, *d, m, s);
-    if (dtype == PASN_F32) return launch_dwconv3d<float>(x, w, scale, bias, y, pool_partial, *d, s);
-    if (dtype == PASN_BF16) return launch_dwconv3d<__bf16>(x, w, scale, bias, y, pool_partial, *d, s);
+    const DwRoute r = dw_route(*d, dtype, pool_partial != nullptr);
+    switch (r.arm) {
+        case DwRoute::TEMPORAL: return launch_dw_temporal(x, w, scale, bias, y, *d, dtype, s);
+        case DwRoute::TZ: return launch_dw_tz(x, w, scale, bias, y, pool_partial, *d, r.tz, s);
+        case DwRoute::MFMA: return launch_dw_mfma(x, w, scale, bias, y, pool_partial, *d, r.mf, s);
+        case DwRoute::MARCH: return launch_dw_march(x, w, scale, bias, y, pool_partial, *d, r.m, s);
+        case DwRoute::STRIP: break;  // strip or generic VALU kernel, by r.g.WT
+    }
+    if (dtype == PASN_F32) return launch_dwconv3d<float>(x, w, scale, bias, y, pool_partial, *d, r.g, s);
+    if (dtype == PASN_BF16) return launch_dwconv3d<__bf16>(x, w, scale, bias, y, pool_partial, *d, r.g, s);
     set_error("pasn_dwconv3d_fwd: unknown dtype");
     return PASN_ERR_ARG;
 }
@@ -980,23 +1001,14 @@ extern "C" int pasn_dwconv3d_fwd(const void* x, const float* w, const float* sca
 // First block of an X3D stage, front half: expand conv + BN + ReLU -> stride-(1,2,2) depthwise stencil + BN (+ act, + SE pool partial rows)
 // in ONE launch (x3d_expdw.hip).  de = the 1x1x1 conv (fragment-major weights), d = the depthwise conv on its output.
 extern "C" int pasn_x3d_expdw_supported(const pasn_conv_desc* de, const pasn_conv_desc* d, int dtype) {
-    if (!conv_desc_ok(de) || !conv_desc_ok(d)) return 0;
-    pasn_conv_desc f = *de;
-    f.w_frag = 1;
-    return xe_geom(f, *d, dtype).ok;
+    return expdw_geom(de, d, dtype).ok;
 }
 extern "C" int pasn_x3d_expdw_pool_blocks(const pasn_conv_desc* de, const pasn_conv_desc* d, int dtype) {
-    if (!conv_desc_ok(de) || !conv_desc_ok(d)) return 0;
-    pasn_conv_desc f = *de;
-    f.w_frag = 1;
-    const XeGeom g = xe_geom(f, *d, dtype);
+    const XeGeom g = expdw_geom(de, d, dtype);
     return g.ok ? g.chunks : 0;
 }
 extern "C" int pasn_x3d_expdw_variant(const pasn_conv_desc* de, const pasn_conv_desc* d, int dtype) {
-    if (!conv_desc_ok(de) || !conv_desc_ok(d)) return -1;
-    pasn_conv_desc f = *de;
-    f.w_frag = 1;
-    const XeGeom g = xe_geom(f, *d, dtype);
+    const XeGeom g = expdw_geom(de, d, dtype);
     return g.ok ? (g.tz ? 1 : 0) : -1;
 }
 extern "C" int pasn_x3d_expdw_fwd(const void* x, const void* wa, const float* scale_a, const float* bias_a, const float* w, const float* scale,
@@ -1005,7 +1017,7 @@ extern "C" int pasn_x3d_expdw_fwd(const void* x, const void* wa, const float* sc
     PASN_REQUIRE(x && wa && bias_a && w && scale && bias && y, "null pointer");  // scale_a may be NULL: norm_a's scale folded into wa by the caller
     PASN_REQUIRE(conv_desc_ok(de) && conv_desc_ok(d), "bad geometry (channel strides must be multiples of 8)");
     PASN_REQUIRE(dtype == PASN_BF16 && de->w_frag == 1, "bf16 with fragment-major expand weights only");
-    const XeGeom g = xe_geom(*de, *d, dtype);
+    const XeGeom g = expdw_geom(de, d, dtype);
     PASN_REQUIRE(g.ok, "layer pair not covered (pasn_x3d_expdw_supported returns 0)");
     return launch_x3d_expdw(x, wa, scale_a, bias_a, w, scale, bias, y, pool_partial, *de, *d, g, (hipStream_t)stream);
 }
@@ -1013,18 +1025,10 @@ extern "C" int pasn_x3d_expdw_fwd(const void* x, const void* wa, const float* sc
 // Depthwise stencil + squeeze-excite gate in ONE launch (the clip's last-arriving block computes the gate); only where the T-marching
 // stencil covers the layer -- pasn_dwconv3d_se_supported says so, the caller otherwise issues pasn_dwconv3d_fwd + pasn_se_gate_fwd.
 extern "C" int pasn_dwconv3d_se_supported(const pasn_conv_desc* d, int dtype, int Cse) {
-    if (!d || d->Cout_p <= 0 || d->Cout_p % 8 != 0 || Cse <= 0) return 0;
-    if (const char* e = tune("PASN_NO_SE_FUSE"))
-        if (e[0] == '1') return 0;
-    if (dw_mfma_geom(*d, dtype).ok) return 0;    // the matrix-core stencil + the stand-alone gate beat the fused VALU launch (8669 vs 8623 clips/s)
-    const DwMarchGeom m = dw_march_geom(*d, dtype);
-    // The last block of a clip computes the gate alone, at the END of the launch: atomic + acquire, the partial rows (agent-scope loads:
-    // memory-side round trips), two FCs -- an exposed tail of 5-30 us that grows with the channel count (432 channels: +29 us per launch,
-    // 216: +4..9 us) against ~9 us for the stand-alone gate launch it replaces.  Measured end to end (32 x 16 x 224 x 224, one box): fused
-    // everywhere 8084 clips/s, fused up to 256 channels 8218, up to 128 channels 8250, nowhere 8193.  A version of the tail with every
-    // load batched up front (fc rows in registers) moved 432 channels to +16 us and the narrow stages to +6..9 us: no better.
-    const int max_c = tune("PASN_SE_FUSE_MAXC") ? atoi(tune("PASN_SE_FUSE_MAXC")) : 128;
-    return m.WT != 0 && d->Cout_p <= max_c && m.R * d->Cout_p >= d->Cout_p + Cse + 8;  // the gate's LDS scratch is the pool scratch
+    return dw_desc_ok(d) && Cse > 0 && Cse <= dw_se_geom(*d, dtype).max_cse;
+}
+extern "C" int pasn_dwconv3d_se_pool_blocks(const pasn_conv_desc* d, int dtype) {
+    return dw_desc_ok(d) ? dw_se_geom(*d, dtype).m.bpc : 0;
 }
 
 extern "C" int pasn_dwconv3d_se_fwd(const void* x, const float* w, const float* scale, const float* bias, void* y, float* pool_partial,
@@ -1032,10 +1036,10 @@ extern "C" int pasn_dwconv3d_se_fwd(const void* x, const float* w, const float* 
                                     const float* fc2_b, int Cse, float* gate, int32_t* counter, void* stream) {
     PASN_REQUIRE(x && w && scale && bias && y && pool_partial && fc1_w && fc1_b && fc2_w && fc2_b && gate && counter, "null pointer");
     PASN_REQUIRE(conv_desc_ok(d) && d->Cin == d->Cout && d->Cin_p == d->Cout_p, "depthwise conv keeps the channel count");
-    PASN_REQUIRE(pasn_dwconv3d_se_supported(d, dtype, Cse), "layer not covered by the fused stencil + gate launch");
-    const DwMarchGeom m = dw_march_geom(*d, dtype);
+    const DwSe r = dw_se_geom(*d, dtype);
+    PASN_REQUIRE(Cse > 0 && Cse <= r.max_cse, "layer not covered by the fused stencil + gate launch");
     const DwSeArgs se = {fc1_w, fc1_b, fc2_w, fc2_b, gate, counter, Cse};
-    return launch_dw_march(x, w, scale, bias, y, pool_partial, *d, m, (hipStream_t)stream, se);
+    return launch_dw_march(x, w, scale, bias, y, pool_partial, *d, r.m, (hipStream_t)stream, se);
 }
 
 // Fast path of the gate (C <= 512, Cse <= 32, Cse % 4 == 0 -- every X3D width): the kernel is three dependent round trips

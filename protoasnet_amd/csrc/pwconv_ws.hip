@@ -553,11 +553,6 @@ WsGeom pw_ws_geom(const pasn_conv_desc& d, int dtype, bool has_gate, bool has_re
     return g;
 }
 
-int pw_ws_variant(const pasn_conv_desc& d, int dtype, bool has_gate, bool has_res) {
-    const WsGeom g = pw_ws_geom(d, dtype, has_gate, has_res, false);
-    return g.ok ? 7000 + g.KS * 10 + g.MT : 0;
-}
-
 int launch_pw_ws(const void* x, const void* w, const float* scale, const float* bias, const void* res, const float* gate, void* y,
                  const pasn_conv_desc& d, const WsGeom& g, hipStream_t s, const WsSe* sep, const WsPair* pairp) {
     const WsSe se = sep ? *sep : WsSe{nullptr, 0, 0.0f, nullptr, nullptr, nullptr, nullptr, 0, 0};

@@ -242,8 +242,6 @@ __global__ __launch_bounds__(256) void dw_wgrad_partial_kernel(const T* __restri
 
 __global__ void dw_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int chunks, int taps, int C, int Cp);
 bool pw_wgrad_bf16(const void* x, const void* dy, float* dw, const pasn_conv_desc& d, hipStream_t s);
-size_t dw_wgrad_strip_floats(const pasn_conv_desc& d);
-bool dw_wgrad_strip(const void* x, const void* dy, float* ws, float* dw, const pasn_conv_desc& d, int dtype, hipStream_t s);
 
 static int wgrad_rows_per_wave(long R, int tiles) {
     long waves_per_tile = std::max<long>(1, std::min<long>(std::min(8192, 2048 + 65536 / std::max(1, tiles)) / std::max(1, tiles), R / 128));
@@ -253,11 +251,15 @@ static int wgrad_rows_per_wave(long R, int tiles) {
     return (int)rpw;
 }
 
+static int pow2_at_least(int v) {  // a block's channel groups, padded so that they divide its 256 threads
+    int b = 1;
+    while (b < v) b <<= 1;
+    return b;
+}
+
 static long dw_wgrad_rows_per_chunk(const pasn_conv_desc& d) {
     const long R = (long)d.N * d.To * d.Ho * d.Wo;
-    int CG = d.Cout_p / 8, b = 1;
-    while (b < CG) b <<= 1;
-    const int RL = 256 / b;
+    const int RL = 256 / pow2_at_least(d.Cout_p / 8);
     const long chunks = std::max<long>(1, std::min<long>(2048, R / ((long)RL * 8)));
     return (R + chunks - 1) / chunks;
 }
@@ -265,43 +267,6 @@ static long dw_wgrad_rows_per_chunk(const pasn_conv_desc& d) {
 }  // namespace pasn
 
 using namespace pasn;
-
-extern "C" size_t pasn_conv3d_wgrad_workspace_bytes(const pasn_conv_desc* d, int dtype) {
-    return d ? wgrad_halo_workspace_bytes(*d, dtype) : 0;
-}
-
-extern "C" int pasn_conv3d_wgrad_ws(const void* x, const void* dy, float* dw, const pasn_conv_desc* d, int dtype, void* ws, void* stream) {
-    PASN_REQUIRE(x && dy && dw && d, "null pointer");
-    PASN_REQUIRE(d->Cin_p % 8 == 0 && d->Cout_p % 8 == 0 && d->Cin <= d->Cin_p && d->Cout <= d->Cout_p, "bad channel extents");
-    if (ws && wgrad_halo(x, dy, dw, ws, *d, dtype, (hipStream_t)stream)) return check_launch("conv3d_wgrad_halo");
-    return pasn_conv3d_wgrad(x, dy, dw, d, dtype, stream);
-}
-
-extern "C" int pasn_conv3d_wgrad(const void* x, const void* dy, float* dw, const pasn_conv_desc* d, int dtype, void* stream) {
-    PASN_REQUIRE(x && dy && dw && d, "null pointer");
-    PASN_REQUIRE(d->Cin_p % 8 == 0 && d->Cout_p % 8 == 0 && d->Cin <= d->Cin_p && d->Cout <= d->Cout_p, "bad channel extents");
-    const int taps = d->kt * d->kh * d->kw;
-    if (dtype == PASN_BF16 && !tune("PASN_NO_WGRAD_LDS") && pw_wgrad_bf16(x, dy, dw, *d, (hipStream_t)stream))
-        return check_launch("conv3d_wgrad");
-    const int co_tiles = ceil_div(d->Cout, 32), ci_tiles = ceil_div(d->Cin, 32);
-    const long tiles = (long)co_tiles * ci_tiles * taps;
-    PASN_REQUIRE(tiles <= 65535, "too many weight tiles for one launch");
-    const long R = (long)d->N * d->To * d->Ho * d->Wo;
-    const int rpw = wgrad_rows_per_wave(R, (int)tiles);
-    const dim3 grid(ceil_div(R, (long)rpw * 4), (unsigned)tiles);
-    const bool pw = taps == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0;
-    hipStream_t s = (hipStream_t)stream;
-#define WG(T, P) hipLaunchKernelGGL((conv_wgrad_kernel<T, P>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, dw, *d, ci_tiles, rpw)
-    if (dtype == PASN_BF16) {
-        if (pw) WG(__bf16, true);
-        else WG(__bf16, false);
-    } else {
-        if (pw) WG(float, true);
-        else WG(float, false);
-    }
-#undef WG
-    return check_launch("conv3d_wgrad");
-}
 
 // im2col of the planar clip for the first conv's weight gradient: X[row][col] (bf16, 32-column groups), col = (ci, r, s); then the
 // gradient is the pointwise GEMM dW[co][col] = sum_rows dy[row][co] X[row][col] on the LDS-transposed bf16 MFMA kernel.  The
@@ -522,38 +487,6 @@ extern "C" int pasn_dwconv3d_dgrad(const void* dy, const float* w, void* dx, con
     return check_launch("dwconv3d_dgrad");
 }
 
-extern "C" size_t pasn_dwconv3d_wgrad_workspace_floats(const pasn_conv_desc* d) {
-    if (!d || d->Cout_p <= 0 || d->Cout_p % 8 || d->Cout_p > 2048) return 0;
-    const size_t fast = tune("PASN_NO_DWWG_STRIP") ? 0 : dw_wgrad_strip_floats(*d);
-    if (fast) return fast;
-    const long R = (long)d->N * d->To * d->Ho * d->Wo;
-    const long rpc = dw_wgrad_rows_per_chunk(*d);
-    const long chunks = (R + rpc - 1) / rpc;
-    return (size_t)chunks * d->kt * d->kh * d->kw * d->Cout_p;
-}
-
-extern "C" int pasn_dwconv3d_wgrad(const void* x, const void* dy, float* ws, float* dw, const pasn_conv_desc* d, int dtype, void* stream) {
-    PASN_REQUIRE(x && dy && ws && dw && d, "null pointer");
-    PASN_REQUIRE(d->Cin_p == d->Cout_p && d->Cin_p % 8 == 0 && d->Cout_p <= 2048, "depthwise conv keeps the channel stride (<= 2048)");
-    PASN_REQUIRE(d->kh * d->kw <= 9, "spatial window above 3x3 is not covered");
-    if (!tune("PASN_NO_DWWG_STRIP") && dw_wgrad_strip(x, dy, ws, dw, *d, dtype, (hipStream_t)stream)) return check_launch("dwconv3d_wgrad");
-    const long R = (long)d->N * d->To * d->Ho * d->Wo;
-    const long rpc = dw_wgrad_rows_per_chunk(*d);
-    const int chunks = (int)((R + rpc - 1) / rpc);
-    int CG = d->Cout_p / 8, CGb = 1;
-    while (CGb < CG) CGb <<= 1;
-    const int taps = d->kt * d->kh * d->kw;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(chunks, 1, d->kt);
-    if (dtype == PASN_BF16)
-        hipLaunchKernelGGL(dw_wgrad_partial_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)x, (const __bf16*)dy, ws, *d, CG, CGb, rpc);
-    else
-        hipLaunchKernelGGL(dw_wgrad_partial_kernel<float>, grid, dim3(256), 0, s, (const float*)x, (const float*)dy, ws, *d, CG, CGb, rpc);
-    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(ceil_div((long)taps * d->Cout_p, 64)), dim3(256), 0, s, ws, dw, chunks, taps, d->Cout,
-                       d->Cout_p);
-    return check_launch("dwconv3d_wgrad");
-}
-
 // =====================================================================================================================
 // bf16 fast paths
 // =====================================================================================================================
@@ -717,22 +650,6 @@ __global__ __launch_bounds__(256) void pw_wgrad_bf16_kernel(const __bf16* __rest
     }
 }
 
-template <int KT, int TPW>
-static void launch_pw_wgrad_bf16(const void* x, const void* dy, float* dw, const pasn_conv_desc& d, int co_tiles, int ci_tiles, int gy,
-                                 hipStream_t s) {
-    const long R = (long)d.N * d.To * d.Ho * d.Wo;
-    // split-K partitions: enough blocks to fill the chip, but every partition ends in ntiles*1024 atomics on the same addresses
-    const long ntiles = (long)co_tiles * ci_tiles;
-    const int taps = d.kt * d.kh * d.kw;
-    const long want_blocks = std::max<long>(1, std::min<long>(2048 / ((long)gy * taps) + 1, std::max<long>(16, 3000 / ntiles)));
-    long rpb = std::max<long>(KT, (R + want_blocks - 1) / want_blocks);
-    rpb = (rpb + KT - 1) / KT * KT;
-    const dim3 grid(ceil_div(R, rpb), gy, taps);
-    const size_t lds = (size_t)(co_tiles + ci_tiles) * 32 * WgLds<KT>::PITCH;
-    hipLaunchKernelGGL((pw_wgrad_bf16_kernel<KT, TPW>), grid, dim3(256), lds, s, (const __bf16*)x, (const __bf16*)dy, dw, d, co_tiles, ci_tiles,
-                       (int)rpb);
-}
-
 // ---- the same for WIDE stride-1 pointwise layers (X3D stages 4-5: 216 <-> 96, 432 <-> 192 channels) -----------------------------
 // pw_wgrad_bf16_kernel stages ALL channels of dy and x per 32-row step in every block and then lets blockIdx.y pick 16 of the (co, ci)
 // tiles: on the 432 x 192 layers six y-blocks each load, transpose and store the same 624 channels for 8 MFMAs per wave and step, one
@@ -860,68 +777,144 @@ __global__ __launch_bounds__(256) void pw_wgrad_tile_kernel(const __bf16* __rest
         }
 }
 
-static bool pw_wgrad_tile(const void* x, const void* dy, float* dw, const pasn_conv_desc& d, hipStream_t s) {
-    if (const char* e = tune("PASN_NO_WGRAD_TILE"))
-        if (e[0] == '1') return false;
+// ---- decide (geometry, ok = 0: not covered) and launch of the two bf16 kernels above ---------------------------------------------
+struct WgTile {  // pw_wgrad_tile_kernel<cot, cit>
+    int ok, cot, cit, co_groups, ci_groups, rpb, gy2;
+    dim3 grid;
+    size_t lds;
+};
+static WgTile pw_wgrad_tile_geom(const pasn_conv_desc& d) {
+    WgTile g{};
     const bool pointwise = d.kt * d.kh * d.kw == 1 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 0 && d.ph == 0 && d.pw == 0;
     const int co_tiles = ceil_div(d.Cout_p, 32), ci_tiles = ceil_div(d.Cin_p, 32);
-    if (!pointwise || co_tiles + ci_tiles <= 6) return false;  // narrow layers: every block stages all channels anyway
+    if (tune_is("PASN_NO_WGRAD_TILE", '1') || !pointwise || co_tiles + ci_tiles <= 6) return g;  // narrow layers: every block stages all channels anyway
     // tiles per wave along the wide side (PASN_WGT_WIDE=0: one tile per wave everywhere, the kernel of rounds 2-3)
     const bool wide = !tune_is("PASN_WGT_WIDE", '0');
-    const int cot = wide && co_tiles >= 2 * ci_tiles ? 2 : 1, cit = wide && cot == 1 && ci_tiles >= 2 * co_tiles ? 2 : 1;
-    const int co_groups = ceil_div(co_tiles, 2 * cot), ci_groups = ceil_div(ci_tiles, 2 * cit);
+    g.cot = wide && co_tiles >= 2 * ci_tiles ? 2 : 1, g.cit = wide && g.cot == 1 && ci_tiles >= 2 * co_tiles ? 2 : 1;
+    g.co_groups = ceil_div(co_tiles, 2 * g.cot), g.ci_groups = ceil_div(ci_tiles, 2 * g.cit);
     const long R = (long)d.N * d.To * d.Ho * d.Wo;
-    const int gy = co_groups * ci_groups;
+    const int gy = g.co_groups * g.ci_groups;
     // row partitions: about four blocks per CU in flight, at least two 128-row steps each
     // (two tiles per wave: the same ~13 steps per block, i.e. half the blocks -- 57-59 us at 216 <-> 96 against 64-69 with 1024: r04_pwwg_xcd.txt)
-    const long target = tune_dev("PASN_WGT_BLOCKS") ? atol(tune_dev("PASN_WGT_BLOCKS")) : (cot * cit == 2 ? 512 : 1024);
-    long parts = std::max<long>(1, std::min<long>(target / gy + 1, R / (2 * WT_KT)));
-    long rpb = (ceil_div(R, parts) + WT_KT - 1) / WT_KT * WT_KT;
-    const long gx = ceil_div(R, rpb);
-    const bool xcd = !tune_is("PASN_WGT_XCD", '0');
-    const dim3 grid = xcd ? dim3((unsigned)(ceil_div(gx, 8L) * 8 * gy)) : dim3((unsigned)gx, gy);
-    const size_t lds = (size_t)64 * (cot + cit) * WT_PITCH;
-#define WGT(A, B)                                                                                                                       \
-    hipLaunchKernelGGL((pw_wgrad_tile_kernel<A, B>), grid, dim3(256), lds, s, (const __bf16*)x, (const __bf16*)dy, dw, d, co_groups, ci_groups, \
-                       (int)rpb, xcd ? gy : 0)
-    if (cot == 2) WGT(2, 1);
-    else if (cit == 2) WGT(1, 2);
-    else WGT(1, 1);
-#undef WGT
-    return true;
+    const long target = tune_dev("PASN_WGT_BLOCKS") ? atol(tune_dev("PASN_WGT_BLOCKS")) : (g.cot * g.cit == 2 ? 512 : 1024);
+    const long parts = std::max<long>(1, std::min<long>(target / gy + 1, R / (2 * WT_KT)));
+    g.rpb = (ceil_div(R, parts) + WT_KT - 1) / WT_KT * WT_KT;
+    const long gx = ceil_div(R, g.rpb);
+    g.gy2 = tune_is("PASN_WGT_XCD", '0') ? 0 : gy;
+    g.grid = g.gy2 ? dim3((unsigned)(ceil_div(gx, 8L) * 8 * gy)) : dim3((unsigned)gx, gy);
+    g.lds = (size_t)64 * (g.cot + g.cit) * WT_PITCH;
+    g.ok = 1;
+    return g;
 }
 
-// returns false when the geometry is outside the fast path
-bool pw_wgrad_bf16(const void* x, const void* dy, float* dw, const pasn_conv_desc& d, hipStream_t s) {
-    if (d.kt * d.kh * d.kw > 64) return false;
-    if (pw_wgrad_tile(x, dy, dw, d, s)) return true;
-    const int co_tiles = ceil_div(d.Cout_p, 32), ci_tiles = ceil_div(d.Cin_p, 32);
-    const int ntiles = co_tiles * ci_tiles;
-    const bool small = (co_tiles + ci_tiles) <= 6;  // few channels: stage more rows per step so every thread has a patch to move
-    const int KT = small ? 128 : 32;
-    if ((size_t)(co_tiles + ci_tiles) * 32 * (KT * 2 + 16) > 64 * 1024) return false;
-    if ((KT / 8) * (d.Cout_p / 8 + d.Cin_p / 8) > 512) return false;  // the kernel's register pipeline holds 2 patches per thread
-    int tpw = ceil_div(ntiles, 4);
-    tpw = tpw <= 1 ? 1 : tpw <= 2 ? 2 : tpw <= 4 ? 4 : 8;
+struct WgLdsGeom {  // pw_wgrad_bf16_kernel<KT, tpw>
+    int ok, KT, tpw, co_tiles, ci_tiles, rpb;
+    dim3 grid;
+    size_t lds;
+};
+static WgLdsGeom pw_wgrad_lds_geom(const pasn_conv_desc& d) {
+    WgLdsGeom g{};
+    g.co_tiles = ceil_div(d.Cout_p, 32), g.ci_tiles = ceil_div(d.Cin_p, 32);
+    const int ntiles = g.co_tiles * g.ci_tiles, taps = d.kt * d.kh * d.kw;
+    g.KT = g.co_tiles + g.ci_tiles <= 6 ? 128 : 32;  // few channels: stage more rows per step so every thread has a patch to move
+    g.lds = (size_t)(g.co_tiles + g.ci_tiles) * 32 * (g.KT * 2 + 16);  // WgLds<KT>::PITCH per channel row
+    if (g.lds > 64 * 1024) return g;
+    if ((g.KT / 8) * (d.Cout_p / 8 + d.Cin_p / 8) > 512) return g;  // the kernel's register pipeline holds 2 patches per thread
+    g.tpw = ceil_div(ntiles, 4);
+    g.tpw = g.tpw <= 1 ? 1 : g.tpw <= 2 ? 2 : g.tpw <= 4 ? 4 : 8;
     const int tpw_cap = tune_dev("PASN_WG_TPW") ? atoi(tune_dev("PASN_WG_TPW")) : 4;  // 8 tiles per wave (occupancy 1) measured 7 % slower
-    tpw = std::min(tpw, std::max(1, tpw_cap));
-    const int gy = ceil_div(ntiles, 4 * tpw);
-#define PW(K, T) launch_pw_wgrad_bf16<K, T>(x, dy, dw, d, co_tiles, ci_tiles, gy, s)
-    if (small) {
-        if (tpw == 1) PW(128, 1);
-        else if (tpw == 2) PW(128, 2);
+    g.tpw = std::min(g.tpw, std::max(1, tpw_cap));
+    const int gy = ceil_div(ntiles, 4 * g.tpw);
+    const long R = (long)d.N * d.To * d.Ho * d.Wo;
+    // split-K partitions: enough blocks to fill the chip, but every partition ends in ntiles*1024 atomics on the same addresses
+    const long want_blocks = std::max<long>(1, std::min<long>(2048 / ((long)gy * taps) + 1, std::max<long>(16, 3000 / ntiles)));
+    g.rpb = (int)((std::max<long>(g.KT, (R + want_blocks - 1) / want_blocks) + g.KT - 1) / g.KT * g.KT);
+    g.grid = dim3(ceil_div(R, g.rpb), gy, taps);
+    g.ok = 1;
+    return g;
+}
+
+// pasn_conv3d_wgrad[_ws]: which kernel takes the layer.  HALO: stride-1 "same" (1,3,3) / (3,1,1) convs through the caller's partial buffer
+// (wgrad_halo.hip: covered exactly where wgrad_halo_workspace_bytes is not 0); TILE / LDS: the bf16 kernels above; GENERIC: conv_wgrad_kernel.
+struct PwWgRoute {
+    enum Arm { HALO, TILE, LDS, GENERIC } arm;
+    WgTile t;
+    WgLdsGeom l;
+};
+static PwWgRoute pw_wgrad_route(const pasn_conv_desc& d, int dtype, bool has_ws, bool lds_switch = true) {
+    PwWgRoute r{};
+    r.arm = PwWgRoute::GENERIC;
+    if (has_ws && wgrad_halo_workspace_bytes(d, dtype) != 0) r.arm = PwWgRoute::HALO;
+    else if (dtype != PASN_BF16 || (lds_switch && tune("PASN_NO_WGRAD_LDS")) || d.kt * d.kh * d.kw > 64) return r;
+    else if ((r.t = pw_wgrad_tile_geom(d)).ok) r.arm = PwWgRoute::TILE;
+    else if ((r.l = pw_wgrad_lds_geom(d)).ok) r.arm = PwWgRoute::LDS;
+    return r;
+}
+
+// launches the TILE / LDS arm; false: the route is neither
+bool pw_wgrad_bf16(const void* x, const void* dy, float* dw, const pasn_conv_desc& d, const PwWgRoute& r, hipStream_t s) {
+    const __bf16 *xb = (const __bf16*)x, *dyb = (const __bf16*)dy;
+#define WGT(A, B) hipLaunchKernelGGL((pw_wgrad_tile_kernel<A, B>), r.t.grid, dim3(256), r.t.lds, s, xb, dyb, dw, d, r.t.co_groups, r.t.ci_groups, r.t.rpb, r.t.gy2)
+#define PW(K, T) hipLaunchKernelGGL((pw_wgrad_bf16_kernel<K, T>), r.l.grid, dim3(256), r.l.lds, s, xb, dyb, dw, d, r.l.co_tiles, r.l.ci_tiles, r.l.rpb)
+    if (r.arm == PwWgRoute::TILE) {
+        if (r.t.cot == 2) WGT(2, 1);
+        else if (r.t.cit == 2) WGT(1, 2);
+        else WGT(1, 1);
+    } else if (r.arm == PwWgRoute::LDS && r.l.KT == 128) {
+        if (r.l.tpw == 1) PW(128, 1);
+        else if (r.l.tpw == 2) PW(128, 2);
         else PW(128, 4);
-    } else {
-        if (tpw == 1) PW(32, 1);
-        else if (tpw == 2) PW(32, 2);
-        else if (tpw == 4) PW(32, 4);
+    } else if (r.arm == PwWgRoute::LDS) {
+        if (r.l.tpw == 1) PW(32, 1);
+        else if (r.l.tpw == 2) PW(32, 2);
+        else if (r.l.tpw == 4) PW(32, 4);
         else PW(32, 8);
     }
 #undef PW
-    return true;
+#undef WGT
+    return r.arm == PwWgRoute::TILE || r.arm == PwWgRoute::LDS;
+}
+
+// the first conv's weight gradient over its im2col rows (above): the bf16 kernels whatever PASN_NO_WGRAD_LDS says
+bool pw_wgrad_bf16(const void* x, const void* dy, float* dw, const pasn_conv_desc& d, hipStream_t s) {
+    return pw_wgrad_bf16(x, dy, dw, d, pw_wgrad_route(d, PASN_BF16, false, false), s);
 }
 
 }  // namespace pasn
+
+extern "C" size_t pasn_conv3d_wgrad_workspace_bytes(const pasn_conv_desc* d, int dtype) {
+    return d ? wgrad_halo_workspace_bytes(*d, dtype) : 0;
+}
+
+extern "C" int pasn_conv3d_wgrad_ws(const void* x, const void* dy, float* dw, const pasn_conv_desc* d, int dtype, void* ws, void* stream) {
+    PASN_REQUIRE(x && dy && dw && d, "null pointer");
+    PASN_REQUIRE(d->Cin_p % 8 == 0 && d->Cout_p % 8 == 0 && d->Cin <= d->Cin_p && d->Cout <= d->Cout_p, "bad channel extents");
+    hipStream_t s = (hipStream_t)stream;
+    const PwWgRoute r = pw_wgrad_route(*d, dtype, ws != nullptr);
+    if (r.arm == PwWgRoute::HALO && wgrad_halo(x, dy, dw, ws, *d, dtype, s)) return check_launch("conv3d_wgrad_halo");
+    if (pw_wgrad_bf16(x, dy, dw, *d, r, s)) return check_launch("conv3d_wgrad");
+    const int taps = d->kt * d->kh * d->kw, co_tiles = ceil_div(d->Cout, 32), ci_tiles = ceil_div(d->Cin, 32);
+    const long tiles = (long)co_tiles * ci_tiles * taps;
+    PASN_REQUIRE(tiles <= 65535, "too many weight tiles for one launch");
+    const long R = (long)d->N * d->To * d->Ho * d->Wo;
+    const int rpw = wgrad_rows_per_wave(R, (int)tiles);
+    const dim3 grid(ceil_div(R, (long)rpw * 4), (unsigned)tiles);
+    const bool pw = taps == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0;
+#define WG(T, P) hipLaunchKernelGGL((conv_wgrad_kernel<T, P>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, dw, *d, ci_tiles, rpw)
+    if (dtype == PASN_BF16) {
+        if (pw) WG(__bf16, true);
+        else WG(__bf16, false);
+    } else {
+        if (pw) WG(float, true);
+        else WG(float, false);
+    }
+#undef WG
+    return check_launch("conv3d_wgrad");
+}
+
+extern "C" int pasn_conv3d_wgrad(const void* x, const void* dy, float* dw, const pasn_conv_desc* d, int dtype, void* stream) {
+    return pasn_conv3d_wgrad_ws(x, dy, dw, d, dtype, nullptr, stream);
+}
 
 // ---- depthwise 3x3 (spatial) weight gradient, strip form -------------------------------------------------------------------
 // item = (channel group, strip of WT outputs along w, HR consecutive output rows of one (n, to) plane); one temporal tap per
@@ -1392,8 +1385,7 @@ static bool dw_temporal_ok(const pasn_conv_desc& d) {
            d.Cout_p % 8 == 0 && d.Cout_p <= 2048;
 }
 static long dw_temporal_blocks(const pasn_conv_desc& d) {
-    int CG = d.Cout_p / 8, b = 1;
-    while (b < CG) b <<= 1;
+    const int b = pow2_at_least(d.Cout_p / 8);
     const long items = (long)d.N * d.Hi * d.Wi;
     return std::min<long>((items + 256 / b - 1) / (256 / b), 2048);
 }
@@ -1412,8 +1404,7 @@ static DwWgGeom dw_wgrad_strip_geom(const pasn_conv_desc& d) {
     g.strips = ceil_div(d.Wo, g.WT);
     g.CG = d.Cout_p / 4;  // 4 channels per thread
     if (g.CG > 256) return g;
-    g.CGb = 1;
-    while (g.CGb < g.CG) g.CGb <<= 1;
+    g.CGb = pow2_at_least(g.CG);
     g.PL = 256 / g.CGb;
     // rows per item: enough items to fill the chip a few times over, few enough partial blocks to keep the combine small
     const long planes = (long)d.N * d.To;
@@ -1429,14 +1420,9 @@ static DwWgGeom dw_wgrad_strip_geom(const pasn_conv_desc& d) {
     return g;
 }
 
-}  // namespace pasn
-
-namespace pasn {
-
 // T-marching form: 3x3x3, temporal stride 1 and pad 1, frames kept (To == Ti)
 static bool dw_wgrad_march_ok(const pasn_conv_desc& d) {
-    if (const char* e = tune("PASN_NO_DWWG_MARCH"))
-        if (e[0] == '1') return false;
+    if (tune_is("PASN_NO_DWWG_MARCH", '1')) return false;
     return d.kt == 3 && d.st == 1 && d.pt == 1 && d.To == d.Ti && d.kh == 3 && d.kw == 3 && d.ph == 1 && d.pw == 1;
 }
 static long dw_wgrad_march_blocks(const pasn_conv_desc& d, const DwWgGeom& g) {
@@ -1471,83 +1457,93 @@ static DwWgMarch2 dw_wgrad_march2_geom(const pasn_conv_desc& d) {
     return g;
 }
 
-size_t dw_wgrad_strip_floats(const pasn_conv_desc& d) {
-    if (dw_temporal_ok(d)) return (size_t)dw_temporal_blocks(d) * d.kt * d.Cout_p;
-    const DwWgGeom g = dw_wgrad_strip_geom(d);
-    if (g.ok && dw_wgrad_march_ok(d)) {  // bf16 takes a marching kernel, fp32 the strip kernel: room for either
-        const DwWgMarch2 m2 = dw_wgrad_march2_geom(d);
-        return (size_t)std::max<long>(std::max<long>(dw_wgrad_march_blocks(d, g), g.blocks), m2.ok ? m2.blocks : 0) * 27 * d.Cout_p;
-    }
-    return g.ok ? (size_t)g.blocks * d.kt * 9 * d.Cout_p : 0;
-}
-
-bool dw_wgrad_strip(const void* x, const void* dy, float* ws, float* dw, const pasn_conv_desc& d, int dtype, hipStream_t s) {
-    if (dw_temporal_ok(d)) {
-        int CG = d.Cout_p / 8, CGb = 1;
-        while (CGb < CG) CGb <<= 1;
-        const long items = (long)d.N * d.Hi * d.Wi, blocks = dw_temporal_blocks(d);
-        if (dtype == PASN_BF16)
-            hipLaunchKernelGGL(dw_wgrad_temporal_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, s, (const __bf16*)x, (const __bf16*)dy, ws, d, CG,
-                               CGb, items);
-        else
-            hipLaunchKernelGGL(dw_wgrad_temporal_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)x, (const float*)dy, ws, d, CG, CGb,
-                               items);
-        hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(ceil_div((long)d.kt * d.Cout_p, 64)), dim3(256), 0, s, ws, dw, (int)blocks, d.kt, d.Cout,
-                           d.Cout_p);
-        return true;
-    }
-    const DwWgGeom g = dw_wgrad_strip_geom(d);
-    if (!g.ok) return false;
-    if (const DwWgMarch2 m = dw_wgrad_march2_geom(d); dtype == PASN_BF16 && m.ok) {
-#define DWM2(SWv, WTv, CHv)                                                                                                                      \
-    hipLaunchKernelGGL((dw_wgrad_march2_kernel<SWv, WTv, CHv>), dim3((unsigned)m.blocks), dim3(256), 0, s, (const __bf16*)x, (const __bf16*)dy, ws, d, \
-                       m.CG, m.PL, m.strips, m.items)
-        if (m.SW == 2) {
-            if (m.CH == 2) DWM2(2, 2, 2);
-            else DWM2(2, 2, 4);
-        } else if (m.WT == 3) {
-            if (m.CH == 2) DWM2(1, 3, 2);
-            else DWM2(1, 3, 4);
-        } else {
-            if (m.CH == 2) DWM2(1, 2, 2);
-            else DWM2(1, 2, 4);
-        }
-#undef DWM2
-        hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(ceil_div((long)27 * d.Cout_p, 64)), dim3(256), 0, s, ws, dw, (int)m.blocks, 27, d.Cout, d.Cout_p);
-        return true;
-    }
-    if (dtype == PASN_BF16 && dw_wgrad_march_ok(d)) {
-        const long items = (long)d.N * d.Ho * g.strips, blocks = dw_wgrad_march_blocks(d, g);
-#define DWM(SWv, WTv) \
-    hipLaunchKernelGGL((dw_wgrad_march_kernel<SWv, WTv>), dim3((unsigned)blocks), dim3(256), 0, s, (const __bf16*)x, (const __bf16*)dy, ws, d, g.CG, g.CGb, g.strips, items)
-        if (g.SW == 1) DWM(1, 3);
-        else DWM(2, 2);
-#undef DWM
-        hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(ceil_div((long)27 * d.Cout_p, 64)), dim3(256), 0, s, ws, dw, (int)blocks, 27, d.Cout, d.Cout_p);
-        return true;
-    }
-    const bool fuse3 = tune("PASN_DWWG_FUSED") ? atoi(tune("PASN_DWWG_FUSED")) != 0 : false;
-    const bool na3 = fuse3 && d.kt == 3;
-    const dim3 grid((unsigned)g.blocks, 1, na3 ? 1 : d.kt);
-#define DWS(T, SWv, WTv)                                                                                                              \
-    if (na3)                                                                                                                          \
-        hipLaunchKernelGGL((dw_wgrad_strip_kernel<T, SWv, WTv, 4, 3>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, ws, d, g.CG, g.CGb, \
-                           g.strips, g.HR, g.hgroups, g.items);                                                                      \
-    else                                                                                                                              \
-        hipLaunchKernelGGL((dw_wgrad_strip_kernel<T, SWv, WTv, 4, 1>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, ws, d, g.CG, g.CGb, g.strips, \
-                       g.HR, g.hgroups, g.items)
-    if (dtype == PASN_BF16) {
-        if (g.SW == 1) DWS(__bf16, 1, 3);
-        else DWS(__bf16, 2, 2);
-    } else {
-        if (g.SW == 1) DWS(float, 1, 3);
-        else DWS(float, 2, 2);
-    }
-#undef DWS
-    const int taps = d.kt * 9;
-    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(ceil_div((long)taps * d.Cout_p, 64)), dim3(256), 0, s, ws, dw, (int)g.blocks, taps, d.Cout,
-                       d.Cout_p);
-    return true;
+// pasn_dwconv3d_wgrad: the kernel that takes the layer and the `blocks` partial rows of taps * Cout_p floats it writes into the workspace
+// for dw_wgrad_reduce_kernel.  march2 = false: the ladder without the second marching kernel.
+struct DwWgRoute {
+    enum Arm { TEMPORAL, MARCH2, MARCH, STRIP, GENERIC } arm;
+    DwWgGeom g;    // MARCH, STRIP
+    DwWgMarch2 m;  // MARCH2
+    long rpc;      // GENERIC: output rows per block
+    long blocks;
+    int taps;
+};
+static DwWgRoute dw_wgrad_route(const pasn_conv_desc& d, int dtype, bool march2 = true) {
+    DwWgRoute r{};
+    const bool fast = !tune("PASN_NO_DWWG_STRIP"), bf16 = dtype == PASN_BF16;
+    if (fast && dw_temporal_ok(d)) r.arm = DwWgRoute::TEMPORAL, r.blocks = dw_temporal_blocks(d), r.taps = d.kt;
+    else if (!fast || !(r.g = dw_wgrad_strip_geom(d)).ok) {
+        r.arm = DwWgRoute::GENERIC, r.rpc = dw_wgrad_rows_per_chunk(d), r.taps = d.kt * d.kh * d.kw;
+        r.blocks = ((long)d.N * d.To * d.Ho * d.Wo + r.rpc - 1) / r.rpc;
+    } else if (bf16 && march2 && (r.m = dw_wgrad_march2_geom(d)).ok) r.arm = DwWgRoute::MARCH2, r.blocks = r.m.blocks, r.taps = 27;
+    else if (bf16 && dw_wgrad_march_ok(d)) r.arm = DwWgRoute::MARCH, r.blocks = dw_wgrad_march_blocks(d, r.g), r.taps = 27;
+    else r.arm = DwWgRoute::STRIP, r.blocks = r.g.blocks, r.taps = d.kt * 9;
+    return r;
 }
 
 }  // namespace pasn
+
+// The buffer is sized before the dtype is known: room for the arm of either dtype, and of either marching kernel.
+extern "C" size_t pasn_dwconv3d_wgrad_workspace_floats(const pasn_conv_desc* d) {
+    if (!d || d->Cout_p <= 0 || d->Cout_p % 8 || d->Cout_p > 2048) return 0;
+    long rows = 0;
+    for (int k = 0; k < 4; ++k) {
+        const DwWgRoute r = dw_wgrad_route(*d, k & 1 ? PASN_BF16 : PASN_F32, k < 2);
+        rows = std::max(rows, r.blocks * r.taps);
+    }
+    return (size_t)rows * d->Cout_p;
+}
+
+extern "C" int pasn_dwconv3d_wgrad(const void* x, const void* dy, float* ws, float* dw, const pasn_conv_desc* d, int dtype, void* stream) {
+    PASN_REQUIRE(x && dy && ws && dw && d, "null pointer");
+    PASN_REQUIRE(d->Cin_p == d->Cout_p && d->Cin_p % 8 == 0 && d->Cout_p <= 2048, "depthwise conv keeps the channel stride (<= 2048)");
+    PASN_REQUIRE(d->kh * d->kw <= 9, "spatial window above 3x3 is not covered");
+    hipStream_t s = (hipStream_t)stream;
+    const DwWgRoute r = dw_wgrad_route(*d, dtype);
+    const DwWgGeom& g = r.g;
+    const bool bf16 = dtype == PASN_BF16, na3 = d->kt == 3 && tune("PASN_DWWG_FUSED") && atoi(tune("PASN_DWWG_FUSED")) != 0;
+    const int CG = d->Cout_p / 8, CGb = pow2_at_least(CG);  // TEMPORAL, GENERIC: 8 channels per thread
+    const dim3 one((unsigned)r.blocks), per_tap((unsigned)r.blocks, 1, d->kt), block(256);
+    const __bf16 *xb = (const __bf16*)x, *dyb = (const __bf16*)dy;
+    const float *xf = (const float*)x, *dyf = (const float*)dy;
+#define DWM2(SWv, WTv, CHv) hipLaunchKernelGGL((dw_wgrad_march2_kernel<SWv, WTv, CHv>), one, block, 0, s, xb, dyb, ws, *d, r.m.CG, r.m.PL, r.m.strips, r.m.items)
+#define DWM(SWv, WTv) hipLaunchKernelGGL((dw_wgrad_march_kernel<SWv, WTv>), one, block, 0, s, xb, dyb, ws, *d, g.CG, g.CGb, g.strips, (long)d->N * d->Ho * g.strips)
+#define DWS(T, X, DY, SWv, WTv, NA) \
+    hipLaunchKernelGGL((dw_wgrad_strip_kernel<T, SWv, WTv, 4, NA>), NA == 3 ? one : per_tap, block, 0, s, X, DY, ws, *d, g.CG, g.CGb, g.strips, g.HR, g.hgroups, g.items)
+#define DWS_NA(T, X, DY, SWv, WTv)           \
+    if (na3) DWS(T, X, DY, SWv, WTv, 3); \
+    else DWS(T, X, DY, SWv, WTv, 1)
+    switch (r.arm) {
+        case DwWgRoute::TEMPORAL:
+            if (bf16) hipLaunchKernelGGL(dw_wgrad_temporal_kernel<__bf16>, one, block, 0, s, xb, dyb, ws, *d, CG, CGb, (long)d->N * d->Hi * d->Wi);
+            else hipLaunchKernelGGL(dw_wgrad_temporal_kernel<float>, one, block, 0, s, xf, dyf, ws, *d, CG, CGb, (long)d->N * d->Hi * d->Wi);
+            break;
+        case DwWgRoute::MARCH2:
+            if (r.m.SW == 2 && r.m.CH == 2) DWM2(2, 2, 2);
+            else if (r.m.SW == 2) DWM2(2, 2, 4);
+            else if (r.m.WT == 3 && r.m.CH == 2) DWM2(1, 3, 2);
+            else if (r.m.WT == 3) DWM2(1, 3, 4);
+            else if (r.m.CH == 2) DWM2(1, 2, 2);
+            else DWM2(1, 2, 4);
+            break;
+        case DwWgRoute::MARCH:
+            if (g.SW == 1) DWM(1, 3);
+            else DWM(2, 2);
+            break;
+        case DwWgRoute::STRIP:
+            if (bf16 && g.SW == 1) { DWS_NA(__bf16, xb, dyb, 1, 3); }
+            else if (bf16) { DWS_NA(__bf16, xb, dyb, 2, 2); }
+            else if (g.SW == 1) { DWS_NA(float, xf, dyf, 1, 3); }
+            else { DWS_NA(float, xf, dyf, 2, 2); }
+            break;
+        case DwWgRoute::GENERIC:
+            if (bf16) hipLaunchKernelGGL(dw_wgrad_partial_kernel<__bf16>, per_tap, block, 0, s, xb, dyb, ws, *d, CG, CGb, r.rpc);
+            else hipLaunchKernelGGL(dw_wgrad_partial_kernel<float>, per_tap, block, 0, s, xf, dyf, ws, *d, CG, CGb, r.rpc);
+            break;
+    }
+#undef DWS_NA
+#undef DWS
+#undef DWM
+#undef DWM2
+    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(ceil_div((long)r.taps * d->Cout_p, 64)), block, 0, s, ws, dw, (int)r.blocks, r.taps, d->Cout, d->Cout_p);
+    return check_launch("dwconv3d_wgrad");
+}

@@ -676,6 +676,51 @@ def test_depthwise_wgrad_march_bf16(c, s, shape, monkeypatch):
         _rel(o, outs[-1], 1e-5, "marching vs strip kernel")
 
 
+_S1, _S2 = ((3, 3, 3), 1, (1, 3, 9, 10)), ((3, 3, 3), 2, (1, 3, 12, 14))
+_MARCH1, _NO_MARCH, _NO_STRIP = {"PASN_DWWG_MARCH2": "0"}, {"PASN_NO_DWWG_MARCH": "1"}, {"PASN_NO_DWWG_STRIP": "1"}
+# (arm of pasn_dwconv3d_wgrad's ladder, dtype, (window, spatial stride, (n, t, h, w)), switches): every arm once, 24 channels, ragged strips
+DW_WGRAD_ARMS = [
+    ("temporal", FP32, ((3, 1, 1), 1, (1, 4, 5, 6)), {}), ("temporal", BF, ((3, 1, 1), 1, (1, 4, 5, 6)), {}),
+    ("march2", BF, _S1, {}), ("march2", BF, _S2, {}), ("march2-ch2-wt3", BF, _S1, {"PASN_DWWG_CH": "2", "PASN_DWWG_WT": "3"}),
+    ("march", BF, _S1, _MARCH1), ("march", BF, _S2, _MARCH1),
+    ("strip", FP32, _S1, {}), ("strip", FP32, _S2, {}), ("strip", BF, _S1, _NO_MARCH), ("strip", BF, _S2, _NO_MARCH),
+    ("strip-133", FP32, ((1, 3, 3), 1, (1, 2, 9, 10)), {}),
+    ("generic", FP32, _S1, _NO_STRIP), ("generic", BF, _S1, _NO_STRIP),
+]
+
+
+@pytest.mark.parametrize("arm,dtype,geom,env", DW_WGRAD_ARMS,
+                         ids=[f"{a}-{'bf16' if t == BF else 'fp32'}-s{g[1]}" for a, t, g, _ in DW_WGRAD_ARMS])
+def test_depthwise_wgrad_stays_inside_its_workspace(arm, dtype, geom, env):
+    """The partial buffer of pasn_dwconv3d_wgrad is sized by pasn_dwconv3d_wgrad_workspace_floats without knowing the dtype, and the
+    launch is not told its size: on every arm of the ladder the launch must stay inside it.  The buffer is followed, in the same
+    allocation, by a guard of 4096 floats that must come back bit-identical; the workspace itself starts as NaN (a row that is read but
+    was not written shows in dW), and dW matches autograd on the (bf16-rounded) operands."""
+    lib = _lib.lib()
+    k, s, (n, t, h, w) = geom
+    c, p = 24, tuple(e // 2 for e in k)
+    g = torch.Generator().manual_seed(sum(k) + s + w)
+    x, wt = torch.randn(n, c, t, h, w, generator=g).to(dtype).float(), torch.zeros(c, 1, *k, requires_grad=True)
+    y = F.conv3d(x, wt, stride=(1, s, s), padding=p, groups=c)
+    dy = torch.randn(y.shape, generator=g).to(dtype).float()
+    y.backward(dy)
+    d = _desc(x, y, k, (1, s, s), p)
+    xd, dyd = _cl(x, dtype=dtype), _cl(dy, dtype=dtype)
+    taps, guard = k[0] * k[1] * k[2], 4096
+    ambient = dict.fromkeys(("PASN_DWWG_CH", "PASN_DWWG_WT", "PASN_DWWG_MARCH2", "PASN_DWWG_BLOCKS", "PASN_DWWG_FUSED", "PASN_NO_DWWG_MARCH", "PASN_NO_DWWG_STRIP"))
+    with _lib.tuning_env(**dict(ambient, **env)):  # only this case's switches choose the arm
+        floats = int(lib.pasn_dwconv3d_wgrad_workspace_floats(ctypes.byref(d)))
+        assert floats > 0
+        buf = torch.full((floats + guard,), float("nan"), device=DEV)
+        buf[floats:] = -12345.0
+        sentinel = buf[floats:].clone()
+        dw = torch.zeros(c, taps, device=DEV)
+        _lib.check(lib.pasn_dwconv3d_wgrad(xd.data_ptr(), dyd.data_ptr(), buf.data_ptr(), dw.data_ptr(), ctypes.byref(d), _lib.dtype_code(dtype), _st()))
+        torch.cuda.synchronize()
+    assert torch.equal(buf[floats:].view(torch.int32), sentinel.view(torch.int32)), f"{arm}: the launch wrote past its {floats}-float workspace"
+    _rel(dw.view_as(wt), wt.grad, 1e-4, f"dW ({arm})")
+
+
 @pytest.mark.parametrize("layer", ["c133_64_144", "c311_144_64", "c133_s2_64_230", "dw_54"])
 def test_weight_gradient_kernels_at_full_benchmark_shapes(layer, monkeypatch):
     """Round-2 weight-gradient kernels at the full R(2+1)D-18 / X3D-S benchmark shapes (no CPU oracle finishes there in seconds): each
