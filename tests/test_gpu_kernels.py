@@ -67,29 +67,51 @@ def _cl_input(pb, x, dtype):
 
 
 CONV_CASES = [
-    # cin, cout, k, s, p, shape(T,H,W), act, residual
+    # cin, cout, k, s, p, shape(T,H,W), act, residual -- two clips each; what a case launches is in CONV_RUNS below
     (24, 54, (1, 1, 1), (1, 1, 1), (0, 0, 0), (3, 9, 7), "relu", False),     # X3D expand (Cout 54 -> pad 56)
     (54, 24, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 8, 8), "relu", True),      # X3D project + residual
-    (24, 48, (1, 1, 1), (1, 2, 2), (0, 0, 0), (2, 9, 9), "none", False),     # strided shortcut
+    (24, 48, (1, 1, 1), (1, 2, 2), (0, 0, 0), (2, 9, 9), "none", False),     # strided shortcut, 50 positions per clip: too few for an X tile
     (45, 64, (3, 1, 1), (1, 1, 1), (1, 0, 0), (4, 6, 6), "relu", False),     # R(2+1)D stem temporal conv
     (64, 144, (1, 3, 3), (1, 1, 1), (0, 1, 1), (2, 7, 7), "relu", False),    # Conv2Plus1D spatial
     (144, 64, (3, 1, 1), (2, 1, 1), (1, 0, 0), (5, 4, 4), "none", True),     # temporal, stride 2, residual
     (64, 128, (3, 3, 3), (2, 2, 2), (1, 1, 1), (4, 8, 8), "swish", False),   # generic 3x3x3
-    (432, 192, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 5, 5), "sigmoid", False),  # many k-steps, 6 output tiles (NT=3)
-    (216, 216, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 6, 6), "abs", False),    # 7 output tiles (NT=4, 2 chunks)
-    # pwconv_xtile instances (whole-K position tiles in LDS; S >= 64 positions per clip); 75 / 130 rows = ragged last tile
-    (48, 216, (1, 1, 1), (1, 1, 1), (0, 0, 0), (3, 5, 5), "relu", False),    # KS = 4, two channel groups
-    (96, 216, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 13, 5), "relu", False),   # KS = 6
-    (216, 96, (1, 1, 1), (1, 1, 1), (0, 0, 0), (5, 4, 4), "relu", True),     # KS = 14 + residual, idle 4th wave
-    (192, 432, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 7, 7), "none", False),   # KS = 12, four channel groups
-    (432, 192, (1, 1, 1), (1, 1, 1), (0, 0, 0), (4, 4, 4), "relu", True),    # KS = 28 (split weight loads) + residual
-    (108, 48, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 8, 8), "none", True),     # KS = 8: preferred over the persistent kernel
+    (432, 192, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 5, 5), "sigmoid", False),  # many k-steps, 50 rows: one wave per 32 x 32 tile
+    (216, 216, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 6, 6), "abs", False),    # 7 output tiles; bf16: whole-K X tiles, KS = 14, two channel groups
+    # wide pointwise layers on 75 ... 160 rows: fp32 (>= 64 input channels, <= 8192 rows) goes to the one-wave-per-tile kernel, bf16 to the
+    # weight-stationary kernel where it is routed by default and to the X-tile kernel elsewhere; ragged last tiles throughout
+    (48, 216, (1, 1, 1), (1, 1, 1), (0, 0, 0), (3, 5, 5), "relu", False),    # bf16: weight-stationary, KS = 4, 7 channel tiles
+    (96, 216, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 13, 5), "relu", False),   # bf16: weight-stationary, KS = 6
+    (216, 96, (1, 1, 1), (1, 1, 1), (0, 0, 0), (5, 4, 4), "relu", True),     # bf16: X tile, KS = 14 + residual, idle 4th wave
+    (192, 432, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 7, 7), "none", False),   # bf16: X tile, KS = 12, four channel groups
+    (432, 192, (1, 1, 1), (1, 1, 1), (0, 0, 0), (4, 4, 4), "relu", True),    # bf16: weight-stationary, KS = 28 + residual
+    (108, 48, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 8, 8), "none", True),     # bf16: weight-stationary, KS = 8 + residual
+]
+# (fp32, bf16) instance of every case above, asserted at run time.  conv3d_mfma_kernel itself is left with the strided shortcut; its NT = 3 / 4
+# instances, which the 432 -> 192 and 216 -> 216 cases once ran, have rows of their own in tests/conv_kernel_cases.py (under routing switches).
+CONV_RUNS = [
+    ("pwconv_persist_kernel<f32,4,2,false>", "pwconv_persist_kernel<bf16,2,2,false>"),
+    ("pwconv_persist_kernel<f32,8,1,true>", "pwconv_persist_kernel<bf16,4,1,true>"),
+    ("conv3d_mfma_kernel<f32,2,1>", "conv3d_mfma_kernel<bf16,2,1>"),
+    ("gemm_conv_kernel<f32,false>", "tconv_ws_kernel<3,false>"),
+    ("gemm_conv_kernel<f32,false>", "igemm_halo_kernel<5,1,0>"),
+    ("gemm_conv_kernel<f32,false>", "igemm_glds_kernel<2,1>"),
+    ("gemm_conv_kernel<f32,false>", "igemm_glds_kernel<4,1>"),
+    ("pwconv_tiny_kernel<f32>", "pwconv_tiny_kernel<bf16>"),
+    ("pwconv_tiny_kernel<f32>", "pwconv_xtile_kernel<bf16,14,false>"),
+    ("pwconv_xtile_kernel<f32,16,false>", "pwconv_ws_kernel<4,2,false,false>"),
+    ("pwconv_tiny_kernel<f32>", "pwconv_ws_kernel<6,2,false,false>"),
+    ("pwconv_tiny_kernel<f32>", "pwconv_xtile_kernel<bf16,14,false>"),
+    ("pwconv_tiny_kernel<f32>", "pwconv_xtile_kernel<bf16,12,false>"),
+    ("pwconv_tiny_kernel<f32>", "pwconv_ws_kernel<28,1,false,true>"),
+    ("pwconv_tiny_kernel<f32>", "pwconv_ws_kernel<8,1,false,true>"),
 ]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv3d_mfma(case, dtype):
+    """``pasn_conv3d_fwd`` on the layer shapes of the trunks (the name dates from when conv3d_mfma_kernel ran them all): each case asserts the
+    instance the dispatch ladder gives it today (CONV_RUNS).  Instance by instance, with fp64 references: tests/test_gpu_conv_cases.py."""
     cin, cout, k, s, p, thw, act, use_res = case
     torch.manual_seed(hash(case) % 1000)
     n = 2
@@ -120,6 +142,7 @@ def test_conv3d_mfma(case, dtype):
         ra, rs = _cl_input(pb, res, dtype)
     conv, bn = conv.to(DEV), bn.to(DEV)
     y = pb.conv(xa, conv, bn, act, residual=ra)
+    assert pb.meta[-1]["kernel"] == CONV_RUNS[CONV_CASES.index(case)][dtype == torch.bfloat16], pb.meta[-1]["kernel"]
     plan = pb.finish(xa, y)
     if ra is not None:
         plan.ptrs[ra.buf] = rs.data_ptr()
@@ -134,7 +157,8 @@ def test_conv3d_mfma(case, dtype):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("gate", [False, True])
 def test_conv3d_input_gate_swish(dtype, gate):
-    """X3D project conv: x' = swish(x * gate[n][c]) fused into the operand load."""
+    """X3D stage-2 project conv: x' = swish(x * gate[n][c]) fused into the operand load of the register-resident persistent kernel (Cin_p 56:
+    too narrow for the X-tile and weight-stationary kernels); three clips of 60 positions, so a 32-row tile straddles two clips."""
     torch.manual_seed(3)
     n, cin, cout, thw = 3, 54, 24, (2, 5, 6)
     x = torch.randn(n, cin, *thw)
@@ -155,6 +179,8 @@ def test_conv3d_input_gate_swish(dtype, gate):
         gt[:, :cin] = g.to(DEV)
         gbuf = pb._new_buf(gt.numel() * 4, external=True)
     y = pb.conv(xa, conv.to(DEV), None, "none", in_gate=gbuf, in_swish=True)
+    want = "pwconv_persist_kernel<f32,8,1,false>" if dtype == torch.float32 else "pwconv_persist_kernel<bf16,4,1,false>"
+    assert pb.meta[-1]["kernel"] == want, pb.meta[-1]["kernel"]
     plan = pb.finish(xa, y)
     if gate:
         plan.ptrs[gbuf] = gt.data_ptr()
@@ -164,11 +190,20 @@ def test_conv3d_input_gate_swish(dtype, gate):
     assert_close(_from_cl(out, cout), ref, atol * max(1.0, float(ref.abs().max())), rtol, "gate+swish conv")
 
 
+WIDE_RUNS = {  # cin -> (fp32, bf16) instance
+    216: ("pwconv_xtile_kernel<f32,28,true>", "pwconv_xtile_kernel<bf16,14,true>"),
+    432: ("gemm_conv_kernel<f32,true>", "pwconv_ws_kernel<28,1,true,true>"),
+    96: ("pwconv_xtile_kernel<f32,16,true>", "pwconv_persist_kernel<bf16,8,2,true>"),
+}
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cin,cout", [(216, 96), (432, 192), (96, 48)])
 def test_pointwise_gate_swish_wide(cin, cout, dtype):
-    """Wide project conv with the fused SE gate + Swish input transform (pwconv_xtile XF instances): three clips of 72
-    positions, so a 64-row tile straddles two clips and must pick each row's own gate vector."""
+    """Wide project conv with the fused SE gate + Swish input transform, + residual + ReLU: three clips of 72 positions, so a 64-row (and a
+    32-row) tile straddles two clips and must pick each row's own gate vector.  216 -> 96 runs the X-tile kernel's transform instances in
+    both types; 432 -> 192 the weight-stationary kernel (bf16) and the LDS-tiled GEMM (fp32: K too wide for X tiles in registers);
+    96 -> 48 the persistent kernel in bf16 and the X-tile kernel in fp32 (WIDE_RUNS)."""
     torch.manual_seed(cin)
     n, thw = 3, (2, 6, 6)
     x = torch.randn(n, cin, *thw)
@@ -189,6 +224,7 @@ def test_pointwise_gate_swish_wide(cin, cout, dtype):
     gt[:, :cin] = g.to(DEV)
     gbuf = pb._new_buf(gt.numel() * 4, external=True)
     y = pb.conv(xa, conv.to(DEV), None, "relu", residual=ra, in_gate=gbuf, in_swish=True)
+    assert pb.meta[-1]["kernel"] == WIDE_RUNS[cin][dtype == torch.bfloat16], pb.meta[-1]["kernel"]
     plan = pb.finish(xa, y)
     plan.ptrs[gbuf] = gt.data_ptr()
     plan.ptrs[ra.buf] = rs.data_ptr()
@@ -309,13 +345,33 @@ WS_CASES = [
     (56, 24, (2, 4, 12, 12), True, True, "relu"),      # stage-2 shape class (Cin_p 56)
     (216, 96, (3, 3, 8, 9), False, True, "sigmoid"),   # Swish input without residual; sigmoid(0) != 0: the padded-channel mask must act
 ]
+# what each case runs: (with PASN_WS=2, ... and the smallest tiles, with PASN_WS=0: the kernel the layer had before / has where the
+# weight-stationary kernel is not routed).  The X-tile instances <bf16,4 / 6 / 8,false> of the default plans are held to the reference here.
+WS_RUNS = [
+    ("pwconv_ws_kernel<4,2,false,false>", "pwconv_ws_kernel<4,1,false,false>", "pwconv_xtile_kernel<bf16,4,false>"),
+    ("pwconv_ws_kernel<8,1,true,true>", "pwconv_ws_kernel<8,1,true,true>", "pwconv_persist_kernel<bf16,8,2,true>"),
+    ("pwconv_ws_kernel<8,1,false,true>", "pwconv_ws_kernel<8,1,false,true>", "pwconv_xtile_kernel<bf16,8,false>"),
+    ("pwconv_ws_kernel<6,2,false,false>", "pwconv_ws_kernel<6,1,false,false>", "pwconv_xtile_kernel<bf16,6,false>"),
+    ("pwconv_ws_kernel<14,1,true,true>", "pwconv_ws_kernel<14,1,true,true>", "pwconv_xtile_kernel<bf16,14,true>"),
+    ("pwconv_ws_kernel<14,1,false,true>", "pwconv_ws_kernel<14,1,false,true>", "pwconv_xtile_kernel<bf16,14,false>"),
+    ("pwconv_ws_kernel<12,2,false,false>", "pwconv_ws_kernel<12,1,false,false>", "pwconv_xtile_kernel<bf16,12,false>"),
+    ("pwconv_ws_kernel<28,1,true,true>", "pwconv_ws_kernel<28,1,true,true>", "pwconv_xtile_kernel<bf16,28,true>"),
+    ("pwconv_ws_kernel<28,1,false,true>", "pwconv_ws_kernel<28,1,false,true>", "pwconv_tiny_kernel<bf16>"),
+    ("pwconv_ws_kernel<12,2,false,false>", "pwconv_ws_kernel<12,1,false,false>", "pwconv_xtile_kernel<bf16,12,false>"),
+    ("pwconv_ws_kernel<16,2,false,false>", "pwconv_ws_kernel<16,1,false,false>", "pwconv_tiny_kernel<bf16>"),
+    ("pwconv_ws_kernel<16,2,false,false>", "pwconv_ws_kernel<16,1,false,false>", "pwconv_tiny_kernel<bf16>"),
+    ("pwconv_ws_kernel<8,1,false,false>", "pwconv_ws_kernel<8,1,false,false>", "pwconv_persist_kernel<bf16,8,1,false>"),
+    ("pwconv_ws_kernel<4,1,true,true>", "pwconv_ws_kernel<4,1,true,true>", "pwconv_persist_kernel<bf16,4,1,true>"),
+    ("pwconv_ws_kernel<14,1,true,false>", "pwconv_ws_kernel<14,1,true,false>", "pwconv_xtile_kernel<bf16,14,true>"),
+]
 
 
 @pytest.mark.parametrize("shrink", [False, True])
 @pytest.mark.parametrize("case", WS_CASES)
 def test_pwconv_ws(case, shrink, monkeypatch):
-    """Weight-stationary persistent pointwise kernel: against torch on the bf16-rounded operands AND bit-for-bit against the X-tile /
-    persistent kernels it replaces (same MFMA k order, same epilogue arithmetic)."""
+    """Weight-stationary persistent pointwise kernel: against torch on the bf16-rounded operands AND bit-for-bit against the X-tile kernel
+    it replaces (same MFMA k order, same epilogue arithmetic).  The kernel the layer takes with PASN_WS=0 (X-tile, persistent or
+    one-wave-per-tile: WS_RUNS) is held to the same reference with the same tolerance, then compared with the weight-stationary result."""
     cin, cout, (n, t, h, w), use_res, gate, act = case
     dtype = torch.bfloat16
     torch.manual_seed(cin * 7 + cout)
@@ -372,12 +428,16 @@ def test_pwconv_ws(case, shrink, monkeypatch):
             monkeypatch.delenv(k, raising=False)
         return out, name
 
+    want_ws, want_shrunk, want_old = WS_RUNS[WS_CASES.index(case)]
     out, name = run(True)
-    assert name.startswith("pwconv_ws_kernel"), name
+    assert name == (want_shrunk if shrink else want_ws), name
     old, old_name = run(False)
-    assert not old_name.startswith("pwconv_ws_kernel"), old_name
+    assert old_name == want_old, old_name
     scale = max(1.0, float(ref.abs().max()))
     assert_close(_from_cl(out, cout), ref, 3e-2 * scale, 2e-2, f"ws conv {case}")
+    assert_close(_from_cl(old, cout), ref, 3e-2 * scale, 2e-2, f"{old_name} {case}")
+    if old.shape[-1] > cout:
+        assert float(old[..., cout:].float().abs().max()) == 0.0, f"{old_name}: padded channels must stay zero"
     if "xtile" in old_name:  # identical arithmetic: the k order of the MFMA chain and the fp32 epilogue are the same
         assert torch.equal(out, old), f"ws vs {old_name}: max diff {float((out.float() - old.float()).abs().max())}"
     else:
