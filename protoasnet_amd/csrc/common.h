@@ -18,6 +18,12 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
+}  // namespace pasn
+
+#include "lds_dma.h"  // LDS pointer / small vector types, buffer_rsrc, BUF_OOB, lds_barrier, wait_vmcnt_all_but, bf16_bits
+
+namespace pasn {
+
 // ---- host-side error plumbing -------------------------------------------------------------------
 void set_error(const std::string& msg);
 int check_launch(const char* what);

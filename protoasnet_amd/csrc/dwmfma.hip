@@ -39,11 +39,6 @@
 
 namespace pasn {
 
-typedef __attribute__((ext_vector_type(4))) unsigned dwm_u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned dwm_u32x2;
-typedef __attribute__((address_space(3))) void* dwm_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* dwm_gbl_ptr_t;
-
 constexpr int DWF_NTL = 7;      // position tiles per wave (7 x 14 outputs: the X3D planes are 56 / 28 / 14 / 7 high)
 constexpr int DWF_RING = 2;      // frame images in LDS: frame t + RING - 1 is requested right after the barrier of frame t (3: measured 4-5 % slower)
 // two-row tiles (planes <= 8 wide): 4 x 2 rows, the LDS image stays <= 25 KB; stride 2: 3 rows of 14 outputs = 7 x 29 staged positions
@@ -59,43 +54,6 @@ constexpr int dwf_rows(int rpt, int ss) { return (dwf_tiles(rpt, ss) * rpt - 1) 
 // of a read cover the 64 banks exactly -- provided the lanes without a position read a cell another lane reads.  One-row tiles are unaffected.
 constexpr int dwf_rowp(int ss) { return dwf_pitch(ss) * dwf_slots(ss) + (ss == 1 ? 6 : 0); }
 constexpr int dwf_ni(int rpt, int ss) { return (dwf_rows(rpt, ss) * dwf_rowp(ss) + 63) / 64; }  // 1-KiB DMA instructions per frame
-
-__device__ __forceinline__ unsigned bf16_bits_rne(float f) {
-    const __bf16 b = (__bf16)f;
-    return (unsigned)__builtin_bit_cast(unsigned short, b);
-}
-
-__device__ __forceinline__ void dwf_wait_all_but(int n) {  // n wave-uniform: everything but this wave's n most recent vector-memory ops is done
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 17: asm volatile("s_waitcnt vmcnt(17)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-        case 19: asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); break;
-        case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;  // n <= (DWF_RING - 1) * DWF_NTL + (DWF_RING - 2) * DWF_NE = 21
-    }
-}
-
-// Barrier of the frame loop WITHOUT the fence of __syncthreads(): that fence is `s_waitcnt vmcnt(0)`, which drains the DMA groups of the
-// next frames (and the output stores) at every frame and serialises the ring.  Here only LDS traffic is drained; what must have landed
-// from memory is waited for by count (dwf_wait_all_but) just before.
-__device__ __forceinline__ void dwf_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ACT: the epilogue activation compiled in (none / Swish: what X3D uses), -1 = the descriptor's.
 // STATS (training forward): `pool` receives [N][chunks][2][Cp] = (sum, sum of squares) of the raw outputs per (clip, chunk) -- the batch
@@ -120,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
 
     // ---- block-diagonal weight operands A[kt][pair]: lane (m, q) holds k = 8q .. 8q+7 = tap (q >> 1) of the pair, channels 8 (q & 1) ..;
     // only element (m & 7) can be nonzero, and only when m's half matches
-    dwm_u32x4 A[3][5];
+    u32x4 A[3][5];
     {
         const int c = c0 + m;
         const bool mine = ((m >> 3) == (q & 1)) && c < Cp;
@@ -137,8 +95,8 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
                 const bool live = mine && 2 * j + (q >> 1) < 9;
-                const unsigned bits = live ? (bf16_bits_rne(wv[kt][j]) << sh) : 0u;
-                A[kt][j] = dwm_u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
+                const unsigned bits = live ? (bf16_bits(wv[kt][j]) << sh) : 0u;
+                A[kt][j] = u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
             }
     }
     // epilogue constants of this lane's 4 output channels c0 + 4q + i
@@ -167,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
     const unsigned fr_in_bytes = (unsigned)(fstride * 2);
     // this clip from the quad's first channel on; the last bytes of the clip's last row belong to the quad's own channels or lie beyond
     // num_records (channels of LATER quads sit below offset fr_in_bytes * Ti - cq * 128: reading them as "padding slots" is harmless)
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(xclip), 0, (unsigned)Ti * fr_in_bytes - (unsigned)(cq * 128), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(xclip, (unsigned)Ti * fr_in_bytes - (unsigned)(cq * 128));
     constexpr int NT = dwf_tiles(RPT, SS);  // position tiles per wave
     const int abl = ABLB ? g.abl : 0;   // timing ablations: a separate instance, the product kernel carries none of the checks
     constexpr int RW = dwf_pitch(SS);  // staged positions per region row ((BW - 1) SS + 3 <= RW used)
@@ -208,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
             const int cc = rem / SLOTS, c = rem - cc * SLOTS;
             const int hi = h0 * SS - 1 + rr, wi = w0 * SS - 1 + cc;
             const bool ok = !(abl & 16) && wave + 4 * e < NI && rr * RW < g.RP && cc < (g.BW - 1) * SS + 3 && c < npieces && hi >= 0 && hi < Hi && wi >= 0 && wi < Wi;
-            goff[e] = ok ? (unsigned)(((hi * Wi + wi) * Cp + c * 8) * 2) : 0x80000000u;
+            goff[e] = ok ? (unsigned)(((hi * Wi + wi) * Cp + c * 8) * 2) : BUF_OOB;
         }
         const int kdma = max(0, (NI - wave + 3) >> 2);  // DMA instructions of this wave per frame (i = wave + 4e < NI)
         auto staged = [&](int ti) -> bool { return ti >= 0 && ti < Ti && ti >= t0 - 1 && ti <= t1; };
@@ -219,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
 #pragma unroll
             for (int e = 0; e < NE; ++e)
                 if (wave + 4 * e < NI)  // wave-uniform
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (dwm_lds_ptr_t)(dst + (wave + 4 * e) * 1024), 16, (int)goff[e], (int)foff, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(dst + (wave + 4 * e) * 1024), 16, (int)goff[e], (int)foff, 0, 0);
         };
         // ---- fragment roles: position tile l holds RPT whole output rows of the region (rows l RPT ..), lane m -> (row m / BW, column
         // m % BW): every per-tile address is the tile-0 address plus a wave-uniform multiple of l
@@ -239,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
         // juggling or 64-bit address arithmetic in the epilogue, and every tile's store is ISSUED, so the wave can count them: vmcnt retires
         // in issue order, the wait for a frame's DMA group must name every younger DMA and store (otherwise it waits for the previous
         // frame's stores to be acknowledged: ~1.5 us per frame, the whole step serialised)
-        const unsigned yvoff = lane_ok ? (unsigned)((((h0 + mrow) * d.Wo + w0 + mcol) * Cp + ce) * 2) : 0x80000000u;
+        const unsigned yvoff = lane_ok ? (unsigned)((((h0 + mrow) * d.Wo + w0 + mcol) * Cp + ce) * 2) : BUF_OOB;
         const unsigned fr_bytes = (unsigned)(ofs * 2);
         const int kst = wave_live ? NT : 0;  // stores per emitted frame: one per tile, whether or not its rows exist
 
@@ -317,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
                 // the vmcnt wait: 7 ds_write + 7 ds_read + the second pass cost more than the partial lines.)
                 int mr = mrow_lim;
                 asm volatile("" : "+v"(mr));
-                const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(yclip + (long)to * ofs, 0, fr_bytes, 0x00020000);
+                const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(yclip + (long)to * ofs, fr_bytes);
                 // Straight-line over ALL tiles (no per-tile branch: a tile below the plane stores out of the descriptor's range and counts
                 // nothing; the pool sums are formed whether or not the launch has a row to write them to; the padded channels carry zero
                 // scale and bias instead of a tail mask) -- with three wave-uniform branches per tile every tile's epilogue was its own
@@ -353,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
                         bf16x4 o;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) o[i] = (__bf16)v[i];
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(dwm_u32x2, o), yrsrc, (int)yvoff, l * ystep * 2, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), yrsrc, (int)yvoff, l * ystep * 2, 0);
                     }
             }
         };
@@ -367,8 +325,8 @@ __global__ __launch_bounds__(256, 2) void dwconv3d_mfma_kernel(const __bf16* __r
                 int younger = stored(ti - LA - 1);
 #pragma unroll
                 for (int j = 1; j < LA; ++j) younger += (staged(ti + j) && !(abl & 2) ? kdma : 0) + stored(ti - LA - 1 + j);
-                dwf_wait_all_but(younger);
-                dwf_barrier();
+                wait_vmcnt_all_but<21>(younger);  // younger <= (DWF_RING - 1) * DWF_NTL + (DWF_RING - 2) * DWF_NE = 21
+                lds_barrier();
             }
             issue(ti + LA, slot + LA >= DWF_RING ? slot + LA - DWF_RING : slot + LA);  // that image was last read in step ti-1: everyone is past it
             frame(ti, slot, P, C, N);

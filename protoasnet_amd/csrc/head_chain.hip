@@ -23,8 +23,6 @@
 
 namespace pasn {
 
-typedef __attribute__((address_space(3))) void* hc_lds_ptr_t;
-
 // Tile geometry per instance: KS1 = k-steps of the trunk channels, ROWS = staged positions per tile (a whole number of 8-position pieces).
 //   <12, 104>: trunk stride <= 192 (X3D): x 41.6 KB | f1 / o1 / occ^T 54.9 KB | f^T 61.4 KB = 158 KB; 104 rows = 3.25 sub-tiles of 32 (S = 784 -> 8
 //              tiles of 98 per clip = one block per CU at 32 clips)
@@ -43,7 +41,6 @@ struct HcGeom {
     static constexpr int LDS = XR_BYTES + B1_BYTES + B2_BYTES;
     static_assert(ROWS % 8 == 0 && XR_BYTES >= ROWS * O2S * 16 && B1_BYTES >= 64 * TS * 16 && LDS <= 160 * 1024, "regions must fit");
 };
-constexpr unsigned HC_OOB = 0x80000000u;
 
 struct HcArgs {
     const __bf16 *x, *w1, *w2, *w3, *w4, *w5;  // fragment-major weights: add_on 0 / 2, occurrence_module 0 / 2 / 4
@@ -51,8 +48,6 @@ struct HcArgs {
     float *slabs, *occ;
     int N, S, Cbp, nks1, P, G, R, full;
 };
-
-__device__ __forceinline__ void hc_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // fragments K0 .. K1 - 1 of channel tile ct (whole-K fragment-major rows of nks steps); steps beyond nks are zero fragments
 template <int KS, int K0 = 0, int K1 = KS>
@@ -156,14 +151,14 @@ __global__ __launch_bounds__(512) void xproto_chain_kernel(HcArgs a) {
     const bool full = a.full != 0;
 
     {  // x tile by LDS-DMA: slot s of the image = (row s / XS, piece s % XS); pieces beyond the channels / rows beyond the tile arrive as zeros
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.x), 0, (unsigned)a.N * (unsigned)a.S * (unsigned)a.Cbp * 2u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(a.x, (unsigned)a.N * (unsigned)a.S * (unsigned)a.Cbp * 2u);
         const int ppr = a.Cbp >> 3;
         constexpr int nix = (HC_ROWS * HC_XS + 63) / 64;  // the last instruction may spill zero slots into B1 (written later)
         for (int j = wave; j < nix; j += 8) {
             const int s = j * 64 + lane;
             const int r = s / HC_XS, p = s - r * HC_XS;
-            const unsigned off = (r < valid && p < ppr) ? (m0 + (unsigned)r) * (unsigned)a.Cbp * 2u + (unsigned)p * 16u : HC_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (hc_lds_ptr_t)(XR + j * 1024), 16, (int)off, 0, 0, 0);
+            const unsigned off = (r < valid && p < ppr) ? (m0 + (unsigned)r) * (unsigned)a.Cbp * 2u + (unsigned)p * 16u : BUF_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(XR + j * 1024), 16, (int)off, 0, 0, 0);
         }
     }
     int rows4[NST];
@@ -176,7 +171,7 @@ __global__ __launch_bounds__(512) void xproto_chain_kernel(HcArgs a) {
         bf16x8 W1[HC_KS1];
         hc_load_w<HC_KS1>(W1, a.w1, wave, a.nks1, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        hc_barrier();
+        lds_barrier();
         // (half of the next stage's weight fragments are requested BEFORE this stage's MFMAs, the rest behind them: all of them up front
         // does not fit the registers -- 19 spilled, 28.8 us -- and all of them behind leaves an L2 round trip per stage exposed)
         // ---- c1: x -> f1 = relu(.), rows of B1 ----
@@ -185,18 +180,18 @@ __global__ __launch_bounds__(512) void xproto_chain_kernel(HcArgs a) {
         hc_mma<HC_KS1, NST, false>(acc, W1, XR, HC_XS, rows4, h);
         hc_load_w<16, 8, 16>(W2, a.w2, wave, 16, lane);
         hc_epi_rows<NST, HC_ROWS>(acc, a.b1, wave, 0, B1, HC_B1S, c, h);
-        hc_barrier();
+        lds_barrier();
         // ---- c2: f1 -> f^T (no activation), B2 ----
         hc_load_w<HC_KS1, 0, 6>(W3, a.w3, wave, a.nks1, lane);
         const float bias2 = a.b2[wave * 32 + c];
         hc_mma<16, NST, true>(acc, W2, B1, HC_B1S, rows4, h);
         hc_load_w<HC_KS1, 6, HC_KS1>(W3, a.w3, wave, a.nks1, lane);
         hc_epi_cols<NST, false, HC_PIECES, HC_TS>(acc, bias2, wave, 0, B2, HC_ROWS, c, h);
-        hc_barrier();  // everyone is past its reads of f1
+        lds_barrier();  // everyone is past its reads of f1
     } else {
         hc_load_w<HC_KS1>(W3, a.w3, wave, a.nks1, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        hc_barrier();
+        lds_barrier();
     }
     // ---- c3: x -> o1 = relu(.), rows of B1 ----
     const int ct4 = wave & 3, sp4 = wave >> 2;
@@ -205,7 +200,7 @@ __global__ __launch_bounds__(512) void xproto_chain_kernel(HcArgs a) {
     hc_mma<HC_KS1, NST, false>(acc, W3, XR, HC_XS, rows4, h);
     hc_load_w<16, 8, 16>(W4, a.w4, ct4, 16, lane);
     hc_epi_rows<NST, HC_ROWS>(acc, a.b3, wave, 0, B1, HC_B1S, c, h);
-    hc_barrier();  // o1 complete; everyone is past its reads of the x tile
+    lds_barrier();  // o1 complete; everyone is past its reads of the x tile
     // ---- c4: o1 -> o2 = relu(.), rows of XR: wave = (channel tile, half of the positions) ----
     {
         f32x16 acc2[2];
@@ -215,14 +210,14 @@ __global__ __launch_bounds__(512) void xproto_chain_kernel(HcArgs a) {
         hc_load_w<8>(W5, a.w5, pt5, 8, lane);
         hc_mma<16, 2, false>(acc2, W4, B1, HC_B1S, rows2, h);
         hc_epi_rows<2, HC_ROWS>(acc2, a.b4, ct4, 2 * sp4, XR, HC_O2S, c, h);
-        hc_barrier();  // o2 complete; everyone is past its reads of o1
+        lds_barrier();  // o2 complete; everyone is past its reads of o1
         // ---- c5: o2 -> occ^T = |.|, rows of B1: wave = (prototype tile, 32-position sub-tile) ----
         f32x16 acc1[1];
         const int rows1[1] = {min(32 * st5 + c, HC_ROWS - 1)};
         hc_mma<8, 1, true>(acc1, W5, XR, HC_O2S, rows1, h);
         hc_epi_cols<1, true, HC_PIECES, HC_TS>(acc1, 0.0f, pt5, st5, B1, valid, c, h);
     }
-    hc_barrier();
+    lds_barrier();
     // ---- occurrence map rows of this tile: occ[n][p][s0 + s] (fp32 of the bf16 map, as the separate launches store it) ----
     for (int idx = threadIdx.x; idx < a.P * valid; idx += 512) {
         const int p = idx / valid, s = idx - p * valid;
@@ -245,8 +240,7 @@ __global__ __launch_bounds__(512) void xproto_chain_kernel(HcArgs a) {
         bf16x8 o0 = *reinterpret_cast<const bf16x8*>(B1 + (c * HC_TS + slot) * 16);
         bf16x8 o1 = *reinterpret_cast<const bf16x8*>(B1 + ((32 + c) * HC_TS + slot) * 16);
         if (2 * ks + 1 >= HC_PIECES) {
-            typedef unsigned hc_u32x4 __attribute__((ext_vector_type(4)));
-            hc_u32x4 z = {0u, 0u, 0u, 0u};
+            u32x4 z = {0u, 0u, 0u, 0u};
             fb = dead ? __builtin_bit_cast(bf16x8, z) : fb;
             o0 = dead ? __builtin_bit_cast(bf16x8, z) : o0;
             o1 = dead ? __builtin_bit_cast(bf16x8, z) : o1;

@@ -22,10 +22,6 @@
 
 namespace pasn {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-
 constexpr int IG_BK = 32;
 
 // NT channel tiles x MT position tiles (of 32) per WAVE; the block is 4 waves along the positions: BM = 128 * MT, BN = 32 * NT.
@@ -97,10 +93,9 @@ __global__ __launch_bounds__(256, 2) void igemm_glds_kernel(const __bf16* __rest
         f_de = r2 - f_db * d.kw;
     }
     // descriptors over the whole activation / weight tensors (igemm_nt guarantees both below 2^31 elements: 32-bit byte offsets)
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<__bf16*>(x), 0, (unsigned)min((long)d.N * d.Ti * d.Hi * d.Wi * Cin_p * 2, 0xffffffe0L), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(x, (unsigned)min((long)d.N * d.Ti * d.Hi * d.Wi * Cin_p * 2, 0xffffffe0L));
     const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(w), 0, (unsigned)min((long)d.w_rows * Ktot * 2, 0xffffffe0L), 0x00020000);
+        buffer_rsrc(w, (unsigned)min((long)d.w_rows * Ktot * 2, 0xffffffe0L));
 
     auto issue = [&](int kt, int buf) {  // called with kt = 0, 1, 2, ... in order
         char* xb = smem + buf * STAGE;
@@ -190,7 +185,6 @@ __global__ __launch_bounds__(256, 2) void igemm_glds_kernel(const __bf16* __rest
     // profiles/README entries 92 / 94; the MFMA stems still use it)
     igemm_epilogue_direct<NT, MT>(acc, scb, res, y, n0, cgs, d, lane, tile_rows);
 }
-
 
 // Instance for this layer: NT channel tiles per block in the low decimal digit, MT position tiles per wave in the next; 0 = not this kernel.
 int igemm_nt(const pasn_conv_desc& d, int dtype) {

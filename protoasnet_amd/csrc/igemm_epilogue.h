@@ -127,10 +127,6 @@ __device__ __forceinline__ void igemm_epilogue_body(const f32x16 (&acc)[NT][MT],
 // piece and reused for the MT position tiles), residual (16-byte loads, all of a channel tile's requested before any is used),
 // activation, one 16-byte store per piece.  Per tile a buffer descriptor over exactly its valid rows: rows beyond them fall out of
 // range (loads return zero, stores are dropped), channel pieces beyond the block's width carry an out-of-range offset.
-typedef __attribute__((ext_vector_type(4))) unsigned ige_u32x4;
-typedef __attribute__((ext_vector_type(2))) float ige_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 ige_bf16x2;
-typedef __attribute__((ext_vector_type(2))) short ige_s16x2;
 
 template <int NT, int MT, bool HAS_RES, int ACT, typename Rows>
 __device__ __forceinline__ void igemm_epilogue_direct_body(const f32x16 (&acc)[NT][MT], const float* scb, const __bf16* __restrict__ res,
@@ -146,8 +142,8 @@ __device__ __forceinline__ void igemm_epilogue_direct_body(const f32x16 (&acc)[N
         int nvalid;
         rows(j, mbase, nvalid);
         const unsigned bytes = nvalid > 0 ? (unsigned)(((nvalid - 1) * Cout_p + width) * 2) : 0u;
-        yr[j] = __builtin_amdgcn_make_buffer_rsrc(y + mbase * Cout_p + n0, 0, bytes, 0x00020000);
-        rr[j] = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(HAS_RES ? res + mbase * Cout_p + n0 : y), 0, HAS_RES ? bytes : 0u, 0x00020000);
+        yr[j] = buffer_rsrc(y + mbase * Cout_p + n0, bytes);
+        rr[j] = buffer_rsrc(HAS_RES ? res + mbase * Cout_p + n0 : y, HAS_RES ? bytes : 0u);
     }
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
@@ -155,7 +151,7 @@ __device__ __forceinline__ void igemm_epilogue_direct_body(const f32x16 (&acc)[N
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
             const int col = i * 32 + 16 * pr + 8 * h;
-            off[pr] = col < width ? (unsigned)((c * Cout_p + col) * 2) : 0x80000000u;
+            off[pr] = col < width ? (unsigned)((c * Cout_p + col) * 2) : BUF_OOB;
         }
         if constexpr (!HAS_RES && (ACT == PASN_ACT_RELU || ACT == PASN_ACT_NONE)) {
             // No residual, ReLU or nothing: scale / bias on the accumulator rows as they are, then bf16 rounding and ReLU on PACKED pairs
@@ -178,9 +174,9 @@ __device__ __forceinline__ void igemm_epilogue_direct_body(const f32x16 (&acc)[N
                 unsigned P[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const ige_f32x2 a = {acc[i][j][2 * k] * scr[2 * k] + bsr[2 * k], acc[i][j][2 * k + 1] * scr[2 * k + 1] + bsr[2 * k + 1]};
-                    ige_s16x2 m = __builtin_bit_cast(ige_s16x2, __builtin_convertvector(a, ige_bf16x2));
-                    if constexpr (ACT == PASN_ACT_RELU) m = __builtin_elementwise_max(m, ige_s16x2{0, 0});
+                    const f32x2 a = {acc[i][j][2 * k] * scr[2 * k] + bsr[2 * k], acc[i][j][2 * k + 1] * scr[2 * k + 1] + bsr[2 * k + 1]};
+                    s16x2 m = __builtin_bit_cast(s16x2, __builtin_convertvector(a, bf16x2));
+                    if constexpr (ACT == PASN_ACT_RELU) m = __builtin_elementwise_max(m, s16x2{0, 0});
                     P[k] = __builtin_bit_cast(unsigned, m);
                 }
 #pragma unroll
@@ -189,7 +185,7 @@ __device__ __forceinline__ void igemm_epilogue_direct_body(const f32x16 (&acc)[N
                     // 16 pr .. + 7 and lanes >= 32 channels 16 pr + 8 .. + 15 of their position
                     const auto s0 = __builtin_amdgcn_permlane32_swap(P[4 * pr + 0], P[4 * pr + 2], false, false);
                     const auto s1 = __builtin_amdgcn_permlane32_swap(P[4 * pr + 1], P[4 * pr + 3], false, false);
-                    ige_u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+                    u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
                     if (ragged) {  // wave-uniform: zero the channels at or beyond the real count (element e = channel col + e)
                         const int nvalid = d.Cout - (n0 + i * 32 + 16 * pr + 8 * h);
 #pragma unroll
@@ -234,7 +230,7 @@ __device__ __forceinline__ void igemm_epilogue_direct_body(const f32x16 (&acc)[N
                 bf16x8 o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ige_u32x4, o), yr[j], (int)off[pr], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yr[j], (int)off[pr], 0, 0);
             }
         }
     }

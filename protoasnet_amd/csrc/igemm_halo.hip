@@ -23,10 +23,6 @@
 
 namespace pasn {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-
 constexpr int HG_MAX = 8;  // 16-row DMA groups of the halo tile per wave (tile <= 512 rows)
 
 // SP (MODE 1 only): SLICE-granular pipeline.  The per-tap schedule below gives a (3,1,1) conv steps of 8 MFMAs between barriers, and because
@@ -106,8 +102,8 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const __bf16* __rest
         wdst[i] = g < WGROUPS ? g * 1024 : -1;  // -1: this wave has no i-th group
     }
     // descriptors over the whole activation / weight tensors (the host guarantees both below 2^31 elements: 32-bit byte offsets)
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(x), 0, (unsigned)min((long)M * Cin_p * 2, 0xffffffe0L), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(w), 0, (unsigned)min((long)d.w_rows * taps * kc * 2, 0xffffffe0L), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(x, (unsigned)min((long)M * Cin_p * 2, 0xffffffe0L));
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(w, (unsigned)min((long)d.w_rows * taps * kc * 2, 0xffffffe0L));
 
     auto issue_a = [&](int cs, int i) -> int {  // this wave's i-th halo group of slice cs into stage cs & 1; returns the DMAs issued
         char* xb = smem + (cs & 1) * XBYTES;
@@ -137,17 +133,6 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const __bf16* __rest
             }
         }
         return n;
-    };
-    auto wait_all_but = [&](int n) {  // n wave-uniform: everything but the n most recent DMAs of this wave has landed
-        switch (n) {
-            case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-            case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-            case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-            case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-            case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-            case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-            default: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;  // stricter than needed for n > 6, never weaker
-        }
     };
 
     // ---- fragment roles ----
@@ -257,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const __bf16* __rest
 #pragma unroll
             for (int tp = 0; tp < 3; ++tp) mma_step(cs, tp, tp, 0, set + tp);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            lds_barrier();
         }
     } else {
     for (int i = 0; i < per_wave; ++i) issue_a(0, i);
@@ -291,10 +276,9 @@ __global__ __launch_bounds__(256, 2) void igemm_halo_kernel(const __bf16* __rest
                 mma_step(cs, tap, tb, te, stage);
                 // the DMAs of steps < s have landed (in-order completion), i.e. the weight tile of step s + 1 and, after the last tap (which
                 // issues no halo group), the whole halo tile of slice cs + 1
-                wait_all_but(issued);
-                // barrier WITHOUT the fence of __syncthreads(): that fence is `s_waitcnt vmcnt(0)` and drained the DMAs just issued for step
-                // s + 2 / slice cs + 1 at every step (pipeline depth 1 instead of 2); only LDS traffic is drained here
-                if (!(ABL & 4)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // everyone's have; nobody still reads this step's weight stage
+                wait_vmcnt_all_but<6>(issued);  // issued <= PA + WD <= 6
+                // (__syncthreads() here drained the DMAs just issued for step s + 2 / slice cs + 1 at every step: pipeline depth 1 instead of 2)
+                if (!(ABL & 4)) lds_barrier();  // everyone's have; nobody still reads this step's weight stage
                 stage = stage == 2 ? 0 : stage + 1;
             }
     }

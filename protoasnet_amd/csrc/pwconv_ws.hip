@@ -25,24 +25,7 @@
 
 namespace pasn {
 
-typedef __attribute__((address_space(3))) void* ws_lds_ptr_t;
-typedef __attribute__((ext_vector_type(4))) unsigned ws_u32x4;
-
-constexpr unsigned WS_OOB = 0x80000000u;  // per-lane offset tag: beyond every num_records (all of them < 2^30)
-
-__device__ __forceinline__ void ws_wait_all_but(int n) {  // n wave-uniform: all but this wave's n most recent vector-memory ops are done
-    switch (n) {
-#define WS_W(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        WS_W(0) WS_W(1) WS_W(2) WS_W(3) WS_W(4) WS_W(5) WS_W(6) WS_W(7) WS_W(8) WS_W(9) WS_W(10) WS_W(11) WS_W(12) WS_W(13) WS_W(14) WS_W(15)
-        WS_W(16) WS_W(17) WS_W(18) WS_W(19) WS_W(20) WS_W(21) WS_W(22) WS_W(23) WS_W(24) WS_W(25) WS_W(26) WS_W(27) WS_W(28) WS_W(29) WS_W(30)
-        WS_W(31) WS_W(32) WS_W(33) WS_W(34) WS_W(35) WS_W(36) WS_W(37) WS_W(38) WS_W(39) WS_W(40) WS_W(41) WS_W(42) WS_W(43) WS_W(44) WS_W(45)
-        WS_W(46) WS_W(47) WS_W(48) WS_W(49) WS_W(50) WS_W(51) WS_W(52) WS_W(53) WS_W(54) WS_W(55) WS_W(56) WS_W(57) WS_W(58) WS_W(59) WS_W(60)
-#undef WS_W
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // stricter than needed, never weaker (launch_pw_ws keeps n <= 60)
-    }
-}
-// barrier WITHOUT the fence of __syncthreads() (that fence is `s_waitcnt vmcnt(0)`: it would drain the DMA groups in flight)
-__device__ __forceinline__ void ws_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (counted waits: launch_pw_ws keeps n <= 60 = the largest immediate wait_vmcnt_all_but<60> holds)
 
 // KS2 > 0: CHAINED PAIR (an X3D block's project conv and the next block's expand conv): after the first conv's epilogue the finished
 // block-output tile goes to HBM AND, as bf16, into an LDS tile; behind one more barrier every wave w < ctiles2 computes channel tile w of the
@@ -83,15 +66,15 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
     constexpr int abl = 0;  // (as a run-time value its tests sat in front of every store and DMA group of the product kernel)
 #endif
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(x), 0, row1 * xrow, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(y, 0, row1 * yrow, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(RES ? res : x), 0, RES ? row1 * yrow : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(x, row1 * xrow);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(y, row1 * yrow);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(RES ? res : x, RES ? row1 * yrow : 0u);
     const bool has_gate = XF && gate != nullptr;
     // squeeze-excite gate computed HERE (se.pool != NULL) from the stencil's pool partial rows: the stand-alone gate launch between the
     // stencil and this conv, and its two kernel boundaries, are gone.  A block's rows touch at most two clips (host: rpb <= S)
     const bool se_on = XF && se.pool != nullptr;
     const unsigned n_first = row0 / (unsigned)S;
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(has_gate ? gate : scale), 0, has_gate ? (unsigned)N * (unsigned)Cin_p * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t grsrc = buffer_rsrc(has_gate ? gate : scale, has_gate ? (unsigned)N * (unsigned)Cin_p * 4u : 0u);
 
     // ---- stationary weights: fragment-major (tile ct, step ks) = 64 lanes x 16 bytes; steps beyond w_kc are zeroed below ---------
     bf16x8 A[KS];
@@ -116,17 +99,17 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
         }
         if (scale) load8(scale + chc, sc[pr]);
         if (bias) load8(bias + chc, bs[pr]);
-        yoff[pr] = ok ? (unsigned)(pt * MT * 32 + c) * yrow + (unsigned)ch * 2u : WS_OOB;
+        yoff[pr] = ok ? (unsigned)(pt * MT * 32 + c) * yrow + (unsigned)ch * 2u : BUF_OOB;
     }
     const bool tail = live && ct * 32 + 32 > Cout;  // wave-uniform: this tile holds channels beyond the real count (stored as zeros)
     // ---- pair mode: the second conv's stationary weights and epilogue constants (channel tile = wave) ----------------------------------
     const int ctiles2 = KS2 ? (pr2.Cout2_p + 31) >> 5 : 0;
     const bool live2 = KS2 && wave < ctiles2;
     const unsigned y2row = KS2 ? (unsigned)pr2.Cout2_p * 2u : 0u;
-    const __amdgpu_buffer_rsrc_t y2rsrc = __builtin_amdgcn_make_buffer_rsrc(KS2 ? pr2.y2 : y, 0, KS2 ? row1 * y2row : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t y2rsrc = buffer_rsrc(KS2 ? pr2.y2 : y, KS2 ? row1 * y2row : 0u);
     bf16x8 A2[KS2 ? KS2 : 1];
     float sc2[KS2 ? 2 : 1][8], bs2[KS2 ? 2 : 1][8];
-    unsigned y2off[2] = {WS_OOB, WS_OOB};
+    unsigned y2off[2] = {BUF_OOB, BUF_OOB};
     char* const y1t = smem + NS * g.stage_bytes;  // [BM][Y1PL] slots: the first conv's output tile as the second conv's operand
     if (KS2) {
         const int c2 = live2 ? wave : ctiles2 - 1;
@@ -145,7 +128,7 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
             }
             if (pr2.scale2) load8(pr2.scale2 + chc, sc2[pr]);
             if (pr2.bias2) load8(pr2.bias2 + chc, bs2[pr]);
-            y2off[pr] = ok ? (unsigned)c * y2row + (unsigned)ch * 2u : WS_OOB;
+            y2off[pr] = ok ? (unsigned)c * y2row + (unsigned)ch * 2u : BUF_OOB;
         }
         // the handed-over tile's pad slot and the k columns beyond the first conv's channels stay zero: cleared once, never written
         for (int i = threadIdx.x; i < BM * Y1PL; i += NW * 64) reinterpret_cast<uint4*>(y1t)[i] = uint4{0u, 0u, 0u, 0u};
@@ -166,24 +149,24 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
         for (int j = wave; j < nix; j += NW) {
             const int s = j * 64 + lane;
             const int r = s / PPRL, p = s - r * PPRL;  // compile-time divisor
-            const unsigned off = (r < BM && p < PPR) ? (m0 + (unsigned)r) * xrow + (unsigned)p * 16u : WS_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (ws_lds_ptr_t)(sb + j * 1024), 16, (int)off, 0, 0, 0);
+            const unsigned off = (r < BM && p < PPR) ? (m0 + (unsigned)r) * xrow + (unsigned)p * 16u : BUF_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(sb + j * 1024), 16, (int)off, 0, 0, 0);
         }
         if (XF) {
             const unsigned n0 = m0 / (unsigned)S;
             for (int j = wave; j < nig; j += NW) {
                 const int s = j * 64 + lane;
                 const int r = s / GPR, p = s - r * GPR;
-                const unsigned off = (r < 2 && p * 4 < Cin_p) ? (n0 + (unsigned)r) * (unsigned)Cin_p * 4u + (unsigned)p * 16u : WS_OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(grsrc, (ws_lds_ptr_t)(sb + g.xreg + j * 1024), 16, (int)off, 0, 0, 0);
+                const unsigned off = (r < 2 && p * 4 < Cin_p) ? (n0 + (unsigned)r) * (unsigned)Cin_p * 4u + (unsigned)p * 16u : BUF_OOB;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(grsrc, (lds_ptr_t)(sb + g.xreg + j * 1024), 16, (int)off, 0, 0, 0);
             }
         }
         if (RES) {
             for (int j = wave; j < nir; j += NW) {
                 const int s = j * 64 + lane;
                 const int r = (int)(((float)s + 0.5f) * rpl_inv), p = s - r * RPL;  // exact: s < 2^16
-                const unsigned off = (r < BM && p * 8 < Cout_p) ? (m0 + (unsigned)r) * yrow + (unsigned)p * 16u : WS_OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rrsrc, (ws_lds_ptr_t)(sb + g.xreg + g.greg + j * 1024), 16, (int)off, 0, 0, 0);
+                const unsigned off = (r < BM && p * 8 < Cout_p) ? (m0 + (unsigned)r) * yrow + (unsigned)p * 16u : BUF_OOB;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rrsrc, (lds_ptr_t)(sb + g.xreg + g.greg + j * 1024), 16, (int)off, 0, 0, 0);
             }
         }
     };
@@ -285,7 +268,7 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
                 if (ncl > 1) mean[Cin_p + tid] = sum1 * se.inv_positions;
             }
         }
-        ws_barrier();
+        lds_barrier();
         for (int q = 0; q < ncl; ++q) {
             float sacc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -304,7 +287,7 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
                 if (lane == 0 && j < cse) hid[q * cse + j] = fmaxf(t + b1r[u], 0.0f);
             }
         }
-        ws_barrier();
+        lds_barrier();
         for (int q = 0; q < ncl; ++q) {
             float gv = 0.0f;
             if (tid < C) {
@@ -321,8 +304,8 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
         }
     }
     if (XF && nt > 0) {  // tile 0 is transformed here; tile i + 1 during iteration i, beside the MFMAs and the epilogue of tile i (host: NS = 3)
-        ws_wait_all_but(min(LA - 1, nt - 1) * kgrp);
-        ws_barrier();
+        wait_vmcnt_all_but<60>(min(LA - 1, nt - 1) * kgrp);
+        lds_barrier();
         transform(0, 0);
     }
 
@@ -334,14 +317,14 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
             // the pieces of tile i + 1 (transformed in this iteration) have landed: this wave has since issued only the stores of tile i - 1
             // (iteration 0: nothing, the prologue ended with the group of tile 1).  Behind the barrier everyone's have, tile i is
             // transformed by everyone, and nobody still reads the stage of tile i - 1, which takes tile i + 2.
-            if (i + 1 < nt) ws_wait_all_but(i > 0 ? kst : 0);
-            ws_barrier();
+            if (i + 1 < nt) wait_vmcnt_all_but<60>(i > 0 ? kst : 0);
+            lds_barrier();
             if (i + 2 < nt) issue(i + 2, nxt + 1 == NS ? 0 : nxt + 1);
         } else {
             // this wave's pieces of tile i have landed: everything it issued since is the groups of the look-ahead tiles and the stores of
             // the last min(i, LA) tiles; then everyone's have, and nobody still reads the stage of tile i - 1, which takes tile i + LA
-            ws_wait_all_but(min(LA - 1, nt - 1 - i) * kgrp + min(i, LA) * kst);
-            ws_barrier();
+            wait_vmcnt_all_but<60>(min(LA - 1, nt - 1 - i) * kgrp + min(i, LA) * kst);
+            lds_barrier();
             if (i + LA < nt) issue(i + LA, stg + LA >= NS ? stg + LA - NS : stg + LA);
         }
         char* sb = smem + stg * g.stage_bytes;
@@ -393,14 +376,14 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
                     if (!(abl & 2))
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ws_u32x4, o), yrsrc, (int)(yoff[pr] + (m0 + (unsigned)(mt * 32)) * yrow), 0, 0);
-                    if (KS2 && yoff[pr] != WS_OOB)  // the same 8 channels of this position, as the second conv's operand
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, (int)(yoff[pr] + (m0 + (unsigned)(mt * 32)) * yrow), 0, 0);
+                    if (KS2 && yoff[pr] != BUF_OOB)  // the same 8 channels of this position, as the second conv's operand
                         *reinterpret_cast<bf16x8*>(y1t + ((pt * 32 + c) * Y1PL + ct * 4 + 2 * pr + h) * 16) = o;
                 }
             }
         }
         if (KS2) {
-            ws_barrier();  // the block-output tile is complete (and every wave is past its reads of the X tile)
+            lds_barrier();  // the block-output tile is complete (and every wave is past its reads of the X tile)
             if (live2) {
                 f32x16 acc2[MT2];
 #pragma unroll
@@ -435,7 +418,7 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
 #pragma unroll
                         for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
                         if (!(abl & 2))
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ws_u32x4, o), y2rsrc, (int)(y2off[pr] + (m0 + (unsigned)(mt * 32)) * y2row), 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), y2rsrc, (int)(y2off[pr] + (m0 + (unsigned)(mt * 32)) * y2row), 0, 0);
                     }
                 }
             }

@@ -18,22 +18,8 @@
 
 namespace pasn {
 
-typedef __attribute__((address_space(3))) void* tc_lds_ptr_t;
-typedef __attribute__((ext_vector_type(4))) unsigned tc_u32x4;
-
-constexpr unsigned TC_OOB = 0x80000000u;
 constexpr int TC_BM = 64;   // positions per tile
 constexpr int TC_NSL = 4;   // ring slots
-
-__device__ __forceinline__ void tc_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void tc_wait_all_but(int n) {  // n wave-uniform, 0 .. 8
-    switch (n) {
-#define TC_W(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        TC_W(0) TC_W(1) TC_W(2) TC_W(3) TC_W(4) TC_W(5) TC_W(6) TC_W(7) TC_W(8)
-#undef TC_W
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
 
 // KSF: k-steps per frame (Cin_p / 16); CT: channel tiles of 32 (the block has 2 CT waves); RES: a residual tensor is added before the activation
 template <int KSF, int CT, bool RES>
@@ -53,10 +39,10 @@ __global__ __launch_bounds__(128 * CT) void tconv_ws_kernel(const __bf16* __rest
     const unsigned xrow = (unsigned)Cin_p * 2u, yrow = (unsigned)Cout_p * 2u;
     const unsigned xframe = (unsigned)HW * xrow, yframe = (unsigned)HW * yrow;
     // this clip (every frame): descriptors' ranges end with the clip
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(x + (long)n * T * HW * Cin_p), 0, (unsigned)T * xframe, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(y + (long)n * T * HW * Cout_p, 0, (unsigned)T * yframe, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(x + (long)n * T * HW * Cin_p, (unsigned)T * xframe);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(y + (long)n * T * HW * Cout_p, (unsigned)T * yframe);
     const __amdgpu_buffer_rsrc_t rrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(RES ? res + (long)n * T * HW * Cout_p : x), 0, RES ? (unsigned)T * yframe : 0u, 0x00020000);
+        buffer_rsrc(RES ? res + (long)n * T * HW * Cout_p : x, RES ? (unsigned)T * yframe : 0u);
 
     // ---- stationary weights: fragment-major (tile ct, step ks) = 64 lanes x 16 bytes, K = (dt, channel) ----
     bf16x8 A[KS];
@@ -81,7 +67,7 @@ __global__ __launch_bounds__(128 * CT) void tconv_ws_kernel(const __bf16* __rest
         }
         if (scale) load8(scale + chc, sc[pr]);
         if (bias) load8(bias + chc, bs[pr]);
-        yoff[pr] = (ok && row_ok) ? (unsigned)(p0 + pt * 32 + c) * yrow + (unsigned)ch * 2u : TC_OOB;
+        yoff[pr] = (ok && row_ok) ? (unsigned)(p0 + pt * 32 + c) * yrow + (unsigned)ch * 2u : BUF_OOB;
     }
     const bool tail = ct * 32 + 32 > Cout;  // wave-uniform: this tile holds channels beyond the real count (stored as zeros)
 
@@ -95,7 +81,7 @@ __global__ __launch_bounds__(128 * CT) void tconv_ws_kernel(const __bf16* __rest
     for (int e = 0; e < NE; ++e) {
         const int s = (wave + NW * e) * 64 + lane;
         const int r = s / PPRL, p = s - r * PPRL;  // compile-time divisor
-        xoff[e] = (wave + NW * e < NIX && r < bm && p < 2 * KSF && p0 + r < HW) ? (unsigned)(p0 + r) * xrow + (unsigned)p * 16u : TC_OOB;
+        xoff[e] = (wave + NW * e < NIX && r < bm && p < 2 * KSF && p0 + r < HW) ? (unsigned)(p0 + r) * xrow + (unsigned)p * 16u : BUF_OOB;
     }
     auto issue = [&](int f) {  // frame f of the clip -> slot f % 4; a frame behind the clip's end: NE instructions that fetch nothing
         const bool in = f < T;   // (issued all the same, NOT branched around: a branch would make the count unknown to the compiler again)
@@ -105,7 +91,7 @@ __global__ __launch_bounds__(128 * CT) void tconv_ws_kernel(const __bf16* __rest
         for (int e = 0; e < NE; ++e) {
             const int j = wave + NW * e;
             char* dst = (in && j < NIX) ? sb + j * 1024 : smem + TC_NSL * SLOT;  // wave-uniform
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (tc_lds_ptr_t)dst, 16, (int)(in ? xoff[e] : TC_OOB), (int)fo, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)dst, 16, (int)(in ? xoff[e] : BUF_OOB), (int)fo, 0, 0);
         }
     };
     // the weights and constants are in their registers before the march starts (no wait of the compiler's for them inside the loop)
@@ -120,9 +106,9 @@ __global__ __launch_bounds__(128 * CT) void tconv_ws_kernel(const __bf16* __rest
     for (int t = 0; t < T; ++t) {
         // frame t + 1 (requested one step ago; t = 0: in the prologue, with frame 0) has landed: this wave has since issued only the stores
         // of frame t - 1; behind the barrier everyone's pieces have, and nobody still reads frame t - 2's slot
-        tc_wait_all_but(t == 0 ? 0 : KST);
-        tc_barrier();
-        tc_u32x4 rq[2];
+        wait_vmcnt_all_but<8>(t == 0 ? 0 : KST);  // KST <= 8
+        lds_barrier();
+        u32x4 rq[2];
         if (RES) {  // (ahead of the DMA group: the wait for these registers then leaves the group in flight)
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) rq[pr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)yoff[pr], (int)((unsigned)t * yframe), 0);
@@ -169,8 +155,8 @@ __global__ __launch_bounds__(128 * CT) void tconv_ws_kernel(const __bf16* __rest
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
             // (frame offset in the vector offset, soffset 0: profiles/README.md entry 144)
-            const unsigned off = yoff[pr] == TC_OOB ? TC_OOB : yoff[pr] + (unsigned)t * yframe;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tc_u32x4, o), yrsrc, (int)off, 0, 0);
+            const unsigned off = yoff[pr] == BUF_OOB ? BUF_OOB : yoff[pr] + (unsigned)t * yframe;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, (int)off, 0, 0);
         }
     }
 }

@@ -56,17 +56,16 @@ __device__ __forceinline__ Raw8<T> load_raw8(const T* p) {
 // Rows through a buffer descriptor that ends where the block's chunk ends (num_records = r1 rows): a row past the chunk reads as zeros and its
 // store is dropped by the hardware -- no clamped row index, no 64-bit address per row, no select per element to keep such a row out of the sums
 // (these passes are bound by vector issue).  Offsets are 32-bit bytes inside ONE clip (the launchers check S * Cp * sizeof(T) < 2^31).
-typedef unsigned rb_u32x4 __attribute__((ext_vector_type(4)));
 template <typename T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const T* clip, int rows, int Cp) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(clip), 0, (unsigned)rows * (unsigned)Cp * (unsigned)sizeof(T), 0x00020000);
+    return buffer_rsrc(clip, (unsigned)rows * (unsigned)Cp * (unsigned)sizeof(T));
 }
 template <typename T>
 __device__ __forceinline__ Raw8<T> load_raw8(__amdgpu_buffer_rsrc_t rs, unsigned off) {
     Raw8<T> q;
 #pragma unroll
     for (int i = 0; i < (int)((8 * sizeof(T)) / 16); ++i) {
-        const rb_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off + 16 * i), 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off + 16 * i), 0, 0);
         q.r[i] = uint4{v[0], v[1], v[2], v[3]};
     }
     return q;
@@ -75,11 +74,11 @@ __device__ __forceinline__ void store8(__amdgpu_buffer_rsrc_t rs, unsigned off, 
     bf16x8 a;
 #pragma unroll
     for (int j = 0; j < 8; ++j) a[j] = (__bf16)v[j];
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(rb_u32x4, a), rs, (int)off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, a), rs, (int)off, 0, 0);
 }
 __device__ __forceinline__ void store8(__amdgpu_buffer_rsrc_t rs, unsigned off, const float (&v)[8], const float*) {
-    __builtin_amdgcn_raw_buffer_store_b128(rb_u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, rs, (int)off, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(rb_u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, rs, (int)off + 16, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, rs, (int)off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, rs, (int)off + 16, 0, 0);
 }
 
 // Sum the per-thread 8-channel accumulators `acc[W][8]` over the row lanes of the block (fixed order) and store them

@@ -1175,8 +1175,6 @@ __global__ __launch_bounds__(256, 2) void dw_wgrad_march_kernel(const __bf16* __
 //  * loads go through buffer descriptors: the frame offset is a scalar operand, positions outside the plane carry an out-of-range offset and
 //    read as zero (no select per loaded value, no 64-bit address arithmetic per step),
 //  * lanes map to (item, channel group) without padding the group count to a power of two.
-typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
-constexpr unsigned WG_OOB = 0x80000000u;
 
 template <int CW>
 __device__ __forceinline__ void wg_load(unsigned (&r)[CW], __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
@@ -1189,9 +1187,9 @@ __device__ __forceinline__ void wg_load(unsigned (&r)[CW], __amdgpu_buffer_rsrc_
     }
 }
 template <int CW>
-__device__ __forceinline__ void wg_cvt(const unsigned (&r)[CW], wg_f32x2 (&v)[CW]) {
+__device__ __forceinline__ void wg_cvt(const unsigned (&r)[CW], f32x2 (&v)[CW]) {
 #pragma unroll
-    for (int c = 0; c < CW; ++c) v[c] = wg_f32x2{__uint_as_float(r[c] << 16), __uint_as_float(r[c] & 0xffff0000u)};
+    for (int c = 0; c < CW; ++c) v[c] = f32x2{__uint_as_float(r[c] << 16), __uint_as_float(r[c] & 0xffff0000u)};
 }
 
 template <int SW, int WT, int CH>
@@ -1201,15 +1199,15 @@ __global__ __launch_bounds__(256) void dw_wgrad_march2_kernel(const __bf16* __re
     __shared__ float red[256 * CH];
     const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
     const bool live = pl < PL;
-    wg_f32x2 acc[27][CW];
+    f32x2 acc[27][CW];
 #pragma unroll
     for (int p = 0; p < 27; ++p)
 #pragma unroll
-        for (int c = 0; c < CW; ++c) acc[p][c] = wg_f32x2{0.0f, 0.0f};
+        for (int c = 0; c < CW; ++c) acc[p][c] = f32x2{0.0f, 0.0f};
     const int Cp = d.Cout_p;
     const unsigned xframe = (unsigned)d.Hi * d.Wi * Cp * 2u, gframe = (unsigned)d.Ho * d.Wo * Cp * 2u;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(x), 0, (unsigned)d.N * d.Ti * xframe, 0x00020000);
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(dy), 0, (unsigned)d.N * d.To * gframe, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(x, (unsigned)d.N * d.Ti * xframe);
+    const __amdgpu_buffer_rsrc_t grs = buffer_rsrc(dy, (unsigned)d.N * d.To * gframe);
     for (long item = (long)blockIdx.x * PL + pl; live && item < items; item += (long)gridDim.x * PL) {  // (n, ho, strip)
         const int strip = (int)(item % strips);
         const long q = item / strips;
@@ -1218,7 +1216,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_march2_kernel(const __bf16* __re
         unsigned gv[WT], xv[3][IW];  // byte offsets inside frame 0 of clip n; outside the plane: out of range (reads as zero)
 #pragma unroll
         for (int j = 0; j < WT; ++j)
-            gv[j] = wo0 + j < d.Wo ? (unsigned)n * d.To * gframe + (unsigned)((ho * d.Wo + wo0 + j) * Cp + cg * CH) * 2u : WG_OOB;
+            gv[j] = wo0 + j < d.Wo ? (unsigned)n * d.To * gframe + (unsigned)((ho * d.Wo + wo0 + j) * Cp + cg * CH) * 2u : BUF_OOB;
 #pragma unroll
         for (int dh = 0; dh < 3; ++dh) {
             const int hi = ho * SW - 1 + dh;
@@ -1226,10 +1224,10 @@ __global__ __launch_bounds__(256) void dw_wgrad_march2_kernel(const __bf16* __re
 #pragma unroll
             for (int i = 0; i < IW; ++i) {
                 const int wi = wi0 + i;
-                xv[dh][i] = (hok && wi >= 0 && wi < d.Wi) ? (unsigned)n * d.Ti * xframe + (unsigned)((hi * d.Wi + wi) * Cp + cg * CH) * 2u : WG_OOB;
+                xv[dh][i] = (hok && wi >= 0 && wi < d.Wi) ? (unsigned)n * d.Ti * xframe + (unsigned)((hi * d.Wi + wi) * Cp + cg * CH) * 2u : BUF_OOB;
             }
         }
-        wg_f32x2 g0[WT][CW], g1[WT][CW];  // gradients of output frames ti - 1, ti
+        f32x2 g0[WT][CW], g1[WT][CW];  // gradients of output frames ti - 1, ti
         unsigned gn[WT][CW], raw[3][IW][CW];
 #pragma unroll
         for (int j = 0; j < WT; ++j) wg_load<CW>(gn[j], grs, gv[j], 0u);
@@ -1237,26 +1235,26 @@ __global__ __launch_bounds__(256) void dw_wgrad_march2_kernel(const __bf16* __re
         for (int j = 0; j < WT; ++j) {
             wg_cvt<CW>(gn[j], g1[j]);
 #pragma unroll
-            for (int c = 0; c < CW; ++c) g0[j][c] = wg_f32x2{0.0f, 0.0f};
+            for (int c = 0; c < CW; ++c) g0[j][c] = f32x2{0.0f, 0.0f};
         }
 #pragma unroll
-        for (int j = 0; j < WT; ++j) wg_load<CW>(gn[j], grs, d.To > 1 ? gv[j] : WG_OOB, d.To > 1 ? gframe : 0u);
+        for (int j = 0; j < WT; ++j) wg_load<CW>(gn[j], grs, d.To > 1 ? gv[j] : BUF_OOB, d.To > 1 ? gframe : 0u);
 #pragma unroll
         for (int dh = 0; dh < 3; ++dh)
 #pragma unroll
             for (int i = 0; i < IW; ++i) wg_load<CW>(raw[dh][i], xrs, xv[dh][i], 0u);
 #pragma unroll 1
         for (int ti = 0; ti < d.Ti; ++ti) {
-            wg_f32x2 g2[WT][CW];  // gradient of output frame ti + 1 (zero past the clip)
+            f32x2 g2[WT][CW];  // gradient of output frame ti + 1 (zero past the clip)
 #pragma unroll
             for (int j = 0; j < WT; ++j) wg_cvt<CW>(gn[j], g2[j]);
             {
                 const bool more = ti + 2 < d.To;
                 const unsigned so = (unsigned)min(ti + 2, d.To - 1) * gframe;
 #pragma unroll
-                for (int j = 0; j < WT; ++j) wg_load<CW>(gn[j], grs, more ? gv[j] : WG_OOB, so);
+                for (int j = 0; j < WT; ++j) wg_load<CW>(gn[j], grs, more ? gv[j] : BUF_OOB, so);
             }
-            wg_f32x2 xc[3][IW][CW];
+            f32x2 xc[3][IW][CW];
             const unsigned sx = (unsigned)min(ti + 1, d.Ti - 1) * xframe;  // (the last step's request is not used)
 #pragma unroll
             for (int dh = 0; dh < 3; ++dh) {
@@ -1274,7 +1272,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_march2_kernel(const __bf16* __re
                     for (int j = 0; j < WT; ++j)
 #pragma unroll
                         for (int c = 0; c < CW; ++c) {
-                            const wg_f32x2 xvv = xc[dh][j * SW + dw_][c];
+                            const f32x2 xvv = xc[dh][j * SW + dw_][c];
                             acc[0 * 9 + dh * 3 + dw_][c] = __builtin_elementwise_fma(g2[j][c], xvv, acc[0 * 9 + dh * 3 + dw_][c]);
                             acc[1 * 9 + dh * 3 + dw_][c] = __builtin_elementwise_fma(g1[j][c], xvv, acc[1 * 9 + dh * 3 + dw_][c]);
                             acc[2 * 9 + dh * 3 + dw_][c] = __builtin_elementwise_fma(g0[j][c], xvv, acc[2 * 9 + dh * 3 + dw_][c]);

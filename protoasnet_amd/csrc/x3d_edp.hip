@@ -43,8 +43,6 @@ __device__ long long edp_stamps[8];
 #define EDP_ON (g.stamps && blockIdx.x == 0 && threadIdx.x == 0)
 #endif
 
-__device__ __forceinline__ void edp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 constexpr int EDP_HW = 7, EDP_S = 49;           // the plane
 constexpr int EDP_RWI = 10, EDP_SLOTS = 10;     // frame image: 9 rows x 10 positions x 10 slots of 16 bytes (8 used: one quad)
 // Slots per image ROW: 100 + 2 of padding (round 5).  A stencil operand read serves 16 lanes = TWO output rows of 7 positions; with rows exactly
@@ -94,9 +92,9 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
             bnp[i] = a.b_n[i];
         }
     const long M = (long)a.N * T * EDP_S;
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.x), 0, (unsigned)(M * Cxp * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (unsigned)(M * Cxp * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ersrc = __builtin_amdgcn_make_buffer_rsrc(NEXT ? a.e_next : a.y, 0, NEXT ? (unsigned)(M * a.Cnp * 2) : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(a.x, (unsigned)(M * Cxp * 2));
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(a.y, (unsigned)(M * Cxp * 2));
+    const __amdgpu_buffer_rsrc_t ersrc = buffer_rsrc(NEXT ? a.e_next : a.y, NEXT ? (unsigned)(M * a.Cnp * 2) : 0u);
     const int PPR = Cxp >> 3;
     const int nTch = (T + TF - 1) / TF;
     const int lbl = xcd_remap(blockIdx.x, gridDim.x);
@@ -131,8 +129,8 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
             const int s = j * 64 + lane;
             const int r = s / XPL, p = s - r * XPL;
             const int f = r / EDP_S, pos = r - f * EDP_S, ti = t0 - 1 + f;
-            const unsigned off = (r < RI && p < PPR && ti >= 0 && ti < T) ? (unsigned)(((n * T + ti) * EDP_S + pos) * Cxp + p * 8) * 2u : XB_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (xb_lds_ptr_t)(xin + j * 1024), 16, (int)off, 0, 0, 0);
+            const unsigned off = (r < RI && p < PPR && ti >= 0 && ti < T) ? (unsigned)(((n * T + ti) * EDP_S + pos) * Cxp + p * 8) * 2u : BUF_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(xin + j * 1024), 16, (int)off, 0, 0, 0);
         }
         if (tid < 128) {
             const int f = tid / EDP_S, pos = tid - f * EDP_S;
@@ -204,9 +202,9 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
                         bf16x8 o;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) o[e] = (__bf16)relu_f32(v[e]);
-                        xb_u32x4 ou = __builtin_bit_cast(xb_u32x4, o);
-                        if (!inclip) ou = xb_u32x4{0u, 0u, 0u, 0u};  // the stencil pads the EXPANDED activation with zeros in T
-                        *reinterpret_cast<xb_u32x4*>(cell + (wr ? pr * 32 : 0)) = ou;
+                        u32x4 ou = __builtin_bit_cast(u32x4, o);
+                        if (!inclip) ou = u32x4{0u, 0u, 0u, 0u};  // the stencil pads the EXPANDED activation with zeros in T
+                        *reinterpret_cast<u32x4*>(cell + (wr ? pr * 32 : 0)) = ou;
                     }
                 }
             }
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
                     PA[i][kk] = load_frag<__bf16>(a.w_c + ((long)((pcg + 2 * i) * KSC + min(4 * qd + kk, KSC - 1)) * 64 + lane) * 8);
-            edp_barrier();  // the four frame images of this quad are complete
+            lds_barrier();  // the four frame images of this quad are complete
 #ifdef PASN_TUNING
             if (g.stamps) {
                 const long long now = EDP_NOW();
@@ -232,7 +230,7 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
 #endif
             // ================================ D: stencil, wave = (channel tile, output frame) =============================================
             if (dlive && t0 + tfo < T) {
-                xb_u32x4 A[3][5];
+                u32x4 A[3][5];
                 const unsigned wd[8] = {w0v.x, w0v.y, w0v.z, w0v.w, w1v.x, w1v.y, w1v.z, w1v.w};
 #pragma unroll
                 for (int kt = 0; kt < 3; ++kt)
@@ -240,7 +238,7 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
                     for (int j = 0; j < 5; ++j) {
                         const int e = kt * 5 + j;
                         const unsigned bits = ((e & 1) ? (wd[e >> 1] >> 16) : (wd[e >> 1] & 0xffffu)) << wsh;
-                        A[kt][j] = xb_u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
+                        A[kt][j] = u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
                     }
                 f32x4 S[4];
 #pragma unroll
@@ -278,7 +276,7 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
                     *reinterpret_cast<bf16x4*>(dch + (r * EDP_CPL) * 16 + (ok ? cel : 0) * 2) = o;
                 }
             }
-            edp_barrier();  // the quad's chunk is complete (and everyone is past the images: the next quad's expand may overwrite them)
+            lds_barrier();  // the quad's chunk is complete (and everyone is past the images: the next quad's expand may overwrite them)
 #ifdef PASN_TUNING
             if (g.stamps) {
                 const long long now = EDP_NOW();
@@ -323,7 +321,7 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
                     const int ch = co * 32 + 16 * pr + 8 * h;
-                    off[pr] = (gp != 0xffffffffu && ch < Cxp) ? (gp * (unsigned)Cxp + (unsigned)ch) * 2u : XB_OOB;
+                    off[pr] = (gp != 0xffffffffu && ch < Cxp) ? (gp * (unsigned)Cxp + (unsigned)ch) * 2u : BUF_OOB;
                     rraw[pr] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)off[pr], 0, 0));
                 }
 #pragma unroll
@@ -347,7 +345,7 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
                     bf16x8 o;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (__bf16)relu_f32(v[e]);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(xb_u32x4, o), yrsrc, (int)off[pr], 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, (int)off[pr], 0, 0);
                     if (NEXT && ch < Cxp) *reinterpret_cast<bf16x8*>(xt + (r * XPL + (ch >> 3)) * 16) = o;
                 }
             }

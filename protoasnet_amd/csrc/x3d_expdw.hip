@@ -24,13 +24,6 @@
 
 namespace pasn {
 
-typedef __attribute__((ext_vector_type(4))) unsigned xe_u32x4;
-typedef __attribute__((ext_vector_type(2))) short xe_s16x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 xe_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float xe_f32x2;
-typedef __attribute__((ext_vector_type(2))) unsigned xe_u32x2;
-typedef __attribute__((address_space(3))) void* xe_lds_ptr_t;
-
 // Region geometry per stride.  Stride 2: 3 x 14 outputs from 7 x 29 staged positions, an expand MFMA tile = one staged row (29 of 32
 // lanes), 9 slots per position.  Stride 1: 6 x 14 outputs from 8 x 16 staged positions = exactly four 32-position MFMA tiles (two staged
 // rows each), 10 slots per position (the slot counts are dwmfma.hip's bank rule: stride x slots = 2 mod 4).
@@ -47,24 +40,6 @@ struct XeR {
     static constexpr int TILES = SS == 2 ? RH : POS / 32;       // expand tiles per frame: 7 / 4
 };
 constexpr int XE_NE = 6;  // x DMA instructions per wave and frame, at most (203 positions x <= 7 slots)
-constexpr unsigned XE_OOB = 0x80000000u;
-
-__device__ __forceinline__ unsigned xe_bf16_bits(float f) {
-    const __bf16 b = (__bf16)f;
-    return (unsigned)__builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ void xe_wait_all_but(int n) {  // n wave-uniform
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;  // n <= NT <= 6
-    }
-}
-__device__ __forceinline__ void xe_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // KS: k-steps of the expand conv held in registers (K = block width <= 16 KS channels); ACT: the stencil's epilogue activation
 template <int KS, int ACT, int SS, bool ABLB = false, bool FOLD = false>  // ABLB: timing-only ablation instance (PASN_EXPDW_ABL; results are wrong when set)
@@ -95,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
     const int abl = ABLB ? g.abl : 0;  // 1: no expand MFMAs, 2: no expand epilogue arithmetic, 4: no x DMA, 8: no stencil MFMAs, 16: no output epilogue / stores
 
     // ---- stencil: block-diagonal weight operands (dwmfma.hip) ----
-    xe_u32x4 A[3][5];
+    u32x4 A[3][5];
     {
         const int c = c0 + m;
         const bool mine = ((m >> 3) == (q & 1)) && c < Cp;
@@ -111,8 +86,8 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
                 const bool live = mine && 2 * j + (q >> 1) < 9;
-                const unsigned bits = live ? (xe_bf16_bits(wv[kt][j]) << sh) : 0u;
-                A[kt][j] = xe_u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
+                const unsigned bits = live ? (bf16_bits(wv[kt][j]) << sh) : 0u;
+                A[kt][j] = u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
             }
     }
     const int ce = c0 + 4 * q;
@@ -171,7 +146,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
     const int Ti = d.Ti, Hi = d.Hi, Wi = d.Wi;
     const long fx = (long)Hi * Wi * Cin_p;  // elements per x frame
     const unsigned fx_bytes = (unsigned)(fx * 2);
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(x + (long)n * Ti * fx), 0, (unsigned)Ti * fx_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(x + (long)n * Ti * fx, (unsigned)Ti * fx_bytes);
     const int nix = (XE_POS * XS + 63) >> 6;   // 1-KiB x DMA instructions per frame
     int tapoff[5];
 #pragma unroll
@@ -198,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
             const int rr = rp / XE_RW, cc = rp - rr * XE_RW;
             const int hi = h0 * SS - 1 + rr, wi = w0 * SS - 1 + cc;
             const bool ok = wave + 4 * e < nix && rp < XE_POS && p < pieces && hi >= 0 && hi < Hi && wi >= 0 && wi < Wi;
-            goff[e] = ok ? (unsigned)(((hi * Wi + wi) * Cin_p + p * 8) * 2) : XE_OOB;
+            goff[e] = ok ? (unsigned)(((hi * Wi + wi) * Cin_p + p * 8) * 2) : BUF_OOB;
         }
         const int kdma = max(0, (nix - wave + 3) >> 2);
         auto staged = [&](int ti) -> bool { return ti >= 0 && ti < Ti && ti >= t0 - 1 && ti <= t1; };
@@ -210,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
 #pragma unroll
             for (int e = 0; e < XE_NE; ++e)
                 if (wave + 4 * e < nix)  // wave-uniform
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (xe_lds_ptr_t)(dst + (wave + 4 * e) * 1024), 16, (int)goff[e], (int)foff, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(dst + (wave + 4 * e) * 1024), 16, (int)goff[e], (int)foff, 0, 0);
         };
         // this lane's staged position inside expand tile i of a frame: stride 2: (row tile, column c32 < 29); stride 1: (row 2 tile + c32 / 16,
         // column c32 % 16).  keepm bit i: the position lies inside the image (the stencil pads the EXPANDED activation with zeros)
@@ -262,27 +237,27 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
             unsigned P[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                xe_f32x2 a = {acc[2 * j], acc[2 * j + 1]};
+                f32x2 a = {acc[2 * j], acc[2 * j + 1]};
                 if (!folded) {  // separate scale / bias: rows acc_row(2j, h32), +1 of this lane's 16 (before the swap)
                     a.x = a.x * scb[32 * ect + acc_row(2 * j, h32)] + scb[64 + 32 * ect + acc_row(2 * j, h32)];
                     a.y = a.y * scb[32 * ect + acc_row(2 * j + 1, h32)] + scb[64 + 32 * ect + acc_row(2 * j + 1, h32)];
                 }
-                xe_s16x2 m = __builtin_bit_cast(xe_s16x2, __builtin_convertvector(a, xe_bf16x2));  // one v_cvt_pk_bf16_f32
-                if (!(abl & 2)) m = __builtin_elementwise_max(m, xe_s16x2{0, 0});
+                s16x2 m = __builtin_bit_cast(s16x2, __builtin_convertvector(a, bf16x2));  // one v_cvt_pk_bf16_f32
+                if (!(abl & 2)) m = __builtin_elementwise_max(m, s16x2{0, 0});
                 P[j] = __builtin_bit_cast(unsigned, m);
             }
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {
                 const auto s0 = __builtin_amdgcn_permlane32_swap(P[4 * pr + 0], P[4 * pr + 2], false, false);
                 const auto s1 = __builtin_amdgcn_permlane32_swap(P[4 * pr + 1], P[4 * pr + 3], false, false);
-                xe_u32x4 ou = {s0[0], s1[0], s0[1], s1[1]};  // this lane's 8 consecutive channels 32 ect + 16 pr + 8 h32 ..
+                u32x4 ou = {s0[0], s1[0], s0[1], s1[1]};  // this lane's 8 consecutive channels 32 ect + 16 pr + 8 h32 ..
                 if (!all_in) {  // wave-uniform: only regions on the image border select (incl. whole tiles of the zero padding)
                     ou.x = keep ? ou.x : 0u;
                     ou.y = keep ? ou.y : 0u;
                     ou.z = keep ? ou.z : 0u;
                     ou.w = keep ? ou.w : 0u;
                 }
-                *reinterpret_cast<xe_u32x4*>(rp + pr * 32) = ou;
+                *reinterpret_cast<u32x4*>(rp + pr * 32) = ou;
             }
         };
         // Straight-line, two tiles at a time: the fragment reads of BOTH tiles, then their MFMA chains, then the two epilogues -- with a
@@ -314,7 +289,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
         const int ystep = d.Wo * Cp;
         __bf16* yclip = y + (long)n * d.To * d.Ho * d.Wo * Cp;
         const long ofs = (long)d.Ho * d.Wo * Cp;
-        const unsigned yvoff = lane_ok ? (unsigned)(((h0 * d.Wo + w0 + m) * Cp + ce) * 2) : XE_OOB;
+        const unsigned yvoff = lane_ok ? (unsigned)(((h0 * d.Wo + w0 + m) * Cp + ce) * 2) : BUF_OOB;
         const unsigned fr_bytes = (unsigned)(ofs * 2);
         const int kst = wave_live ? XE_NT : 0;  // stores per emitted frame: one per tile, whether or not its row exists
         auto stored = [&](int to) -> int { return (to >= t0 && to < t1 && !(abl & 16)) ? kst : 0; };
@@ -363,7 +338,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
         auto emit = [&](int ti, f32x4 (&P)[XE_NT]) {  // output frame ti - 1 has now seen frames ti - 2, ti - 1, ti
             const int to = ti - 1;
             if (wave_live && to >= t0 && to < t1 && !(abl & 16)) {
-                const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(yclip + (long)to * ofs, 0, fr_bytes, 0x00020000);
+                const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(yclip + (long)to * ofs, fr_bytes);
                 // straight-line over ALL tiles, as in dwmfma.hip: a row below the plane stores out of the descriptor's range and counts nothing,
                 // the pool sums are formed whether or not the launch has a row for them, padded channels carry zero scale and bias
                 f32x4 sc, bs;
@@ -395,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
                         bf16x4 o;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) o[i] = (__bf16)v[i];
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xe_u32x2, o), yrsrc, (int)yvoff, l * ystep * 2, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), yrsrc, (int)yvoff, l * ystep * 2, 0);
                     }
             }
         };
@@ -419,13 +394,13 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
             unsigned Pk[8];
             // the expand epilogue of tile i in ten steps: eight packed convert + ReLU pairs, two (lane swap, border mask, store) halves
             auto e_cvt = [&](int j) {
-                xe_f32x2 a = {acc[2 * j], acc[2 * j + 1]};
+                f32x2 a = {acc[2 * j], acc[2 * j + 1]};
                 if (!folded) {
                     a.x = a.x * scb[32 * ect + acc_row(2 * j, h32)] + scb[64 + 32 * ect + acc_row(2 * j, h32)];
                     a.y = a.y * scb[32 * ect + acc_row(2 * j + 1, h32)] + scb[64 + 32 * ect + acc_row(2 * j + 1, h32)];
                 }
-                xe_s16x2 mm = __builtin_bit_cast(xe_s16x2, __builtin_convertvector(a, xe_bf16x2));
-                mm = __builtin_elementwise_max(mm, xe_s16x2{0, 0});
+                s16x2 mm = __builtin_bit_cast(s16x2, __builtin_convertvector(a, bf16x2));
+                mm = __builtin_elementwise_max(mm, s16x2{0, 0});
                 Pk[j] = __builtin_bit_cast(unsigned, mm);
             };
             auto e_out = [&](int i, int pr) {
@@ -437,14 +412,14 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
                 const bool keep = (keepm >> i) & 1u;
                 const auto s0 = __builtin_amdgcn_permlane32_swap(Pk[4 * pr + 0], Pk[4 * pr + 2], false, false);
                 const auto s1 = __builtin_amdgcn_permlane32_swap(Pk[4 * pr + 1], Pk[4 * pr + 3], false, false);
-                xe_u32x4 ou = {s0[0], s1[0], s0[1], s1[1]};
+                u32x4 ou = {s0[0], s1[0], s0[1], s1[1]};
                 if (!all_in) {
                     ou.x = keep ? ou.x : 0u;
                     ou.y = keep ? ou.y : 0u;
                     ou.z = keep ? ou.z : 0u;
                     ou.w = keep ? ou.w : 0u;
                 }
-                *reinterpret_cast<xe_u32x4*>(rp + pr * 32) = ou;
+                *reinterpret_cast<u32x4*>(rp + pr * 32) = ou;
             };
             p_read(0, xb, xf);
 #pragma unroll
@@ -497,8 +472,8 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
         for (int ti = t0 - 1; ti <= t1; ++ti) {
             // the x rows of frame ti + 1 (requested in step ti - 1, before that step's stores) have landed; behind the barrier everyone's
             // have, frame ti's image (written in step ti - 1) is complete, and nobody still reads the image / x tile of frame ti - 1
-            xe_wait_all_but(stored(ti - 2));
-            xe_barrier();
+            wait_vmcnt_all_but<6>(stored(ti - 2));  // n <= NT <= 6
+            lds_barrier();
             if (SS == 2 && staged(ti + 1) && wave_live && ti >= 0 && ti < Ti && !(abl & 8) && fuse) {  // wave-uniform: the steady state (stride 1: 6 stencil tiles' accumulators leave no room, 66 spilled VGPRs)
                 issue_x(ti + 2);  // (its x tile held frame ti: everyone is past produce(ti))
                 fused(ti, S0, S1, S2);

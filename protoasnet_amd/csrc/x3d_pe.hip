@@ -43,8 +43,6 @@ __device__ long long pe_stamps[8];
 #define PE_STAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ void pe_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // The squeeze-excite gate rows of clips n0 .. n0 + ncl - 1 into G ([2][GP] floats in LDS): pwconv_ws.hip's prologue, thread for thread (same
 // summation orders: bit-identical gate rows) -- mean over positions from the stencil's partial rows (fixed order) -> fc1 + ReLU (a wave per
 // hidden unit, lanes over channels) -> fc2 + sigmoid (a thread per channel).  NOT inlined: its 70-odd registers of FC weights, live across two
@@ -96,7 +94,7 @@ __device__ __attribute__((noinline)) void pe_se_gate(const float* __restrict__ p
             if (ncl > 1) mean[Cmp + tid] = sum1 * inv_positions;
         }
     }
-    pe_barrier();
+    lds_barrier();
     for (int q = 0; q < ncl; ++q) {
         float sacc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -115,7 +113,7 @@ __device__ __attribute__((noinline)) void pe_se_gate(const float* __restrict__ p
             if (lane == 0 && j < cse) hid[q * cse + j] = fmaxf(t + b1r[u], 0.0f);
         }
     }
-    pe_barrier();
+    lds_barrier();
     for (int q = 0; q < ncl; ++q) {
         float gv = 0.0f;
         if (tid < C) {
@@ -159,10 +157,10 @@ __global__ __launch_bounds__(512) void x3d_pe_kernel(PeArgs a, PeGeom g) {
         sap[i] = a.s_a[i];
         bap[i] = a.b_a[i];
     }
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.x), 0, (unsigned)((long)M * Cmp * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.res), 0, (unsigned)((long)M * Cop * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (unsigned)((long)M * Cop * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ersrc = __builtin_amdgcn_make_buffer_rsrc(a.e_next, 0, (unsigned)((long)M * a.Cnp * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(a.x, (unsigned)((long)M * Cmp * 2));
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(a.res, (unsigned)((long)M * Cop * 2));
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(a.y, (unsigned)((long)M * Cop * 2));
+    const __amdgpu_buffer_rsrc_t ersrc = buffer_rsrc(a.e_next, (unsigned)((long)M * a.Cnp * 2));
     const int PPR = Cmp >> 3;
     const int lbl = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_end = min(g.tiles, (lbl + 1) * g.tpb);
@@ -180,8 +178,8 @@ __global__ __launch_bounds__(512) void x3d_pe_kernel(PeArgs a, PeGeom g) {
         for (int j = wave; j < nix; j += 8) {
             const int s = j * 64 + lane;
             const int r = s / DPL, p = s - r * DPL;
-            const unsigned off = (r < R && p < PPR && m0 + (unsigned)r < (unsigned)M) ? (m0 + (unsigned)r) * (unsigned)(Cmp * 2) + (unsigned)p * 16u : XB_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (xb_lds_ptr_t)(img + j * 1024), 16, (int)off, 0, 0, 0);
+            const unsigned off = (r < R && p < PPR && m0 + (unsigned)r < (unsigned)M) ? (m0 + (unsigned)r) * (unsigned)(Cmp * 2) + (unsigned)p * 16u : BUF_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(img + j * 1024), 16, (int)off, 0, 0, 0);
         }
         if (SE && n0 != gate_clip) {
             const int n_last = (int)(min((unsigned)M, m0 + (unsigned)R) - 1u) / S;

@@ -5,12 +5,6 @@
 
 namespace pasn {
 
-typedef __attribute__((ext_vector_type(4))) unsigned xb_u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned xb_u32x2;
-typedef __attribute__((address_space(3))) void* xb_lds_ptr_t;
-
-constexpr unsigned XB_OOB = 0x80000000u;
-
 // One pointwise conv of the tile: out[r][ch] = act(scale * sum_k W[ch][k] img[r][k] + bias (+ residual)), unit = (32 channels, MT 32-row tiles).
 // MT: row tiles that share a unit's weight fragments -- 2: twice as many units (all eight waves busy on narrow outputs), every fragment read by
 // ceil(RTn / 2) units; 4: half the weight stream (what bounds the 432-channel layers: each CU ingests the layer's whole weight set per tile).
@@ -43,7 +37,7 @@ __device__ __forceinline__ void xb_pointwise(const __bf16* __restrict__ w, const
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
                     const int ch = pco * 32 + 16 * pr + 8 * h;
-                    off[mt][pr] = (ppp * MT + mt < RTn && gp != 0xffffffffu && ch < Cout_p) ? (gp * (unsigned)Cout_p + (unsigned)ch) * 2u : XB_OOB;
+                    off[mt][pr] = (ppp * MT + mt < RTn && gp != 0xffffffffu && ch < Cout_p) ? (gp * (unsigned)Cout_p + (unsigned)ch) * 2u : BUF_OOB;
                     if (RES) rraw[mt][pr] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)off[mt][pr], 0, 0));
                 }
             }
@@ -82,7 +76,7 @@ __device__ __forceinline__ void xb_pointwise(const __bf16* __restrict__ w, const
                     bf16x8 o;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (__bf16)relu_f32(v[e]);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(xb_u32x4, o), orsrc, (int)off[mt][pr], 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), orsrc, (int)off[mt][pr], 0, 0);
                     if (TOLDS) {
                         const int ch = pco * 32 + 16 * pr + 8 * h;
                         // (channels beyond the width would spill into the next row; a row tile beyond the tile's rows has no image rows)
