@@ -135,6 +135,33 @@ struct DwRedArgs {
     const float* stat;
     int act;
 };
+// The (T chunk, units per block) split of the T-marching block-diagonal stencils (dwmfma.hip, x3d_expdw.hip).  A unit = (T chunk, region);
+// blocks run two per CU, a block costs a setup (weight operands, pipeline fill) plus upb units of Tc + `halo` frames (the per-unit frame
+// overhead: 2, or 3 with the expand prologue); at most 64 chunks per clip where it costs nothing (the chunk count is the number of SE
+// partial rows per clip the gate has to sum; 128: 209 vs 195 us per launch).  bpch = blocks per chunk (N x channel quads); force_*: 0 = search.
+struct TSplit {
+    int Tc, nT, upb, chunks;
+};
+inline TSplit t_split(int To, int regions, long bpch, int halo, int force_tc, int force_upb) {
+    TSplit r{};
+    double best = 1e30;
+    for (int tc = To;; tc = (tc + 1) / 2) {
+        const int tcu = force_tc ? (force_tc < To ? force_tc : To) : tc;
+        const int nT = ceil_div(To, tcu), units = nT * regions;
+        for (int upb = 1; upb <= units; ++upb) {
+            if (force_upb && upb != (force_upb < units ? force_upb : units)) continue;
+            const int chunks = ceil_div(units, upb);
+            if (chunks > 64 && upb < units && !force_upb) continue;
+            const double t = (double)ceil_div(bpch * chunks, 512L) * (4.0 + upb * (tcu + (double)halo));
+            if (t < best) {
+                best = t;
+                r = TSplit{tcu, nT, upb, chunks};
+            }
+        }
+        if (force_tc || tc <= 4) break;
+    }
+    return r;
+}
 // dwmfma.hip: the stride-1 depthwise 3x3x3 stencil on the matrix cores (block-diagonal bf16 weight operands, LDS-DMA frame ring, T-marching); ok = 0: not covered
 struct DwMfmaGeom {
     int ok, CT, CQ;            // channel tiles of 16, quads of 4 tiles (one block owns a quad)

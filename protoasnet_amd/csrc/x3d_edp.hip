@@ -7,14 +7,16 @@
 // affordable: a tile = (clip, two output frames) needs the block input of FOUR whole frames -- 196 rows x 192 channels = 78 KB, no spatial halo --
 // and from then on everything is on chip: per 64-channel quad of the inner width
 //   E  expand conv of the four frames from the x image (MFMA 32x32x16, weight fragments streamed from L2), ReLU, rounded to bf16, written as
-//      dwmfma.hip's frame images (10-position rows, zero border kept from one clearing pass; frames outside the clip are written as zeros:
+//      blockdiag.h's frame images (10-position rows, zero border kept from one clearing pass; frames outside the clip are written as zeros:
 //      the stencil pads the EXPANDED activation);
 //   D  stencil: wave = (16-channel tile of the quad, output frame): 3 kt x 5 tap pairs x 4 position tiles of block-diagonal 16x16x32 MFMAs
+//      (blockdiag.h: the formulation, the operand placement, the tap offsets; the chains here accumulate in place, kt outermost)
 //      straight from the four images -- no ring, no DMA, no rotation; scale / bias / Swish -> bf16 -> the quad's chunk [98 rows][64 ch];
 //   P  project conv, this quad's four k-steps: wave = (row tile, three 32-channel output tiles), accumulators kept across the quads.
 // Two barriers per quad, 14 in all; the expand conv is computed on 4 frames for 2 outputs (the T halo: 2x its MFMAs, ~1/3 of the launch's).
 // Then the project epilogue (+ residual from the block input, ReLU, 16-byte stores, block-output image) and, optionally, the next block's
 // expand conv from that image (xb_pointwise.h).  Rounding points and accumulation orders are those of the separate launches: bit-identical.
+#include "blockdiag.h"
 #include "common.h"
 #include "xb_pointwise.h"
 
@@ -99,16 +101,11 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
     const int nTch = (T + TF - 1) / TF;
     const int lbl = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_end = min(g.tiles, (lbl + 1) * g.tpb);
-    // stencil roles (dwmfma.hip's two-rows-per-tile layout on 10-position image rows)
+    // stencil roles (two output rows per position tile on 10-position image rows)
     const int ctw = wave & 3, tfo = wave >> 2;
     const int mrow = m / EDP_HW, mcol = m - mrow * EDP_HW;
-    const int dwsel = (m & 7) >> 1, wsh = (m & 1) * 16;
     int tapoff[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int tap9 = min(2 * j + (q4 >> 1), 8);
-        tapoff[j] = ((tap9 / 3) * EDP_ROWP + (tap9 % 3) * EDP_SLOTS) * 16;
-    }
+    bd_tap_offsets<EDP_ROWP, EDP_SLOTS>(q4, tapoff);
     const bool mpos = m < 2 * EDP_HW;  // lanes 14, 15 hold no position: they read lane 13's cell
     const int lbase0 = ((mpos ? mrow : 1) * EDP_ROWP + (mpos ? mcol : EDP_HW - 1) * EDP_SLOTS + 2 * ctw + (q4 & 1)) * 16;
     constexpr int lstep = 2 * EDP_ROWP * 16;
@@ -237,13 +234,12 @@ __global__ __launch_bounds__(512) void x3d_edp_kernel(EdpArgs a, EdpGeom g) {
 #pragma unroll
                     for (int j = 0; j < 5; ++j) {
                         const int e = kt * 5 + j;
-                        const unsigned bits = ((e & 1) ? (wd[e >> 1] >> 16) : (wd[e >> 1] & 0xffffu)) << wsh;
-                        A[kt][j] = u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
+                        A[kt][j] = bd_place((e & 1) ? (wd[e >> 1] >> 16) : (wd[e >> 1] & 0xffffu), m);
                     }
                 f32x4 S[4];
 #pragma unroll
                 for (int l = 0; l < 4; ++l) S[l] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                // accumulation order per output = dwmfma.hip's: kt = 0 (frame t - 1), kt = 1 (t), kt = 2 (t + 1), five tap pairs each
+                // accumulation order per output = that of blockdiag.h's marching chains: kt = 0 (frame t - 1), kt = 1 (t), kt = 2 (t + 1), five tap pairs each
 #pragma unroll
                 for (int kt = 0; kt < 3; ++kt) {
                     const char* fb = fimg + (tfo + kt) * EDP_FB + lbase0;

@@ -12,21 +12,22 @@
 //     v_mfma_f32_32x32x16_bf16 with a staged ROW of the region as the 32-position tile (A = this wave's 32 expand channels, whole K, in
 //     registers for the launch); the accumulator goes through the lane swap (8 channels of one position per lane), BN + ReLU, is forced
 //     to ZERO outside the image (the stencil pads the EXPANDED activation), and is written as one 16-byte piece per lane into the frame
-//     image of a 2-frame ring -- [position][9 slots], the layout dwmfma.hip stages by DMA;
-//   * the stencil is dwmfma.hip's: v_mfma_f32_16x16x32_bf16 with block-diagonal weight operands, one 16-byte LDS read per lane and tap
-//     pair, three accumulator sets (outputs t-1, t, t+1) whose role rotation rides in the MFMAs, outputs stored straight from the
-//     accumulators through a per-frame buffer descriptor;
+//     image of a 2-frame ring -- [position][9 slots], the layout blockdiag.h's chains read;
+//   * the stencil is the block-diagonal one of blockdiag.h: v_mfma_f32_16x16x32_bf16 with block-diagonal weight operands, one 16-byte LDS
+//     read per lane and tap pair, three accumulator sets (outputs t-1, t, t+1) whose role rotation rides in the MFMAs, outputs stored
+//     straight from the accumulators through a per-frame buffer descriptor (what this file keeps of it: the MFMA order of the fused step);
 //   * ONE fence-free barrier per frame: frame t+1 is expanded into the other ring slot before frame t's stencil, the x rows of frame
 //     t+2 are requested in between; what must have landed is waited for by count.
 // Rounding points are those of the two launches (the expanded activation is rounded to bf16 before the stencil; fp32 accumulation), the
-// MFMA k order of the expand conv is pwconv's, the stencil's is dwmfma's.
+// MFMA k order of the expand conv is pwconv's, the stencil's is blockdiag.h's.
+#include "blockdiag.h"
 #include "common.h"
 
 namespace pasn {
 
 // Region geometry per stride.  Stride 2: 3 x 14 outputs from 7 x 29 staged positions, an expand MFMA tile = one staged row (29 of 32
 // lanes), 9 slots per position.  Stride 1: 6 x 14 outputs from 8 x 16 staged positions = exactly four 32-position MFMA tiles (two staged
-// rows each), 10 slots per position (the slot counts are dwmfma.hip's bank rule: stride x slots = 2 mod 4).
+// rows each), 10 slots per position (the bank rule of the operand reads: stride x slots = 2 mod 4).
 template <int SS>
 struct XeR {
     static constexpr int NT = SS == 2 ? 3 : 6;                  // output rows of a region = 16-lane position tiles per wave
@@ -39,6 +40,14 @@ struct XeR {
     static constexpr int TP = SS == 2 ? RW : 32;                // staged positions per expand tile (stride 2: a row; stride 1: two rows)
     static constexpr int TILES = SS == 2 ? RH : POS / 32;       // expand tiles per frame: 7 / 4
 };
+// This lane's (clamped) staged position inside expand tile (wave >> 1) + 2 i of a frame, for the fragment reads and for the epilogue's
+// stores.  (A function, not a lambda of the kernel: as a lambda the non-FOLD stride-2 instances, at 256 VGPRs, spilled 2.)
+template <typename R>
+__device__ __forceinline__ int xe_tile_pos(int wave, int c32, int i) {
+    const int tile = (wave >> 1) + 2 * i;
+    const int tl = min(tile, R::TILES - 1);
+    return tl * R::TP + min(c32, R::TP - 1);
+}
 constexpr int XE_NE = 6;  // x DMA instructions per wave and frame, at most (203 positions x <= 7 slots)
 
 // KS: k-steps of the expand conv held in registers (K = block width <= 16 KS channels); ACT: the stencil's epilogue activation
@@ -69,27 +78,8 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
     const bool fuse = g.fuse != 0;
     const int abl = ABLB ? g.abl : 0;  // 1: no expand MFMAs, 2: no expand epilogue arithmetic, 4: no x DMA, 8: no stencil MFMAs, 16: no output epilogue / stores
 
-    // ---- stencil: block-diagonal weight operands (dwmfma.hip) ----
-    u32x4 A[3][5];
-    {
-        const int c = c0 + m;
-        const bool mine = ((m >> 3) == (q & 1)) && c < Cp;
-        const int dwsel = (m & 7) >> 1, sh = (m & 1) * 16;
-        float wv[3][5];
-        const int cc = min(c, Cp - 1);
-#pragma unroll
-        for (int kt = 0; kt < 3; ++kt)
-#pragma unroll
-            for (int j = 0; j < 5; ++j) wv[kt][j] = w[(kt * 9 + min(2 * j + (q >> 1), 8)) * Cp + cc];
-#pragma unroll
-        for (int kt = 0; kt < 3; ++kt)
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const bool live = mine && 2 * j + (q >> 1) < 9;
-                const unsigned bits = live ? (bf16_bits(wv[kt][j]) << sh) : 0u;
-                A[kt][j] = u32x4{dwsel == 0 ? bits : 0u, dwsel == 1 ? bits : 0u, dwsel == 2 ? bits : 0u, dwsel == 3 ? bits : 0u};
-            }
-    }
+    u32x4 A[3][5];  // stencil: block-diagonal weight operands
+    bd_build_operands(w, Cp, c0, m, q, A);
     const int ce = c0 + 4 * q;
     const bool cev = ce < Cp;
     // FOLD instances (the plan's form): the stencil's epilogue constants of this quad live in LDS and are read where they are used -- as eight
@@ -97,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
     // traffic inside the pinned schedule: round-3 verdict).  They take the place of the expand conv's scale | bias table, which a FOLD instance
     // reads only once, into biasC, before the march (the launch sits at 79.6 KB of LDS: two blocks per CU leave no room for another table).
     // (zero for the padded channels: act(0 * P + 0) = 0 for none / ReLU / Swish -- the epilogue stores without a tail mask)
-    float sc_r[4], bs_r[4];
+    f32x4 sc_r, bs_r;
     if (!FOLD) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -149,11 +139,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
     const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(x + (long)n * Ti * fx, (unsigned)Ti * fx_bytes);
     const int nix = (XE_POS * XS + 63) >> 6;   // 1-KiB x DMA instructions per frame
     int tapoff[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int tap9 = min(2 * j + (q >> 1), 8);
-        tapoff[j] = ((tap9 / 3) * XE_RW + (tap9 % 3)) * (XE_SLOTS * 16);
-    }
+    bd_tap_offsets<XE_RW * XE_SLOTS, XE_SLOTS>(q, tapoff);
     const int regions = g.RTH * g.RTW;
     const int units = g.nT * regions;
     const int u_end = min(units, (chunk + 1) * g.upb);
@@ -204,15 +190,13 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
         }
         // expand frame ti from its x tile into its ring image.  (K columns beyond the block width carry zero WEIGHTS -- the packed rows
         // are zero-padded to w_kc -- so the lanes that supply them read a real piece instead of selecting a zero fragment.)
-        // The three parts of expand tile i of this wave (tile (wave >> 1) + 2 i of the frame), shared by produce() and by the fused step:
-        // p_read: the x fragments; p_mma: the chain of KS 32x32x16 MFMAs; p_epi: ReLU + rounding + lane swap + border mask + 2 ds_write_b128.
+        // The parts of expand tile i of this wave (tile (wave >> 1) + 2 i of the frame), shared by produce() and by the fused step:
+        // p_read: the x fragments; p_mma: the chain of KS 32x32x16 MFMAs; the epilogue in ten steps: e_cvt x 8 (a packed pair: convert + ReLU),
+        // e_out x 2 (lane swap, border mask, one ds_write_b128).
         // Lanes / tiles that hold nothing (lanes 29-31 at stride 2, the fourth tile of waves 2 and 3) run like the others on clamped
         // addresses and store into a dummy region instead of branching around the store (a branch ends the scheduling region).
         auto p_read = [&](int i, const char* xb, bf16x8 (&xf)[KS]) {
-            const int tile = (wave >> 1) + 2 * i;
-            const int tl = min(tile, R::TILES - 1);
-            const int pos = tl * R::TP + min(c32, R::TP - 1);
-            const char* xp = xb + pos * XS * 16;
+            const char* xp = xb + xe_tile_pos<R>(wave, c32, i) * XS * 16;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(xp + min(2 * ks + h32, XS - 1) * 16);
         };
@@ -223,42 +207,42 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
                 else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AE[ks], xf[ks], ks == 0 ? biasC : acc, 0, 0, 0);
             }
         };
-        auto p_epi = [&](int i, char* rb, const f32x16& acc) {
-            const int tile = (wave >> 1) + 2 * i;
-            const int tl = min(tile, R::TILES - 1);
-            const int pos = tl * R::TP + min(c32, R::TP - 1);
-            const bool wr = lane_used && tile < R::TILES;
+        // ReLU and the bf16 rounding BEFORE the lane swap, on packed pairs: v_cvt_pk_bf16_f32 + v_pk_max_i16 (a bf16 is
+        // negative iff it is negative as an int16; rounding keeps the sign, so max(round(v), 0) == round(max(v, 0)) and
+        // -0 becomes +0 either way) and half the swaps -- 14 vector instructions per 8 x 64 outputs where the float path
+        // (swap, canonicalise, max, convert) took 34, on a kernel bound by vector issue.
+        auto e_cvt = [&](const f32x16& acc, int j, bool relu) -> unsigned {
+            f32x2 a = {acc[2 * j], acc[2 * j + 1]};
+            if (!folded) {  // separate scale / bias: rows acc_row(2j, h32), +1 of this lane's 16 (before the swap)
+                a.x = a.x * scb[32 * ect + acc_row(2 * j, h32)] + scb[64 + 32 * ect + acc_row(2 * j, h32)];
+                a.y = a.y * scb[32 * ect + acc_row(2 * j + 1, h32)] + scb[64 + 32 * ect + acc_row(2 * j + 1, h32)];
+            }
+            s16x2 mm = __builtin_bit_cast(s16x2, __builtin_convertvector(a, bf16x2));  // one v_cvt_pk_bf16_f32
+            if (relu) mm = __builtin_elementwise_max(mm, s16x2{0, 0});
+            return __builtin_bit_cast(unsigned, mm);
+        };
+        auto e_out = [&](int i, char* rb, const unsigned (&Pk)[8], int pr) {
+            const int pos = xe_tile_pos<R>(wave, c32, i);
+            const bool wr = lane_used && (wave >> 1) + 2 * i < R::TILES;
             char* const rp = wr ? rb + (pos * XE_SLOTS + 4 * ect + h32) * 16 : dummy;
             const bool keep = (keepm >> i) & 1u;
-            // ReLU and the bf16 rounding BEFORE the lane swap, on packed pairs: v_cvt_pk_bf16_f32 + v_pk_max_i16 (a bf16 is
-            // negative iff it is negative as an int16; rounding keeps the sign, so max(round(v), 0) == round(max(v, 0)) and
-            // -0 becomes +0 either way) and half the swaps -- 14 vector instructions per 8 x 64 outputs where the float path
-            // (swap, canonicalise, max, convert) took 34, on a kernel bound by vector issue.
-            unsigned P[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                f32x2 a = {acc[2 * j], acc[2 * j + 1]};
-                if (!folded) {  // separate scale / bias: rows acc_row(2j, h32), +1 of this lane's 16 (before the swap)
-                    a.x = a.x * scb[32 * ect + acc_row(2 * j, h32)] + scb[64 + 32 * ect + acc_row(2 * j, h32)];
-                    a.y = a.y * scb[32 * ect + acc_row(2 * j + 1, h32)] + scb[64 + 32 * ect + acc_row(2 * j + 1, h32)];
-                }
-                s16x2 m = __builtin_bit_cast(s16x2, __builtin_convertvector(a, bf16x2));  // one v_cvt_pk_bf16_f32
-                if (!(abl & 2)) m = __builtin_elementwise_max(m, s16x2{0, 0});
-                P[j] = __builtin_bit_cast(unsigned, m);
+            const auto s0 = __builtin_amdgcn_permlane32_swap(Pk[4 * pr + 0], Pk[4 * pr + 2], false, false);
+            const auto s1 = __builtin_amdgcn_permlane32_swap(Pk[4 * pr + 1], Pk[4 * pr + 3], false, false);
+            u32x4 ou = {s0[0], s1[0], s0[1], s1[1]};  // this lane's 8 consecutive channels 32 ect + 16 pr + 8 h32 ..
+            if (!all_in) {  // wave-uniform: only regions on the image border select (incl. whole tiles of the zero padding)
+                ou.x = keep ? ou.x : 0u;
+                ou.y = keep ? ou.y : 0u;
+                ou.z = keep ? ou.z : 0u;
+                ou.w = keep ? ou.w : 0u;
             }
+            *reinterpret_cast<u32x4*>(rp + pr * 32) = ou;
+        };
+        auto p_epi = [&](int i, char* rb, const f32x16& acc) {
+            unsigned Pk[8];
 #pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                const auto s0 = __builtin_amdgcn_permlane32_swap(P[4 * pr + 0], P[4 * pr + 2], false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(P[4 * pr + 1], P[4 * pr + 3], false, false);
-                u32x4 ou = {s0[0], s1[0], s0[1], s1[1]};  // this lane's 8 consecutive channels 32 ect + 16 pr + 8 h32 ..
-                if (!all_in) {  // wave-uniform: only regions on the image border select (incl. whole tiles of the zero padding)
-                    ou.x = keep ? ou.x : 0u;
-                    ou.y = keep ? ou.y : 0u;
-                    ou.z = keep ? ou.z : 0u;
-                    ou.w = keep ? ou.w : 0u;
-                }
-                *reinterpret_cast<u32x4*>(rp + pr * 32) = ou;
-            }
+            for (int j = 0; j < 8; ++j) Pk[j] = e_cvt(acc, j, !(abl & 2));
+            e_out(i, rb, Pk, 0);
+            e_out(i, rb, Pk, 1);
         };
         // Straight-line, two tiles at a time: the fragment reads of BOTH tiles, then their MFMA chains, then the two epilogues -- with a
         // wave-uniform branch per tile (rows of the zero padding, a wave's missing fourth tile) every tile paid an LDS round trip and an
@@ -280,10 +264,10 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
             }
         };
 
-        // ---- stencil roles (dwmfma.hip, one output row per tile) ----
+        // ---- stencil roles (one output row per tile) ----
         const bool lane_ok = m < XE_BW && w0 + m < d.Wo && cev;
         const int rows_valid = min(XE_NT, d.Ho - h0);
-        const int ntl = rows_valid;
+        const int mrow_lim = lane_ok ? 0 : (1 << 20);  // row of this lane inside its tile, or "never valid"
         const int lbase0 = ((min(m, XE_BW - 1) * SS) * XE_SLOTS + 2 * wave + (q & 1)) * 16;
         constexpr int lstep = SS * XE_RW * XE_SLOTS * 16;
         const int ystep = d.Wo * Cp;
@@ -300,78 +284,17 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
         for (int l = 0; l < XE_NT; ++l) S0[l] = S1[l] = S2[l] = zero4;
 
         auto frame = [&](int ti, f32x4 (&P)[XE_NT], f32x4 (&C)[XE_NT], f32x4 (&N)[XE_NT]) {
-            if (wave_live && ti >= 0 && ti < Ti && !(abl & 8)) {  // wave-uniform
-                int fbo = slot_of(ti) * XE_FRB + lbase0;
-                asm volatile("" : "+v"(fbo));
-                const char* ta[5];
-#pragma unroll
-                for (int j = 0; j < 5; ++j) ta[j] = ring + fbo + tapoff[j];
-                bf16x8 Bq[2][5];
-#pragma unroll
-                for (int j = 0; j < 5; ++j) Bq[0][j] = *reinterpret_cast<const bf16x8*>(ta[j]);
-                __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-#pragma unroll
-                for (int l = 0; l < XE_NT; ++l) {
-                    if (l + 1 < XE_NT) {
-#pragma unroll
-                        for (int j = 0; j < 5; ++j) Bq[(l + 1) & 1][j] = *reinterpret_cast<const bf16x8*>(ta[j] + (l + 1) * lstep);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) {
-                        const bf16x8 B = Bq[l & 1][j];
-                        P[l] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[2][j]), B, j == 0 ? C[l] : P[l], 0, 0, 0);
-                        C[l] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[1][j]), B, j == 0 ? N[l] : C[l], 0, 0, 0);
-                        N[l] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[0][j]), B, j == 0 ? zero4 : N[l], 0, 0, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 15, 0);
-                }
-            } else {
-#pragma unroll
-                for (int l = 0; l < XE_NT; ++l) {
-                    P[l] = C[l];
-                    C[l] = N[l];
-                    N[l] = zero4;
-                }
-            }
+            if (wave_live && ti >= 0 && ti < Ti && !(abl & 8))  // wave-uniform
+                bd_chains<XE_NT, lstep, true, true, true>(ring, slot_of(ti) * XE_FRB + lbase0, tapoff, A, P, C, N);
+            else
+                bd_rotate(P, C, N);
         };
         auto emit = [&](int ti, f32x4 (&P)[XE_NT]) {  // output frame ti - 1 has now seen frames ti - 2, ti - 1, ti
             const int to = ti - 1;
             if (wave_live && to >= t0 && to < t1 && !(abl & 16)) {
                 const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(yclip + (long)to * ofs, fr_bytes);
-                // straight-line over ALL tiles, as in dwmfma.hip: a row below the plane stores out of the descriptor's range and counts nothing,
-                // the pool sums are formed whether or not the launch has a row for them, padded channels carry zero scale and bias
-                f32x4 sc, bs;
-                if (FOLD) {
-                    sc = *reinterpret_cast<const f32x4*>(scl);
-                    bs = *reinterpret_cast<const f32x4*>(scl + 64);
-                } else {
-                    sc = f32x4{sc_r[0], sc_r[1], sc_r[2], sc_r[3]};
-                    bs = f32x4{bs_r[0], bs_r[1], bs_r[2], bs_r[3]};
-                }
-#pragma unroll
-                for (int l = 0; l < XE_NT; ++l)
-                    {
-                        float v[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) v[i] = P[l][i] * sc[i] + bs[i];
-                        {
-                            const bool ok = lane_ok && l < ntl;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) psum[i] += ok ? v[i] : 0.0f;
-                        }
-                        if constexpr (ACT == PASN_ACT_SWISH) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) v[i] = v[i] * sigmoidf_(v[i]);
-                        } else if constexpr (ACT != PASN_ACT_NONE) {
-                            act_vec(v, d.act);
-                        }
-                        if (ACT == -1 && wave_tail) mask_tail(v, d.Cout - ce);  // (run-time activation: sigmoid(0) is not 0)
-                        bf16x4 o;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) o[i] = (__bf16)v[i];
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), yrsrc, (int)yvoff, l * ystep * 2, 0);
-                    }
+                const f32x4 sc = FOLD ? *reinterpret_cast<const f32x4*>(scl) : sc_r, bs = FOLD ? *reinterpret_cast<const f32x4*>(scl + 64) : bs_r;
+                bd_epilogue<ACT, false, 1, XE_NT>(P, sc, bs, f32x4{}, psum, mrow_lim, rows_valid, d.act, wave_tail ? d.Cout - ce : 4, yrsrc, yvoff, ystep * 2);
             }
         };
 
@@ -383,44 +306,12 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
             static_assert(SS != 2 || (NU == 4 && XE_NT == 3), "the pinned schedule below is written for 4 expand tiles under 3 stencil tiles");
             const char* xb = xt + slot_of(ti + 1) * g.xtb;
             char* rb = ring + slot_of(ti + 1) * XE_FRB;
-            int fbo = slot_of(ti) * XE_FRB + lbase0;
-            asm volatile("" : "+v"(fbo));
             const char* ta[5];
-#pragma unroll
-            for (int j = 0; j < 5; ++j) ta[j] = ring + fbo + tapoff[j];
+            bd_tap_addrs(ring, slot_of(ti) * XE_FRB + lbase0, tapoff, ta);
             bf16x8 Bq[2][5];
             bf16x8 xf[KS];
             f32x16 acc;
             unsigned Pk[8];
-            // the expand epilogue of tile i in ten steps: eight packed convert + ReLU pairs, two (lane swap, border mask, store) halves
-            auto e_cvt = [&](int j) {
-                f32x2 a = {acc[2 * j], acc[2 * j + 1]};
-                if (!folded) {
-                    a.x = a.x * scb[32 * ect + acc_row(2 * j, h32)] + scb[64 + 32 * ect + acc_row(2 * j, h32)];
-                    a.y = a.y * scb[32 * ect + acc_row(2 * j + 1, h32)] + scb[64 + 32 * ect + acc_row(2 * j + 1, h32)];
-                }
-                s16x2 mm = __builtin_bit_cast(s16x2, __builtin_convertvector(a, bf16x2));
-                mm = __builtin_elementwise_max(mm, s16x2{0, 0});
-                Pk[j] = __builtin_bit_cast(unsigned, mm);
-            };
-            auto e_out = [&](int i, int pr) {
-                const int tile = (wave >> 1) + 2 * i;
-                const int tl = min(tile, R::TILES - 1);
-                const int pos = tl * R::TP + min(c32, R::TP - 1);
-                const bool wr = lane_used && tile < R::TILES;
-                char* const rp = wr ? rb + (pos * XE_SLOTS + 4 * ect + h32) * 16 : dummy;
-                const bool keep = (keepm >> i) & 1u;
-                const auto s0 = __builtin_amdgcn_permlane32_swap(Pk[4 * pr + 0], Pk[4 * pr + 2], false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(Pk[4 * pr + 1], Pk[4 * pr + 3], false, false);
-                u32x4 ou = {s0[0], s1[0], s0[1], s1[1]};
-                if (!all_in) {
-                    ou.x = keep ? ou.x : 0u;
-                    ou.y = keep ? ou.y : 0u;
-                    ou.z = keep ? ou.z : 0u;
-                    ou.w = keep ? ou.w : 0u;
-                }
-                *reinterpret_cast<u32x4*>(rp + pr * 32) = ou;
-            };
             p_read(0, xb, xf);
 #pragma unroll
             for (int j = 0; j < 5; ++j) Bq[0][j] = *reinterpret_cast<const bf16x8*>(ta[j]);
@@ -445,15 +336,15 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
                 }
                 if (E < NU) {
                     if (r >= 2 && r <= 5) {
-                        e_cvt(2 * (r - 2));
-                        e_cvt(2 * (r - 2) + 1);
+                        Pk[2 * (r - 2)] = e_cvt(acc, 2 * (r - 2), true);
+                        Pk[2 * (r - 2) + 1] = e_cvt(acc, 2 * (r - 2) + 1, true);
                     }
                     if (r == 6) {
                         if (E + 1 < NU) p_mma(xf, acc);
-                        e_out(E, 0);
+                        e_out(E, rb, Pk, 0);
                     }
                     if (r == 7) {
-                        e_out(E, 1);
+                        e_out(E, rb, Pk, 1);
                         if (E + 2 < NU) p_read(E + 2, xb, xf);
                     }
                     if (r == 0 && E == 0) p_read(1, xb, xf);
@@ -488,21 +379,7 @@ __global__ __launch_bounds__(256, 2) void x3d_expdw_kernel(const __bf16* __restr
         __syncthreads();
     }
 
-    if (pool && wave_live) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float s = psum[i];
-            s += __shfl_xor(s, 1);
-            s += __shfl_xor(s, 2);
-            s += __shfl_xor(s, 4);
-            s += __shfl_xor(s, 8);
-            psum[i] = s;
-        }
-        if (m == 0 && cev) {
-            float* pr = pool + ((long)n * g.chunks + chunk) * Cp + ce;
-            *reinterpret_cast<f32x4*>(pr) = f32x4{psum[0], psum[1], psum[2], psum[3]};
-        }
-    }
+    if (pool && wave_live) bd_pool_row<false>(psum, pool + ((long)n * g.chunks + chunk) * Cp + ce, Cp, m == 0 && cev);
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
@@ -561,29 +438,10 @@ XeGeom xe_geom(const pasn_conv_desc& de, const pasn_conv_desc& d, int dtype) {
     g.CQ = ceil_div(ceil_div(d.Cout_p, 16), 4);
     g.RTH = ceil_div(d.Ho, NT);
     g.RTW = ceil_div(d.Wo, XeR<1>::BW);
-    const int regions = g.RTH * g.RTW;
     const int force_tc = tune("PASN_EXPDW_TC") ? atoi(tune("PASN_EXPDW_TC")) : 0;
     const int force_upb = tune("PASN_EXPDW_UPB") ? atoi(tune("PASN_EXPDW_UPB")) : 0;
-    double best = 1e30;
-    for (int tc = d.To;; tc = (tc + 1) / 2) {
-        const int tcu = force_tc ? std::min(force_tc, d.To) : tc;
-        const int nT = ceil_div(d.To, tcu), units = nT * regions;
-        for (int upb = 1; upb <= units; ++upb) {
-            if (force_upb && upb != std::min(force_upb, units)) continue;
-            const int chunks = ceil_div(units, upb);
-            if (chunks > 64 && upb < units && !force_upb) continue;  // the chunk count is the number of SE partial rows per clip (128: 209 vs 195 us per launch)
-            const long blocks = (long)d.N * g.CQ * chunks;
-            const double t = (double)ceil_div(blocks, 512L) * (4.0 + upb * (tcu + 3.0));
-            if (t < best) {
-                best = t;
-                g.Tc = tcu;
-                g.nT = nT;
-                g.upb = upb;
-                g.chunks = chunks;
-            }
-        }
-        if (force_tc || tc <= 4) break;
-    }
+    const TSplit ts = t_split(d.To, g.RTH * g.RTW, (long)d.N * g.CQ, 3, force_tc, force_upb);  // a unit costs Tc + 3 frames
+    g.Tc = ts.Tc, g.nT = ts.nT, g.upb = ts.upb, g.chunks = ts.chunks;
     g.bpc = g.CQ * g.chunks;
     g.abl = tune_dev("PASN_EXPDW_ABL") ? atoi(tune_dev("PASN_EXPDW_ABL")) : 0;
     g.ok = 1;

@@ -512,17 +512,36 @@ def test_conv_with_fused_strided_shortcut(inner, cout, cin2, thw, gate, monkeypa
         assert float(out[..., cout:].float().abs().max()) == 0.0, "padded channels must stay zero"
 
 
+_XE_SHAPES = [(24, 54, 2, (4, 16, 30), 2), (24, 108, 3, (5, 13, 17), 2), (24, 54, 2, (18, 12, 56), 2),
+              (16, 40, 2, (3, 7, 9), 2), (24, 54, 1, (2, 2, 3), 2), (8, 72, 2, (3, 11, 16), 2),
+              (24, 54, 2, (4, 14, 56), 1), (24, 54, 2, (18, 7, 59), 1), (16, 40, 3, (3, 13, 70), 1),
+              (24, 54, 2, (5, 56, 56), 1), (24, 54, 1, (1, 9, 57), 1), (8, 24, 2, (7, 17, 71), 1)]
+# cin, cm, n, thw, stride, act (None: Swish, or none with the pool rows), fold (False: PASN_EXPDW_FOLD=0, norm_a's scale behind the expand
+# MFMAs).  The shapes above run x3d_expdw_kernel<2,{0,3},2,false,true> and, at stride 1 behind PASN_EXPDW_TZ=0, <2,{0,3},1,false,true>; the
+# cases below pin the other six product instances (the plan's name carries <KS,ACT,SS>; FOLD follows the switch): the run-time activation
+# <2,-1,2,false,{true,false}> and the separate-scale <2,{0,3},{1,2},false,false>.
+_XE_CASES = [pytest.param(*c, None, True, id=f"{c[0]}-{c[1]}-{c[2]}-thw{i}-{c[4]}") for i, c in enumerate(_XE_SHAPES)] + [
+    pytest.param(24, 54, 1, (2, 2, 3), 2, "relu", True, id="24-54-1-223-s2-relu"),
+    pytest.param(24, 108, 3, (5, 13, 17), 2, "relu", True, id="24-108-3-51317-s2-relu"),
+    pytest.param(24, 54, 1, (2, 2, 3), 2, "relu", False, id="24-54-1-223-s2-relu-fold0"),
+    pytest.param(24, 108, 3, (5, 13, 17), 2, None, False, id="24-108-3-51317-s2-fold0"),
+    pytest.param(24, 54, 2, (4, 14, 56), 1, None, False, id="24-54-2-41456-s1-fold0")]
+
+
 @pytest.mark.parametrize("se", [False, True])
-@pytest.mark.parametrize("cin,cm,n,thw,stride", [(24, 54, 2, (4, 16, 30), 2), (24, 108, 3, (5, 13, 17), 2), (24, 54, 2, (18, 12, 56), 2),
-                                                 (16, 40, 2, (3, 7, 9), 2), (24, 54, 1, (2, 2, 3), 2), (8, 72, 2, (3, 11, 16), 2),
-                                                 (24, 54, 2, (4, 14, 56), 1), (24, 54, 2, (18, 7, 59), 1), (16, 40, 3, (3, 13, 70), 1),
-                                                 (24, 54, 2, (5, 56, 56), 1), (24, 54, 1, (1, 9, 57), 1), (8, 24, 2, (7, 17, 71), 1)])
-def test_expand_conv_and_strided_stencil_in_one_launch(cin, cm, n, thw, stride, se):
+@pytest.mark.parametrize("cin,cm,n,thw,stride,act,fold", _XE_CASES)
+def test_expand_conv_and_strided_stencil_in_one_launch(cin, cm, n, thw, stride, act, fold, se):
     """Front half of an X3D block: 1x1x1 expand conv + BN + ReLU -> depthwise 3x3x3 conv, stride (1,2,2) (a stage's first block) or stride 1
     (the blocks of planes >= 56 wide), + BN (+ Swish, or the squeeze-excite pool partial rows) in ONE launch with the expanded activation in LDS (pasn_x3d_expdw_fwd) -- against torch on the
     bf16-rounded operands and against the two launches.  Even and odd planes (the last strided row / column exists or not), planes
     smaller than a region, several regions and T chunks, two channel quads (108), block widths of 8 / 16 / 24 channels, channel counts
-    that are not multiples of 16, T = 18 (chunked march), clips of 2 frames."""
+    that are not multiples of 16, T = 18 (chunked march), clips of 2 frames; a ReLU stencil epilogue (the run-time-activation instance) and
+    norm_a's scale applied behind the expand MFMAs (PASN_EXPDW_FOLD=0: the block-diagonal kernel at either stride)."""
+    with _lib_env(PASN_EXPDW_FOLD=None if fold else "0"):
+        _expand_dw_case(cin, cm, n, thw, stride, se, act, tz=stride == 1 and fold)
+
+
+def _expand_dw_case(cin, cm, n, thw, stride, se, act, tz):
     dtype = torch.bfloat16
     torch.manual_seed(cin + cm + n)
     t, hi, wi = thw
@@ -538,11 +557,13 @@ def test_expand_conv_and_strided_stencil_in_one_launch(cin, cm, n, thw, stride, 
             b.running_mean.normal_(0, 0.3)
             b.running_var.uniform_(0.5, 1.5)
     bn_a.eval(), bn_b.eval()
-    act_b = "none" if se else "swish"
+    act_b = act or ("none" if se else "swish")
     e_ref = _rt(F.relu(bn_a(F.conv3d(_rt(x, dtype), _rt(conv_a.weight.data, dtype)))), dtype)
     pre = bn_b(F.conv3d(e_ref, _rt(conv_b.weight.data, dtype), stride=(1, stride, stride), padding=1, groups=cm)).detach()
-    ref = pre if se else pre * torch.sigmoid(pre)
+    ref = {"none": pre, "swish": pre * torch.sigmoid(pre), "relu": F.relu(pre)}[act_b]
     conv_a, conv_b, bn_a, bn_b = conv_a.to(DEV), conv_b.to(DEV), bn_a.to(DEV), bn_b.to(DEV)
+
+    want_inst = f"x3d_expdw_kernel<2,{ {'none': 0, 'swish': 3}.get(act_b, -1)},{stride}>"  # the block-diagonal kernel's instance <KS,ACT,SS>
 
     def run(fused: bool, want_kernel: str = "x3d_expdw"):
         pb = _pb(dtype)
@@ -551,6 +572,8 @@ def test_expand_conv_and_strided_stencil_in_one_launch(cin, cm, n, thw, stride, 
             out = pb.expand_dw(xa, conv_a, bn_a, conv_b, bn_b, act_b, pool=se)
             assert out is not None and pb.meta[-1]["kind"] == "expand+dwconv", "the fused launch must cover this pair"
             assert pb.meta[-1]["kernel"].startswith(want_kernel + "<"), pb.meta[-1]["kernel"]
+            if want_kernel == "x3d_expdw_kernel":
+                assert pb.meta[-1]["kernel"] == want_inst, pb.meta[-1]["kernel"]
         else:
             e = pb.conv(xa, conv_a, bn_a, act="relu")
             out = pb.dwconv(e, conv_b, bn_b, act=act_b, pool=se)
@@ -568,11 +591,11 @@ def test_expand_conv_and_strided_stencil_in_one_launch(cin, cm, n, thw, stride, 
 
     # stride 1: the Toeplitz kernel on a channel-planar image (x3d_expdw_tz.hip, round 5) is the default; the block-diagonal kernel is the
     # PASN_EXPDW_TZ=0 route -- both are held to the same bounds, and to each other
-    out, pool_f, n_f = run(True, "x3d_expdw_tz_kernel" if stride == 1 else "x3d_expdw_kernel")
+    out, pool_f, n_f = run(True, "x3d_expdw_tz_kernel" if tz else "x3d_expdw_kernel")
     two, pool_t, n_t = run(False)
     assert n_f == 1 and n_t == 2
     scale = max(1.0, float(ref.abs().max()))
-    if stride == 1:
+    if tz:
         with _lib_env(PASN_EXPDW_TZ="0"):
             old, pool_o, _ = run(True, "x3d_expdw_kernel")
         assert_close(_from_cl(out, cm), _from_cl(old, cm), 1.6e-2 * scale, 1e-2, "Toeplitz vs block-diagonal fused launch")  # one bf16 ulp
@@ -1178,16 +1201,23 @@ def _run_march(x, conv, bn, act, dtype=torch.bfloat16):
     return out, part, pb.meta[-1]["kernel"]
 
 
-@pytest.mark.parametrize("c", [24, 56, 108, 432])
-@pytest.mark.parametrize("geom", ["0,0", "4,1", "4,3", "16,2", "2,1000"])
-@pytest.mark.parametrize("thw", [(9, 11, 13), (9, 14, 22), (5, 7, 7), (4, 30, 8)])
-def test_dwconv3d_mfma_variants(thw, geom, c, monkeypatch):
+_MFMA_THW = [(9, 11, 13), (9, 14, 22), (5, 7, 7), (4, 30, 8)]
+_MFMA_CASES = [pytest.param(thw, geom, c, "swish", id=f"thw{i}-{geom}-{c}") for c in (24, 56, 108, 432)
+               for geom in ("0,0", "4,1", "4,3", "16,2", "2,1000") for i, thw in enumerate(_MFMA_THW)] + [
+    # the run-time-activation instances: two rows per tile with a partial channel tile; one row per tile, a short last quad, ragged regions
+    pytest.param((5, 7, 7), "0,0", 24, "relu", id="thw2-0,0-24-relu"), pytest.param((9, 11, 13), "0,0", 108, "relu", id="thw0-0,0-108-relu"),
+    # no activation (the squeeze-excite blocks' instances), by name
+    pytest.param((5, 7, 7), "0,0", 24, "none", id="thw2-0,0-24-none"), pytest.param((9, 11, 13), "0,0", 108, "none", id="thw0-0,0-108-none")]
+
+
+@pytest.mark.parametrize("thw,geom,c,act", _MFMA_CASES)
+def test_dwconv3d_mfma_variants(thw, geom, c, act, monkeypatch):
     """Matrix-core stencil (block-diagonal bf16 weight operands, LDS-DMA frame ring, T-marching accumulators): the cost model's own
     split and forced (T chunk, units per block) splits on ragged shapes -- T = 9 (chunk halos, partial last chunk), planes that are not
     multiples of the 4 x 14 region (ragged rows and strips), planes at most 8 wide (two output rows per position tile), channel counts
     with a partial 16-channel tile (24, 56, 108) and a short last channel quad (108, 432) -- with the Swish epilogue and SE partial
     sums, against torch; and against round 1's VALU stencil within the bf16 rounding of the weights (the only arithmetic difference:
-    fp32 accumulation in both)."""
+    fp32 accumulation in both).  With a ReLU epilogue: the instances that switch on the activation at run time; with none: the SE blocks'."""
     tc, upb = geom.split(",")
     monkeypatch.setenv("PASN_DWMFMA", "1")  # every stride-1 layer (default: only the planes at most 8 wide)
     monkeypatch.setenv("PASN_DW_TZ", "0")   # (planes 9 .. 14 wide take the Toeplitz kernel by default)
@@ -1195,16 +1225,17 @@ def test_dwconv3d_mfma_variants(thw, geom, c, monkeypatch):
         monkeypatch.setenv("PASN_DWMFMA_TC", tc)
         monkeypatch.setenv("PASN_DWMFMA_UPB", upb)
     x, conv, bn, pre = _march_case(1, c, thw=thw)
-    ref = pre * torch.sigmoid(pre)
-    out, part, kernel = _run_march(x, conv, bn, "swish")
+    ref = {"swish": pre * torch.sigmoid(pre), "relu": F.relu(pre), "none": pre}[act]
+    out, part, kernel = _run_march(x, conv, bn, act)
     assert kernel.startswith("dwconv3d_mfma_kernel<"), kernel
+    assert kernel == f"dwconv3d_mfma_kernel<{2 if thw[2] <= 8 else 1},false,{ {'none': 0, 'swish': 3, 'relu': -1}[act]}>", kernel
     atol, rtol = _tols(torch.bfloat16)
     assert_close(_from_cl(out, c), ref, atol * max(1.0, float(ref.abs().max())), rtol, f"mfma stencil {thw} {geom} c{c}")
     want = pre.sum(dim=(2, 3, 4))
     assert_close(part.sum(dim=1)[:, :c].cpu(), want, 2e-2 * float(want.abs().max()), 0, "SE partial sums")
     assert float(out[..., c:].abs().max() if out.shape[-1] > c else 0.0) == 0.0, "padded channels must stay zero"
     monkeypatch.setenv("PASN_DWMFMA", "0")  # (unset, the planes at most 8 wide take the matrix-core stencil by default)
-    out1, part1, kernel1 = _run_march(x, conv, bn, "swish")
+    out1, part1, kernel1 = _run_march(x, conv, bn, act)
     assert kernel1.startswith("dwconv3d_march_kernel<"), kernel1
     d = (out.float() - out1.float()).abs()
     assert float(d.max()) <= 2.0 ** -6 * max(1.0, float(out1.float().abs().max())), float(d.max())
