@@ -769,6 +769,53 @@ int pasn_pack_chunk(void);
 int pasn_pack_weights(const pasn_pack_job* jobs, const int* block_job, const int* block_chunk, int nblocks, void* stream);
 
 /*
+ * Training: the optimizer side of a step, ONE launch each (csrc/optim.hip).  Tables as for pasn_pack_weights: `jobs`, `block_job` and
+ * `block_chunk` are DEVICE arrays, block b works on elements [block_chunk[b], block_chunk[b] + 1) x pasn_optim_chunk() of job
+ * block_job[b].  `jobs_host` is the same job table in host memory: it is checked before the launch (a NULL pointer, n <= 0, a group index
+ * out of range, more than PASN_OPTIM_MAX_GROUPS groups, or an `nblocks` that is not the sum of the jobs' chunk counts returns
+ * PASN_ERR_ARG and launches nothing).  The check reads the host copy ONLY: that the device table holds the same jobs is the caller's
+ * business (build both from one array, as optim.py does).  Both calls are stream-ordered: no host synchronisation, no allocation, no pointer kept after the
+ * return.  16-byte accesses when every pointer of a job is 16-byte aligned, 4-byte accesses otherwise (views at odd storage offsets).
+ *
+ * pasn_adam_step replaces `optimizer.step()` of the reference's loop (Video_XProtoNet_e2e.py:137-142) for torch.optim.Adam with
+ * amsgrad = maximize = decoupled_weight_decay = False, over the parameter groups of XProtoNet_e2e.py:36-82, per parameter:
+ *   t += 1;  g += wd p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ * in torch's order of fp32 operations (lerp, mul + addcmul, sqrt / div / add, addcdiv), the scalars formed in double.  A parameter
+ * without a gradient has no job: its moments and its t do not move.  `groups` is read at the call (host memory, passed to the kernel by
+ * value): a learning rate a scheduler rewrote between two steps is seen by the next one.
+ *   step : one 8-byte word per parameter in device memory, zero before the first step: t in the low 32 bits; the high 32 bits hold
+ *          the `stamp` of the call that last advanced it.  The kernel advances t itself.  `stamp` must be non-zero and differ from
+ *          the previous call's (a call counter): it is how the blocks of one job agree on t while one of them stores t + 1.
+ *
+ * pasn_grad_accumulate: dst[i] += src[i] (one fp32 add per element, bitwise `dst.add_(src)`) for every job: the reference's undivided
+ * accumulation over micro-batches (Video_XProtoNet_e2e.py:137-142) for the gradients that do not lie in one flat span (those take
+ * pasn_add_inplace).
+ */
+#define PASN_OPTIM_MAX_GROUPS 8
+typedef struct pasn_adam_group {
+    double lr, beta1, beta2, eps, weight_decay;
+} pasn_adam_group;
+typedef struct pasn_adam_job {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    unsigned long long* step;
+    long n;
+    int group, reserved;
+} pasn_adam_job;
+typedef struct pasn_accum_job {
+    float* dst;
+    const float* src;
+    long n;
+} pasn_accum_job;
+int pasn_optim_chunk(void);
+int pasn_adam_step(const pasn_adam_job* jobs, const pasn_adam_job* jobs_host, int njobs, const int* block_job, const int* block_chunk,
+                   int nblocks, const pasn_adam_group* groups, int ngroups, unsigned stamp, void* stream);
+int pasn_grad_accumulate(const pasn_accum_job* jobs, const pasn_accum_job* jobs_host, int njobs, const int* block_job, const int* block_chunk,
+                         int nblocks, void* stream);
+
+/*
  * Data-parallel gradient exchange on RCCL (xGMI), without torch.distributed in the data path: ONE in-place sum all-reduce of the
  * flat fp32 gradient bucket per optimizer step.  The reference trains on one GPU and has no collective
  * (SURVEY section 0); these four calls are what a trainer needs around protoasnet_amd/dp.py.  librccl.so is resolved at run time.

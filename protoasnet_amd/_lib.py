@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_uint, c_void_p
 
 F32, BF16, U8, I32 = 0, 1, 2, 3
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "swish": 3, "abs": 4}
@@ -32,6 +32,13 @@ class ProtoLossDesc(ctypes.Structure):
                 + [(n, c_int32) for n in ("ce_mode", "ce_reduction", "cluster_reduction", "sep_reduction", "sep_abstain", "patch", "ortho_mode",
                                           "map_p", "map_reduction", "fc_p", "map_dtype")]
                 + [(n, c_float) for n in ("w_ce", "ab_weight", "w_cluster", "w_sep", "w_ortho", "w_map", "w_fc")])
+
+
+OPTIM_MAX_GROUPS = 8  # PASN_OPTIM_MAX_GROUPS
+
+
+class AdamGroup(ctypes.Structure):
+    _fields_ = [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
 
 
 # name -> (restype, argtypes); every symbol the header declares
@@ -153,6 +160,10 @@ SIGNATURES = {
     # ---- the training loss recipe (losses.FusedCriterion)
     "pasn_proto_loss_fwd": (c_int, [c_void_p] * 13 + [POINTER(ProtoLossDesc), c_void_p]),
     "pasn_proto_loss_bwd": (c_int, [c_void_p] * 14 + [POINTER(ProtoLossDesc), c_void_p]),
+    # ---- the optimizer side of a training step (optim.py)
+    "pasn_optim_chunk": (c_int, []),
+    "pasn_adam_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(AdamGroup), c_int, c_uint, c_void_p]),
+    "pasn_grad_accumulate": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     # ---- raw cine windows -> model clips (resample.py)
     "pasn_cine_resize_pixels_per_block": (c_int, [c_int]),
     "pasn_cine_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p] + [c_int] * 10 + [c_float] * 2 + [c_int] * 2 + [c_void_p]),

@@ -40,6 +40,9 @@ reference's per-clip prediction CSV (``save_dir/csv_<mode>/e<epoch>_f1_<f1>.csv`
 the one per-epoch all-reduce, the AUC sees every rank's rows (one ``all_gather``), and the CSV rows reach rank 0 rank-major: rank 0's
 clips in its loader order, then rank 1's, and so on.  ``evaluate(mode)`` is the reference's ``eval_only`` entry (main.py:52-53).
 
+``train.fused_optimizer`` (not a key of the reference's configs; default off): Adam's update as one library call per optimizer step and
+the micro-batches' gradients summed in at most two (``protoasnet_amd.optim``); ``p.grad`` is ``None`` between micro-batches then.
+
 Out of scope: wandb, plots, the ``classification_report`` text.
 """
 from __future__ import annotations
@@ -195,6 +198,17 @@ class DPTrainer:
             ]
         else:
             raise ValueError(f"optimizer mode {mode} not valid.")
+        # train.fused_optimizer (not a key of the reference's configs; default off): the same groups under optim.FlatAdam -- one library
+        # call per optimizer step -- and the micro-batches' gradients summed by optim.GradAccumulator instead of autograd's per-tensor adds
+        self.accumulator = None
+        if self.train_config.get("fused_optimizer", False):
+            if name != "Adam":
+                raise ValueError(f"train.fused_optimizer implements Adam, the optimizer of the reference's configs; optimizer.name is {name!r}")
+            from . import optim
+
+            self.optimizer = optim.FlatAdam(specs)
+            self.accumulator = optim.GradAccumulator(p for g in self.optimizer.param_groups for p in g["params"])
+            return
         self.optimizer = torch.optim.__dict__[name](specs)
 
     def get_lr_scheduler(self):
@@ -364,10 +378,16 @@ class DPTrainer:
                 if mode == "train":
                     self._norm_dirty = True  # this rank's running statistics moved on their own
                     loss.backward()  # undivided, as the reference accumulates it
+                    if self.accumulator is not None:
+                        self.accumulator.absorb()  # p.grad is None from here to the boundary: the accumulator holds the sums
                     if (i + 1) % self.local_accumulation == 0:
+                        if self.accumulator is not None:
+                            self.accumulator.materialize()
                         dp.allreduce_gradients(self.params, average=False)  # ONE exchange per optimizer step: SUM over ranks
                         self.optimizer.step()
                         self.optimizer.zero_grad(set_to_none=True)
+                        if self.accumulator is not None:
+                            self.accumulator.reset()
                     self.current_iteration += 1
         stats = torch.cat([cm.float(), loss_sum, torch.tensor([float(n_batches)], device=self.device)])
         evm = None

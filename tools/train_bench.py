@@ -9,7 +9,10 @@ Loss (``--loss reference``, default): the recipe of src/configs/Ours_ProtoASNet_
 (Video_XProtoNet_e2e.py:88-100) -- CeLoss (mean) + 0.8 ClusterRoiFeat + 0.08 SeparationRoiFeat + 1e-3 TransformLoss (a SECOND trunk
 pass, with gradients, over the affinely warped clip: model.compute_occurence_map) + 1e-4 L1 of the last layer's off-class weights;
 ``--loss simple`` keeps one pass (cross entropy + L1 of the maps + a cluster term).  protoasnet_amd.losses supplies the classes.
-The optimizer is torch.optim.Adam (lr 1e-4) as in the reference's agents (Video_XProtoNet_e2e.py:36-62)."""
+The optimizer is torch.optim.Adam (lr 1e-4) as in the reference's agents (Video_XProtoNet_e2e.py:36-62); ``--optimizer flat`` takes the
+library's (optim.FlatAdam, gradients summed over micro-batches by optim.GradAccumulator).  ``--accumulate K``: K micro-batches per optimizer
+step, undivided (Video_XProtoNet_e2e.py:137-142); a "step" is then K forward + backward passes and one update.  ``--ab-blocks B``: after
+the timed region, B blocks of ``--steps`` steps of each optimizer, alternating on the one model in the one process (``optimizer_ab``)."""
 import argparse
 import json
 import os
@@ -35,6 +38,9 @@ def main(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--per-op", default="", help="write per-launch device times of one step to this file")
     ap.add_argument("--loss", default="reference", choices=["reference", "reference_two_passes", "simple"])
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "flat"])
+    ap.add_argument("--accumulate", type=int, default=1, help="micro-batches per optimizer step")
+    ap.add_argument("--ab-blocks", type=int, default=0, help="alternating blocks of each optimizer after the timed region")
     args = ap.parse_args(argv)
     import bench  # repo root: the rank launcher / process-group set-up shared with the forward benchmark
 
@@ -58,6 +64,11 @@ def main(argv=None):
     labels = torch.randint(0, 3, (args.batch,), generator=torch.Generator().manual_seed(rank)).to(dev)
     params = [p for p in model.parameters() if p.requires_grad]
     opt = torch.optim.Adam(params, lr=1e-4)
+    flat_opt = accum = None
+    if args.optimizer == "flat" or args.ab_blocks > 0:
+        from protoasnet_amd import optim as O
+
+        flat_opt, accum = O.FlatAdam(params, lr=1e-4), O.GradAccumulator(params)
     ident = model.prototype_class_identity.to(dev)
     from protoasnet_amd import losses as L
 
@@ -69,23 +80,33 @@ def main(argv=None):
 
     random.seed(1234 + rank)
 
-    def step():
-        opt.zero_grad(set_to_none=True)
+    def micro_loss():
         if args.loss == "reference":  # the transform term's second trunk pass in the forward's launch list (model.forward_pair)
             (logits, sim, occ), t_loss = trans.paired_forward(x, model)
-            loss = (ce.compute(logits, labels) + cluster.compute(sim, labels) + separation.compute(sim, labels)
+            return (ce.compute(logits, labels) + cluster.compute(sim, labels) + separation.compute(sim, labels)
                     + t_loss + fc_l1.compute(model.last_layer.weight))
-        elif args.loss == "reference_two_passes":  # ... as a second pass (model.compute_occurence_map, loss.py:302)
+        if args.loss == "reference_two_passes":  # ... as a second pass (model.compute_occurence_map, loss.py:302)
             logits, sim, occ = model(x)
-            loss = (ce.compute(logits, labels) + cluster.compute(sim, labels) + separation.compute(sim, labels)
+            return (ce.compute(logits, labels) + cluster.compute(sim, labels) + separation.compute(sim, labels)
                     + trans.compute(x, occ, model) + fc_l1.compute(model.last_layer.weight))
-        else:
-            logits, sim, occ = model(x)
-            own = ident[:, labels].t()  # (N, P): prototypes of the clip's class
-            loss = F.cross_entropy(logits, labels) + 1e-3 * occ.abs().mean() + 0.1 * ((1 - sim) * own).sum(1).mean()
-        loss.backward()
+        logits, sim, occ = model(x)
+        own = ident[:, labels].t()  # (N, P): prototypes of the clip's class
+        return F.cross_entropy(logits, labels) + 1e-3 * occ.abs().mean() + 0.1 * ((1 - sim) * own).sum(1).mean()
+
+    def step(kind=args.optimizer):
+        flat = kind == "flat"
+        (flat_opt if flat else opt).zero_grad(set_to_none=True)
+        for _ in range(args.accumulate):
+            loss = micro_loss()
+            loss.backward()
+            if flat:
+                accum.absorb()
+        if flat:
+            accum.materialize()
         dp.allreduce_gradients(params)
-        opt.step()
+        (flat_opt if flat else opt).step()
+        if flat:
+            accum.reset()
         return loss
 
     def barrier():
@@ -106,6 +127,24 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(loss), "non-finite loss"
+    ab = None
+    if args.ab_blocks > 0:  # both optimizers update the one set of parameters: a timing comparison, not a training run
+        import statistics
+
+        for kind in ("torch", "flat", "torch", "flat"):
+            step(kind)
+        ms = {"torch": [], "flat": []}
+        for b in range(2 * args.ab_blocks):
+            kind = ("torch", "flat")[b & 1]
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step(kind)
+            barrier()
+            ms[kind].append(round((time.perf_counter() - t0) / args.steps * 1e3, 3))
+        ab = {"steps_per_block": args.steps, "ms_per_step_blocks": ms, "median_ms": {k: round(statistics.median(v), 3) for k, v in ms.items()},
+              "spread_ms": {k: round(max(v) - min(v), 3) for k, v in ms.items()},
+              "library_calls": {"adam_step": flat_opt.library_calls, "accumulate": accum.library_calls}}
     exchange = _time_exchange(params, world, dev) if world > 1 else None
     if rank == 0 and os.environ.get("PASN_TB_TORCHPROF"):
         # which torch-side ops (weight repacking, gradient accumulation, optimizer) a step issues, with their Python call sites
@@ -160,7 +199,7 @@ def main(argv=None):
     if rank == 0:
         plan = runner.plan
         print(json.dumps({
-            "metric": "clips/sec train step", "value": round(args.batch * world * args.steps / elapsed, 2), "unit": "clips/s",
+            "metric": "clips/sec train step", "value": round(args.batch * args.accumulate * world * args.steps / elapsed, 2), "unit": "clips/s",
             "n_gpus": world, "ranks_seen": ranks_seen, "collective_backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
@@ -172,6 +211,7 @@ def main(argv=None):
             "naive_bytes": plan.naive_bytes, "grad_bucket_bytes": plan.gsize * 4, "loss": round(float(loss.detach()), 5),
             "max_memory_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 2),
             "roofline": roofline, "device_ms_by_entry_point": per_entry, "exchange": exchange,
+            "optimizer": args.optimizer, "accumulate": args.accumulate, "optimizer_ab": ab,
         }))
     if world > 1:
         dist.destroy_process_group()
