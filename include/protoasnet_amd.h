@@ -532,6 +532,19 @@ int pasn_conv3d_wgrad(const void* x, const void* dy, float* dw, const pasn_conv_
  * gradient is then accumulated per row partition into ws and the partitions are summed in index order -- deterministic, no atomics. */
 size_t pasn_conv3d_wgrad_workspace_bytes(const pasn_conv_desc* d, int dtype);
 int pasn_conv3d_wgrad_ws(const void* x, const void* dy, float* dw, const pasn_conv_desc* d, int dtype, void* ws, void* stream);
+/* Which kernel instance pasn_conv3d_wgrad (has_ws = 0) / pasn_conv3d_wgrad_ws with a workspace (has_ws = 1) runs for this geometry:
+ * arm * 100000 + mode * 10000 + A * 100 + B with
+ *   arm 1 = conv_wgrad_kernel<T, PW>           A = dtype (0 fp32, 1 bf16), B = 1 where the window map is the identity   (atomics)
+ *   arm 2 = pw_wgrad_bf16_kernel<KT, TPW>      A = KT (128 | 32 rows per step), B = TPW (tiles per wave: 1 | 2 | 4 | 8)  (atomics)
+ *   arm 3 = pw_wgrad_tile_kernel<COT, CIT>     A = COT, B = CIT (tiles per wave along co / ci: 101 | 201 | 102)          (atomics)
+ *   arm 4 = conv_wgrad_halo_kernel<COT, PW>    A = COT (1..3), B = PW (1..3); mode 0 = (1,3,3) taps, 1 = (3,1,1) taps    (partial buffer)
+ *   arm 5 = conv_wgrad_gather_kernel                                                                                    (partial buffer)
+ * e.g. 212804 = pw_wgrad_bf16_kernel<128, 4>, 410301 = the halo kernel <3, 1> on temporal taps; 0 on a NULL descriptor.
+ * pasn_conv3d_wgrad_row_parts: bits 0..31 = the row partitions of that launch -- the fp32 adds every dw element receives in the
+ * atomic arms (up to 2 the sum has one value whatever order the atomics take), the partitions summed in index order in the
+ * partial-buffer arms; bits 32.. = the blocks of the launch's grid.  For tests, profilers and benchmarks. */
+int pasn_conv3d_wgrad_variant(const pasn_conv_desc* d, int dtype, int has_ws);
+long pasn_conv3d_wgrad_row_parts(const pasn_conv_desc* d, int dtype, int has_ws);
 /* ws: NULL, or pasn_first_conv_wgrad_workspace_bytes(d, dtype) bytes (non-zero for bf16): the clip's windows are then gathered once
  * into im2col rows and the gradient runs on the LDS-transposed bf16 MFMA kernel instead of the per-element gather. */
 size_t pasn_first_conv_wgrad_workspace_bytes(const pasn_conv_desc* d, int dtype);

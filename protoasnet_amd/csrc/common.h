@@ -242,9 +242,6 @@ int launch_first_conv_mfma(const void* x, const void* wq, const float* scale, co
 int x3d_stem_mfma_supported(const pasn_conv_desc& d, int out_dtype);
 int launch_x3d_stem_mfma(const void* x, const void* wq, const float* scale, const float* bias, void* y, const pasn_conv_desc& d, int in_dtype,
                          float in_a, float in_b, hipStream_t s);
-// wgrad_halo.hip: weight gradient of the stride-1 "same" (1,3,3) / (3,1,1) convs (bf16) through a partial buffer; 0 bytes = not covered
-size_t wgrad_halo_workspace_bytes(const pasn_conv_desc& d, int dtype);
-bool wgrad_halo(const void* x, const void* dy, float* dw, void* ws, const pasn_conv_desc& d, int dtype, hipStream_t s);
 // igemm_halo.hip: the same for stride-1 "same" (1,k,k) / (3,1,1) layers with the activation halo tile kept in LDS across the taps
 int igemm_halo_mode(const pasn_conv_desc& d);
 bool igemm_halo_fits(const pasn_conv_desc& d, int mode, int nt, int mt);
@@ -257,7 +254,7 @@ int launch_gemm_pw(const void* x, const void* w, const float* scale, const float
                    void* y, const pasn_conv_desc& d, hipStream_t s);
 
 // ---- routes (DESIGN.md "Routes"): which kernel a launch takes and the geometry it needs, decided by ONE function per family; probes,
-// sizing and launches read a route and nothing else.  (The weight-gradient routes are private to wgrad.hip.)
+// sizing and launches read a route and nothing else.  (The dense weight gradient's: wgrad_tile.h; the depthwise one's is private to dw_wgrad.hip.)
 inline pasn_conv_desc frag_major(pasn_conv_desc d) { return d.w_frag = 1, d; }  // the layer with its weights packed fragment-major
 // `unpacked`: asked before the host has packed the weights (it packs what the answer needs): the fragment-major kernels are open whatever
 // d.w_frag says.  The fields after arm are those of the arm taken.

@@ -18,35 +18,9 @@
 //   * no atomics: a block stores its tiles to partial[partition][tap][co][ci] (contiguous 128-byte runs) and conv_wgrad_reduce_kernel sums
 //     the partitions in index order into dW[co][ci][tap] -- deterministic, and the 36-byte scatter happens once on 83 k values instead of
 //     once per partition.
-#include "common.h"
+#include "wgrad_tile.h"
 
 namespace pasn {
-
-constexpr int WH_KT = 128;
-
-__device__ __forceinline__ void wh_transpose8x8(const uint4 (&in)[8], uint4 (&out)[8]) {
-    const unsigned* I = reinterpret_cast<const unsigned*>(in);
-    unsigned* O = reinterpret_cast<unsigned*>(out);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const unsigned lo = I[(2 * p) * 4 + q], hi = I[(2 * p + 1) * 4 + q];
-            O[(2 * q) * 4 + p] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-            O[(2 * q + 1) * 4 + p] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);
-        }
-}
-
-struct WhGeom {
-    int mode;        // 0: (1,3,3) spatial taps, 1: (3,1,1) temporal taps
-    int taps;        // 9 | 3
-    int HAL;         // mode 0: halo rows either side of a copy (multiple of 64, >= W); mode 1: 0
-    int L;           // rows per copy (WH_KT + 2 HAL)
-    int pitchA, pitchB;
-    int co_tiles, ci_tiles, co_groups, ci_groups;
-    int rows_per_block, parts;
-    int Cout_r, Cin_r;  // padded extents of the partial buffer
-};
 
 template <int COT, int PW>
 __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ dy, float* __restrict__ partial,
@@ -98,8 +72,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const __bf16* __re
     const int dy_cgs = COT * 4, dy_units = (WH_KT / 8) * dy_cgs;
     const int x_oct = g.L / 8, x_units = 3 * x_oct * 8;
     const int units = dy_units + x_units;  // <= 1024 (host-checked)
-    int u_dst[2];                 // LDS byte offset (an int: a pointer kept in a register array loses its address space and every
-                                  // access through it becomes a flat_load / flat_store), -1 = no unit
+    int u_dst[2];                 // LDS byte offset (wg_stage), -1 = no unit
     int u_pitch[2], u_cp[2];      // u_cp: -1 = dy patch, 0..2 = x copy
     int u_row[2];                 // source row of the patch's first row in the CURRENT step (32-bit: the host bounds rows * channels by 2^31)
     int u_ch[2];                  // first channel of the patch, -1 = zeros (channel group past the tensor / no unit)
@@ -154,12 +127,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const __bf16* __re
             const __bf16* src = (u_cp[v] < 0 ? dy : x) + (chok ? u_ch[v] : 0);
             const int s0 = u_row[v];
             if (u_cp[v] < 0) {  // dy rows of this partition
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const bool ok = chok && s0 + i < r1i;
-                    pre[i] = *reinterpret_cast<const uint4*>(src + (ok ? s0 + i : r0i) * u_rowlen[v]);
-                    okbits |= (ok ? 1u : 0u) << i;
-                }
+                wg_load8<int>(src, s0, r1i, r0i, chok, u_rowlen[v], pre, okbits);
             } else {
                 // x rows of copy cp; a row is zero when its column (mode 0) / frame (mode 1) is the one that only a wrapped tap would read
                 const int period = g.mode == 0 ? W : T;
@@ -194,15 +162,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const __bf16* __re
                 }
             }
             u_row[v] += WH_KT;
-            if (u_dst[v] >= 0) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (!((okbits >> i) & 1u)) pre[i] = make_uint4(0, 0, 0, 0);
-                uint4 out[8];
-                wh_transpose8x8(pre, out);
-#pragma unroll
-                for (int c = 0; c < 8; ++c) *reinterpret_cast<uint4*>(lds + u_dst[v] + c * u_pitch[v]) = out[c];
-            }
+            if (u_dst[v] >= 0) wg_stage(lds, u_dst[v], u_pitch[v], pre, okbits);
         }
         if (g.mode == 0 && tid < WH_KT / 8) {  // rows whose tap row b = 0 / b = 2 leaves the image: bit i of byte [sel][octet] = row valid
             unsigned m0 = 0, m2 = 0;
@@ -258,18 +218,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_halo_kernel(const __bf16* __re
 #pragma unroll
     for (int i = 0; i < PW; ++i) {
         if (!p_ok[i]) continue;
-        const int ci = ci0 + p_ci[i] * 32 + m;
-        float* base = partial + (((size_t)blockIdx.x * g.taps + p_tap[i]) * g.Cout_r) * g.Cin_r + ci;
 #pragma unroll
-        for (int c = 0; c < COT; ++c) {
-            if ((blockIdx.y * COT + c) < g.co_tiles) {
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int co = co0 + c * 32 + acc_row(reg, h);
-                    base[(size_t)co * g.Cin_r] = acc[i][c][reg];
-                }
-            }
-        }
+        for (int c = 0; c < COT; ++c)
+            if ((blockIdx.y * COT + c) < g.co_tiles)
+                wg_tile_store(partial, acc[i][c], blockIdx.x, g.taps, p_tap[i], co0 + c * 32, ci0 + p_ci[i] * 32 + m, h, g.Cout_r, g.Cin_r);
     }
 }
 
@@ -302,7 +254,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __r
 // (deterministic) instead of atomics 36 bytes apart.  pw_wgrad_bf16_kernel took 1.08 ms for the 64 -> 230 (1,3,3) stride-2 layer.
 __global__ __launch_bounds__(256) void conv_wgrad_gather_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ dy, float* __restrict__ partial,
                                                                 pasn_conv_desc d, int ci_pairs, int rows_per_block, int Cout_r, int Cin_r) {
-    constexpr int PITCH = WH_KT * 2 + 16;
+    constexpr int PITCH = WH_KT * 2 + 16, SLOTS = WH_KT / 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* const At = lds;                         // [64 co channels][PITCH]
     unsigned char* const Bt = lds + (size_t)64 * PITCH;    // [64 ci channels][PITCH]
@@ -322,7 +274,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_gather_kernel(const __bf16* __
     const int ch = (is_a ? co0 : ci0) + cg * 8;
     const bool ch_ok = ch < cp;
     const __bf16* src = (is_a ? dy : x) + (ch_ok ? ch : 0);
-    const int dst = (is_a ? 0 : 64 * PITCH) + (cg * 8) * PITCH + ((r8 + cg) & (WH_KT / 8 - 1)) * 16;  // slot rotation: see wgrad.hip (wg_slot)
+    const int dst = (is_a ? 0 : 64 * PITCH) + (cg * 8) * PITCH + wg_slot(r8, cg, SLOTS) * 16;
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
@@ -332,12 +284,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_gather_kernel(const __bf16* __
         unsigned okbits = 0;
         const int rr = rb + r8 * 8;
         if (is_a) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const bool ok = ch_ok && rr + i < r1;
-                pre[i] = *reinterpret_cast<const uint4*>(src + (ok ? rr + i : r0) * cp);
-                okbits |= (ok ? 1u : 0u) << i;
-            }
+            wg_load8<int>(src, rr, r1, r0, ch_ok, cp, pre, okbits);
         } else {
             // output position of the patch's first row, then one position per row
             const int rc = min(rr, R - 1);
@@ -364,142 +311,37 @@ __global__ __launch_bounds__(256) void conv_wgrad_gather_kernel(const __bf16* __
                 }
             }
         }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (!((okbits >> i) & 1u)) pre[i] = make_uint4(0, 0, 0, 0);
-        uint4 out[8];
-        wh_transpose8x8(pre, out);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) *reinterpret_cast<uint4*>(lds + dst + c * PITCH) = out[c];
+        wg_stage(lds, dst, PITCH, pre, okbits);
         __syncthreads();
 #pragma unroll
         for (int kk = 0; kk < WH_KT / 16; ++kk) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8*>(At + (size_t)(tco * 32 + m) * PITCH + ((kk * 2 + h + tco * 4 + (m >> 3)) & (WH_KT / 8 - 1)) * 16);
-            const bf16x8 b = *reinterpret_cast<const bf16x8*>(Bt + (size_t)(tci * 32 + m) * PITCH + ((kk * 2 + h + tci * 4 + (m >> 3)) & (WH_KT / 8 - 1)) * 16);
+            const bf16x8 a = wg_frag<SLOTS>(At, PITCH, tco, m, kk * 2 + h);
+            const bf16x8 b = wg_frag<SLOTS>(Bt, PITCH, tci, m, kk * 2 + h);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
         }
         __syncthreads();
     }
     // partial[part][tap][co][ci]
     const int ci = ci0 + tci * 32 + m;
-    if (ci < Cin_r && co0 + tco * 32 < Cout_r) {
-        float* base = partial + (((size_t)blockIdx.x * taps + tap) * Cout_r) * Cin_r + ci;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) base[(size_t)(co0 + tco * 32 + acc_row(reg, h)) * Cin_r] = acc[reg];
+    if (ci < Cin_r && co0 + tco * 32 < Cout_r) wg_tile_store(partial, acc, blockIdx.x, taps, tap, co0 + tco * 32, ci, h, Cout_r, Cin_r);
+}
+
+// the route's HALO / GATHER arm into the partial buffer ws, then the partitions summed in index order into dw
+void wgrad_partial_launch(const WgradRoute& r, const void* x, const void* dy, float* dw, void* ws, const pasn_conv_desc& d, hipStream_t s) {
+    const __bf16 *xb = (const __bf16*)x, *dyb = (const __bf16*)dy;
+    if (r.arm == WgradRoute::GATHER) {
+        hipLaunchKernelGGL(conv_wgrad_gather_kernel, r.grid, dim3(256), r.lds, s, xb, dyb, (float*)ws, d, r.ci_split, r.rows_per_block, r.Cout_r, r.Cin_r);
     }
-}
-
-struct WgGather {
-    int taps, co_pairs, ci_pairs, rows_per_block, parts, Cout_r, Cin_r;
-};
-
-static bool wgrad_gather_geom(const pasn_conv_desc& d, int dtype, WgGather& g) {
-    if (const char* e = tune("PASN_NO_WGRAD_GATHER"))
-        if (e[0] == '1') return false;
-    if (dtype != PASN_BF16 || d.Cin_p % 8 || d.Cout_p % 8) return false;
-    g.taps = d.kt * d.kh * d.kw;
-    const bool strided = d.st != 1 || d.sh != 1 || d.sw != 1;
-    const bool det = tune("PASN_WGRAD_DET") ? atoi(tune("PASN_WGRAD_DET")) != 0 : false;
-    if (g.taps == 1 && !strided && !det) return false;  // plain pointwise layers keep their (atomic) kernels unless asked
-    if (g.taps > 27) return false;
-    const long R = (long)d.N * d.To * d.Ho * d.Wo, Rin = (long)d.N * d.Ti * d.Hi * d.Wi;
-    if (R * d.Cout_p >= (1L << 31) || Rin * d.Cin_p >= (1L << 31)) return false;
-    const int co_tiles = ceil_div(d.Cout_p, 32), ci_tiles = ceil_div(d.Cin_p, 32);
-    g.co_pairs = ceil_div(co_tiles, 2);
-    g.ci_pairs = ceil_div(ci_tiles, 2);
-    g.Cout_r = g.co_pairs * 64;
-    g.Cin_r = g.ci_pairs * 64;
-    const long gy = (long)g.co_pairs * g.ci_pairs * g.taps;
-    // about 2048 blocks, at least two 128-row steps each, at most 48 MB of partials
-    const long per_part = (long)g.taps * g.Cout_r * g.Cin_r * 4;
-    long parts = std::max<long>(1, std::min<long>(std::min<long>((48L << 20) / per_part, 2048 / gy + 1), R / (2 * WH_KT)));
-    const long rpb = (ceil_div(R, parts) + WH_KT - 1) / WH_KT * WH_KT;
-    g.rows_per_block = (int)rpb;
-    g.parts = (int)ceil_div(R, rpb);
-    return true;
-}
-
-bool wgrad_halo_geom(const pasn_conv_desc& d, int dtype, WhGeom& g) {
-    if (const char* e = tune("PASN_NO_WGRAD_HALO"))
-        if (e[0] == '1') return false;
-    if (dtype != PASN_BF16) return false;
-    if (d.st != 1 || d.sh != 1 || d.sw != 1 || d.To != d.Ti || d.Ho != d.Hi || d.Wo != d.Wi) return false;
-    if (d.kt == 1 && d.pt == 0 && d.kh == 3 && d.kw == 3 && d.ph == 1 && d.pw == 1 && d.Wi % 2 == 0) g.mode = 0;
-    else if (d.kt == 3 && d.pt == 1 && d.kh == 1 && d.kw == 1 && d.ph == 0 && d.pw == 0) g.mode = 1;
-    else return false;
-    if (d.Cin_p % 8 || d.Cout_p % 8) return false;
-    const long M = (long)d.N * d.To * d.Ho * d.Wo;
-    if (M * d.Cin_p >= (1L << 31) || M * d.Cout_p >= (1L << 31)) return false;
-    g.taps = g.mode == 0 ? 9 : 3;
-    g.HAL = g.mode == 0 ? (d.Wi + 63) / 64 * 64 : 0;  // L a multiple of 128: copy pitch = 4 dwords mod 64 banks
-    g.L = WH_KT + 2 * g.HAL;
-    g.pitchA = WH_KT * 2 + 16;
-    g.pitchB = g.L * 2 + 16;
-    g.co_tiles = ceil_div(d.Cout_p, 32);
-    g.ci_tiles = ceil_div(d.Cin_p, 32);
-    g.Cout_r = g.co_tiles * 32;
-    g.Cin_r = g.ci_tiles * 32;
-    return true;
-}
-
-static int wh_cot(const WhGeom& g) { return g.co_tiles >= 3 ? 3 : g.co_tiles; }
-static size_t wh_lds(const WhGeom& g, int cot) { return (size_t)cot * 32 * g.pitchA + (size_t)3 * 64 * g.pitchB + 2 * (WH_KT / 8); }
-
-static void wh_partition(const pasn_conv_desc& d, WhGeom& g) {
-    const int cot = wh_cot(g);
-    g.co_groups = ceil_div(g.co_tiles, cot);
-    g.ci_groups = ceil_div(g.ci_tiles, 2);
-    const long M = (long)d.N * d.To * d.Ho * d.Wo;
-    // one block per CU (LDS); about two rounds of blocks, at least two 128-row steps each, at most 256 partitions (partial buffer)
-    long parts = std::max<long>(1, std::min<long>(std::min<long>(256, 512 / ((long)g.co_groups * g.ci_groups) + 1), M / (2 * WH_KT)));
-    long rpb = (ceil_div(M, parts) + WH_KT - 1) / WH_KT * WH_KT;
-    g.rows_per_block = (int)rpb;
-    g.parts = (int)ceil_div(M, rpb);
-}
-
-size_t wgrad_halo_workspace_bytes(const pasn_conv_desc& d, int dtype) {
-    WhGeom g{};
-    if (!wgrad_halo_geom(d, dtype, g)) {
-        WgGather q{};
-        return wgrad_gather_geom(d, dtype, q) ? (size_t)q.parts * q.taps * q.Cout_r * q.Cin_r * sizeof(float) : 0;
-    }
-    if (wh_lds(g, wh_cot(g)) > 160 * 1024 || (WH_KT / 8) * wh_cot(g) * 4 + 3 * (g.L / 8) * 8 > 1024) return 0;
-    wh_partition(d, g);
-    return (size_t)g.parts * g.taps * g.Cout_r * g.Cin_r * sizeof(float);
-}
-
-bool wgrad_halo(const void* x, const void* dy, float* dw, void* ws, const pasn_conv_desc& d, int dtype, hipStream_t s) {
-    WhGeom g{};
-    if (!ws) return false;
-    if (!wgrad_halo_geom(d, dtype, g)) {
-        WgGather q{};
-        if (!wgrad_gather_geom(d, dtype, q)) return false;
-        const dim3 grid(q.parts, q.co_pairs * q.ci_pairs, q.taps);
-        hipLaunchKernelGGL(conv_wgrad_gather_kernel, grid, dim3(256), (size_t)128 * (WH_KT * 2 + 16), s, (const __bf16*)x, (const __bf16*)dy, (float*)ws, d,
-                           q.ci_pairs, q.rows_per_block, q.Cout_r, q.Cin_r);
-        const long total = (long)q.taps * d.Cout * d.Cin;
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)ceil_div(total, 256L)), dim3(256), 0, s, (const float*)ws, dw, q.parts, q.taps, d.Cout,
-                           d.Cin, q.Cout_r, q.Cin_r);
-        return true;
-    }
-    const int cot = wh_cot(g);
-    const size_t lds = wh_lds(g, cot);
-    if (lds > 160 * 1024 || (WH_KT / 8) * cot * 4 + 3 * (g.L / 8) * 8 > 1024) return false;
-    wh_partition(d, g);
-    const int pairs = std::min(2, g.ci_tiles) * g.taps;
-    const int pw = ceil_div(pairs, 8);
-    const dim3 grid(g.parts, g.co_groups, g.ci_groups), block(512);
-#define PASN_WH(COT_, PW_)                                                                                                        \
-    if (cot == COT_ && pw == PW_) {                                                                                               \
-        PASN_MAX_LDS(160 * 1024, conv_wgrad_halo_kernel<COT_, PW_>);                                                              \
-        hipLaunchKernelGGL((conv_wgrad_halo_kernel<COT_, PW_>), grid, block, lds, s, (const __bf16*)x, (const __bf16*)dy, (float*)ws, d, g); \
+#define PASN_WH(COT_, PW_)                                                                                                \
+    if (r.arm == WgradRoute::HALO && r.sel_a == COT_ && r.sel_b == PW_) {                                                 \
+        PASN_MAX_LDS(160 * 1024, conv_wgrad_halo_kernel<COT_, PW_>);                                                      \
+        hipLaunchKernelGGL((conv_wgrad_halo_kernel<COT_, PW_>), r.grid, dim3(512), r.lds, s, xb, dyb, (float*)ws, d, r.h); \
     }
     PASN_WH(1, 1) PASN_WH(2, 1) PASN_WH(3, 1) PASN_WH(1, 2) PASN_WH(2, 2) PASN_WH(3, 2) PASN_WH(1, 3) PASN_WH(2, 3) PASN_WH(3, 3)
 #undef PASN_WH
-    const long total = (long)g.taps * d.Cout * d.Cin;
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)ceil_div(total, 256L)), dim3(256), 0, s, (const float*)ws, dw, g.parts, g.taps, d.Cout,
-                       d.Cin, g.Cout_r, g.Cin_r);
-    return true;
+    const long total = (long)r.taps * d.Cout * d.Cin;
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)ceil_div(total, 256L)), dim3(256), 0, s, (const float*)ws, dw, (int)r.parts, r.taps, d.Cout,
+                       d.Cin, r.Cout_r, r.Cin_r);
 }
 
 }  // namespace pasn

@@ -27,12 +27,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 
 OUT = os.path.join(HERE, "probe_sweep.json")
+OUT_WGRAD = os.path.join(HERE, "probe_sweep_wgrad.json")
 _BIG = {"PASN_DWWG_BLOCKS": "2048"}
 ENVS = [("default", {})] + [(f"{k}={v}", {k: v}) for k, v in (
     ("PASN_XTILE_GATED", "1"), ("PASN_NO_SE_PROLOGUE", "1"), ("PASN_NO_SE_FUSE", "1"), ("PASN_SE_FUSE_MAXC", "256"), ("PASN_WS", "0"),
     ("PASN_DWMFMA", "0"), ("PASN_NO_DWWG_STRIP", "1"), ("PASN_NO_DWWG_MARCH", "1"), ("PASN_DWWG_MARCH2", "0"), ("PASN_DWWG_CH", "2"),
     ("PASN_DWWG_WT", "3"), ("PASN_DWWG_BLOCKS", "256"), ("PASN_DWWG_BLOCKS", "2048"))] + [
     (f"PASN_DWWG_BLOCKS=2048,{k}={v}", dict(_BIG, **{k: v})) for k, v in (("PASN_DWWG_MARCH2", "0"), ("PASN_DWWG_CH", "2"), ("PASN_DWWG_WT", "3"))]
+# The dense weight-gradient switches and probes came later.  They live in a file of their own (OUT_WGRAD: their environments' cells for
+# every probe, and the two probes' cells for every environment), so that probe_sweep.json, which they leave byte for byte as it was, stays
+# untouched; load_golden() reads the two as one.
+N_BASE_ENVS = len(ENVS)
+ENVS += [(f"{k}={v}", {k: v}) for k, v in (
+    ("PASN_NO_WGRAD_HALO", "1"), ("PASN_NO_WGRAD_GATHER", "1"), ("PASN_WGRAD_DET", "1"), ("PASN_NO_WGRAD_TILE", "1"), ("PASN_NO_WGRAD_LDS", "1"),
+    ("PASN_WGT_WIDE", "0"), ("PASN_WGT_XCD", "0"))]
 # The depthwise weight-gradient workspace is sized for the first marching kernel's block count (at most 1024) whenever a marching kernel
 # covers the layer, and the second marching kernel's count stays below it up to its default cap of 512: alone, these four environments
 # move no answer (they are recorded all the same -- a change that made them matter would show).  With the cap raised above 1024 each
@@ -47,6 +55,10 @@ SINGLE = {
     "conv3d_variant": lambda L, d: [L.pasn_conv3d_variant(d, t, f) for t in DTYPES for f in range(4)],
     "conv3d_se_supported": lambda L, d: [L.pasn_conv3d_se_supported(d, t, c, r) for t in DTYPES for c in CSE for r in (0, 1)],
     "conv3d_wgrad_workspace_bytes": lambda L, d: [L.pasn_conv3d_wgrad_workspace_bytes(d, t) for t in DTYPES],
+}
+WGRAD = {  # asked of every descriptor, like SINGLE; recorded in OUT_WGRAD
+    "conv3d_wgrad_variant": lambda L, d: [L.pasn_conv3d_wgrad_variant(d, t, w) for t in DTYPES for w in (0, 1)],
+    "conv3d_wgrad_row_parts": lambda L, d: [L.pasn_conv3d_wgrad_row_parts(d, t, w) for t in DTYPES for w in (0, 1)],
 }
 DEPTHWISE = {
     "dwconv3d_variant": lambda L, d: [L.pasn_dwconv3d_variant(d, t) for t in DTYPES],
@@ -64,7 +76,7 @@ PAIR = {
     "x3d_expdw_variant": lambda L, a, b: [L.pasn_x3d_expdw_variant(a, b, t) for t in DTYPES],
     "x3d_expdw_pool_blocks": lambda L, a, b: [L.pasn_x3d_expdw_pool_blocks(a, b, t) for t in DTYPES],
 }
-PROBES = tuple(SINGLE) + tuple(DEPTHWISE) + tuple(PAIR)
+PROBES = tuple(SINGLE) + tuple(DEPTHWISE) + tuple(PAIR) + tuple(WGRAD)
 
 
 def _fields():
@@ -87,7 +99,7 @@ def answers(probe, singles, pairs):
         return [((a, b), PAIR[probe](L, mk(a), mk(b))) for a, b in pairs]
     if probe in DEPTHWISE:
         return [(t, DEPTHWISE[probe](L, mk(t))) for t in singles if _is_depthwise(t)]
-    return [(t, SINGLE[probe](L, mk(t))) for t in singles]
+    return [(t, dict(SINGLE, **WGRAD)[probe](L, mk(t))) for t in singles]
 
 
 BLOCK = 16
@@ -219,6 +231,17 @@ def sweep(groups):
     return out
 
 
+def load_golden():
+    """probe_sweep.json and probe_sweep_wgrad.json as one record."""
+    g, w = json.load(open(OUT)), json.load(open(OUT_WGRAD))
+    g["envs"] += w["envs"]
+    g["probes"] += w["probes"]
+    for grp, per in w["digests"].items():
+        for p, cell in per.items():
+            g["digests"][grp].setdefault(p, {}).update(cell)
+    return g
+
+
 def stored_groups(golden):
     descs = [tuple(t) for t in golden["descs"]]
     return {g: ([descs[i] for i in v["singles"]], [(descs[i], descs[j]) for i, j in v["pairs"]]) for g, v in golden["groups"].items()}
@@ -238,7 +261,13 @@ if __name__ == "__main__":
         print(f"{g}: {len(s)} descriptors, {len(p)} pairs")
     digests = {g: {p: {e: c for e, c in cell.items() if e == "default" or c != cell["default"]} for p, cell in per.items()}
                for g, per in sweep(groups).items()}
+    base_envs, late_envs = [e for e, _ in ENVS[:N_BASE_ENVS]], [e for e, _ in ENVS[N_BASE_ENVS:]]
+    base = {g: {p: {e: c for e, c in cell.items() if e in base_envs} for p, cell in per.items() if p not in WGRAD} for g, per in digests.items()}
+    late = {g: {p: {e: c for e, c in cell.items() if p in WGRAD or e in late_envs} for p, cell in per.items()} for g, per in digests.items()}
     with open(OUT, "w") as fh:
-        json.dump({"fields": _fields(), "envs": [e for e, _ in ENVS], "probes": list(PROBES), "descs": [list(t) for t in index],
-                   "groups": stored, "digests": digests}, fh, separators=(",", ":"))
-    print(f"{OUT}: {len(groups)} groups, {len(index)} stored descriptors, {os.path.getsize(OUT)} bytes")
+        json.dump({"fields": _fields(), "envs": base_envs, "probes": [p for p in PROBES if p not in WGRAD], "descs": [list(t) for t in index],
+                   "groups": stored, "digests": base}, fh, separators=(",", ":"))
+    with open(OUT_WGRAD, "w") as fh:
+        json.dump({"envs": late_envs, "probes": list(WGRAD), "digests": {g: {p: c for p, c in per.items() if c} for g, per in late.items()}},
+                  fh, separators=(",", ":"))
+    print(f"{OUT}: {len(groups)} groups, {len(index)} stored descriptors, {os.path.getsize(OUT)} + {os.path.getsize(OUT_WGRAD)} bytes")

@@ -2,7 +2,6 @@
 digest of what the routing and sizing questions of csrc/conv.hip and csrc/wgrad.hip answer -- over every descriptor the compiled plans
 and training tapes pass to the library and over a synthetic grid across the rungs of the ladders, under the default environment and
 under each routing switch those ladders read (tests/golden/make_probe_sweep.py).  Runs no kernel."""
-import json
 import os
 import sys
 
@@ -14,7 +13,7 @@ from protoasnet_amd import _lib
 sys.path.insert(0, GOLDEN)
 import make_probe_sweep as snap  # noqa: E402
 
-_GOLDEN = json.load(open(snap.OUT))
+_GOLDEN = snap.load_golden()
 _GROUPS = {}
 
 

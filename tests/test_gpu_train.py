@@ -272,7 +272,29 @@ WGRAD_CASES = [
     (432, 192, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 4, 7, 7)),    # wide layers: 2 x 2 tile groups, several row partitions, ragged last step
     (192, 432, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 5, 7, 7)),
     (96, 216, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 9, 14, 14)),   # 7 / 3 tiles: half-empty last pairs
+    # one case per remaining bf16 instance of the product build (WGRAD_BF16_INSTANCE below names them)
+    (128, 128, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 5, 7, 10)),   # 700 rows: two partitions of three 128-row steps, the last ragged
+    (64, 96, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 3, 9, 7)),
+    (96, 96, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 3, 9, 7)),
+    (200, 24, (1, 1, 1), (1, 2, 2), (0, 0, 0), (2, 2, 9, 9)),
+    # the regime of every real layer, a block walking several K steps: 43 200 rows is the smallest count at which the 333 partitions this
+    # geometry asks for no longer hold a block to one 128-row step (256 rows per block, 192 in the last)
+    (96, 96, (1, 1, 1), (1, 1, 1), (0, 0, 0), (2, 6, 60, 60)),
+    (64, 144, (1, 3, 3), (1, 1, 1), (0, 1, 1), (1, 2, 70, 56)),   # 64 rows per block = two 32-row steps, 9 taps, borders on every side
 ]
+# The instance pasn_conv3d_wgrad runs for each case in bf16 (pasn_conv3d_wgrad_variant; encoding: include/protoasnet_amd.h) and, where the
+# case is about it, its row partitions.  pw_wgrad_bf16_kernel<32, 1> and <32, 8> are reachable only through the tuning build's PASN_WG_TPW.
+WGRAD_BF16_INSTANCE = dict(zip(WGRAD_CASES, [
+    (212801, None), (300102, None), (212801, None), (212801, None), (300102, None), (300201, None), (300201, None),
+    (300101, 2), (212802, None), (212804, None), (203202, None), (212804, 169), (203204, 123)]))
+
+
+def _assert_wgrad_instance(d, code, has_ws, variant, row_parts=None):
+    """The library is about to launch the kernel instance the case names (the probe reads the route the launch reads)."""
+    lib = _lib.lib()
+    assert lib.pasn_conv3d_wgrad_variant(ctypes.byref(d), code, has_ws) == variant
+    if row_parts is not None:
+        assert lib.pasn_conv3d_wgrad_row_parts(ctypes.byref(d), code, has_ws) & 0xFFFFFFFF == row_parts
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -289,6 +311,10 @@ def test_conv_wgrad(cin, cout, k, s, p, shape, dtype):
     d = _desc(x, y, k, s, p)
     xd, dyd = _cl(x, dtype=dtype), _cl(dy, dtype=dtype)
     dw = torch.zeros(cout, cin, k[0] * k[1] * k[2], device=DEV)
+    if dtype == torch.bfloat16:
+        _assert_wgrad_instance(d, BF16, 0, *WGRAD_BF16_INSTANCE[(cin, cout, k, s, p, shape)])
+    else:  # conv_wgrad_kernel<float, PW>
+        _assert_wgrad_instance(d, F32, 0, 100000 + (k == (1, 1, 1) and s == (1, 1, 1)))
     _lib.check(lib.pasn_conv3d_wgrad(xd.data_ptr(), dyd.data_ptr(), dw.data_ptr(), ctypes.byref(d), _lib.dtype_code(dtype), _st()))
     _rel(dw.view_as(wt), wt.grad, 1e-4, "dW")
 
@@ -301,7 +327,16 @@ WGRAD_HALO_CASES = [
     (128, 288, (1, 3, 3), (0, 1, 1), (1, 2, 14, 14)),   # 9 co tiles = 3 groups, 4 ci tiles = 2 groups
     (64, 64, (1, 3, 3), (0, 1, 1), (3, 1, 28, 28)),     # ResNet-18 block conv (T = 1), several row partitions
     (64, 144, (1, 3, 3), (0, 1, 1), (1, 2, 20, 56)),    # W = 56 as in stage 1 of the 112 x 112 clip
+    # the other six instances.  Temporal shape: 640 rows = two partitions, the clip boundary inside the ragged one
+    (72, 128, (3, 1, 1), (1, 0, 0), (2, 5, 8, 8)),      # <3, 1>: what R(2+1)D's 230 -> 128 temporal convs run
+    (16, 24, (3, 1, 1), (1, 0, 0), (2, 5, 8, 8)),
+    (16, 24, (1, 3, 3), (0, 1, 1), (2, 3, 10, 12)),
+    (24, 40, (1, 3, 3), (0, 1, 1), (2, 3, 10, 12)),
+    (24, 96, (1, 3, 3), (0, 1, 1), (2, 3, 10, 12)),
+    (64, 24, (1, 3, 3), (0, 1, 1), (2, 3, 10, 12)),
 ]
+# conv_wgrad_halo_kernel<COT, PW> of each case: 400000 + 10000 * (temporal taps) + 100 COT + PW -- all nine instances
+WGRAD_HALO_INSTANCE = dict(zip(WGRAD_HALO_CASES, [400303, 410201, 410201, 400303, 400203, 400303, 410301, 410101, 400102, 400202, 400302, 400103]))
 
 
 @pytest.mark.parametrize("cin,cout,k,p,shape", WGRAD_HALO_CASES)
@@ -322,6 +357,7 @@ def test_conv_wgrad_halo(cin, cout, k, p, shape):
     nbytes = int(lib.pasn_conv3d_wgrad_workspace_bytes(ctypes.byref(d), BF16))
     assert nbytes > 0, "this layer must take the partial-buffer path"
     assert int(lib.pasn_conv3d_wgrad_workspace_bytes(ctypes.byref(d), F32)) == 0
+    _assert_wgrad_instance(d, BF16, 1, WGRAD_HALO_INSTANCE[(cin, cout, k, p, shape)])
     taps = k[0] * k[1] * k[2]
     outs = []
     for _ in range(2):
@@ -632,6 +668,7 @@ def test_conv_wgrad_gather(cin, cout, k, s, p, shape):
     xd, dyd = _cl(x, dtype=dtype), _cl(dy, dtype=dtype)
     nbytes = int(lib.pasn_conv3d_wgrad_workspace_bytes(ctypes.byref(d), BF16))
     assert nbytes > 0
+    _assert_wgrad_instance(d, BF16, 1, 500000)  # conv_wgrad_gather_kernel
     taps = k[0] * k[1] * k[2]
     outs = []
     for _ in range(2):
