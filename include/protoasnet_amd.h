@@ -222,6 +222,9 @@ int pasn_dwconv3d_pool_blocks(const pasn_conv_desc* d, int dtype);
  * 60001 = dwconv3d_tz_kernel (stride-1 3x3x3, planes 9 .. 14 wide: Toeplitz form); 70000 + kt = dwconv_t_kernel<dtype, kt> ((kt,1,1),
  * kt = 3 / 5, stride 1, taken when pool_partial is NULL: the X3D stem's conv_t as a launch of its own); 0 = generic kernel. */
 int pasn_dwconv3d_variant(const pasn_conv_desc* d, int dtype);
+/* The instance of the launch WITH pool partial rows (pool_partial != NULL), same codes: differs from pasn_dwconv3d_variant only on the
+ * (kt,1,1) layers, which the strip kernel <dtype, WT, 1, 1> runs then (dwconv_t_kernel writes no pool rows). */
+int pasn_dwconv3d_pool_variant(const pasn_conv_desc* d, int dtype);
 /* The same stencil with the squeeze-excite gate of the block fused into the launch (X3D conv_b + SE: global average pool ->
  * fc1 + ReLU -> fc2 + sigmoid): every block writes its pool partial row, the clip's last-arriving block reduces them and computes
  * gate[n][:].  Same results as pasn_dwconv3d_fwd followed by pasn_se_gate_fwd up to fp32 summation order (fixed: repeat runs are

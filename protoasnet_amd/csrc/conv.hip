@@ -962,9 +962,9 @@ extern "C" int pasn_conv3d_short_fwd(const void* x, const void* w, const float* 
     return launch_pwconv<__bf16>(x, w, scale, bias, nullptr, gate, y, *d, pw_geom(*d, dtype), (hipStream_t)stream, &sc);
 }
 
-extern "C" int pasn_dwconv3d_variant(const pasn_conv_desc* d, int dtype) {
+static int dw_variant_code(const pasn_conv_desc* d, int dtype, bool wants_pool) {
     if (!dw_desc_ok(d)) return 0;
-    const DwRoute r = dw_route(*d, dtype, false);  // the launch without pool partial rows
+    const DwRoute r = dw_route(*d, dtype, wants_pool);
     switch (r.arm) {
         case DwRoute::TEMPORAL: return 70000 + d->kt;             // dwconv_t_kernel<dtype, KT>
         case DwRoute::TZ: return 60001;                           // dwconv3d_tz_kernel
@@ -973,6 +973,9 @@ extern "C" int pasn_dwconv3d_variant(const pasn_conv_desc* d, int dtype) {
         default: return r.g.WT ? r.g.WT * 100 + d->kw * 10 + d->sw : 0;  // dwconv3d_strip_kernel<dtype, WT, KW, SW>, 0: dwconv3d_kernel
     }
 }
+extern "C" int pasn_dwconv3d_variant(const pasn_conv_desc* d, int dtype) { return dw_variant_code(d, dtype, false); }  // the launch without pool partial rows
+// ... and with them: the (kt,1,1) layers leave dwconv_t_kernel for the strip kernel <dtype, WT, 1, 1>; every other layer keeps its instance
+extern "C" int pasn_dwconv3d_pool_variant(const pasn_conv_desc* d, int dtype) { return dw_variant_code(d, dtype, true); }
 
 extern "C" int pasn_dwconv3d_pool_blocks(const pasn_conv_desc* d, int dtype) {
     return dw_desc_ok(d) ? dw_route(*d, dtype, true).pool_rows : 0;

@@ -211,8 +211,8 @@ def conv_kernel_name(v: int, tname: str, gate: bool, in_swish: bool, res: bool) 
 
 def dwconv_kernel_name(dv: int, tname: str, act: str, pool: bool, wo: int) -> str:
     actc = _lib.ACT[act]
-    if dv >= DW_TEMPORAL:  # with pool partial rows the (kt,1,1) layer stays on the generic kernel
-        return f"dwconv3d_kernel<{tname}>" if pool else f"dwconv_t_kernel<{tname},{dv - DW_TEMPORAL}>"
+    if dv >= DW_TEMPORAL:  # (never with pool partial rows: pasn_dwconv3d_pool_variant answers the strip kernel's code for a (kt,1,1) layer)
+        return f"dwconv_t_kernel<{tname},{dv - DW_TEMPORAL}>"
     if dv >= DW_TZ:
         return f"dwconv3d_tz_kernel<{actc},{'true' if pool else 'false'}>"
     if dv >= DW_MFMA:  # the instance as the profiler prints it: <rows per position tile, ablation build, compiled-in activation>
@@ -637,7 +637,7 @@ class PlanBuilder:
         xb, yb, pb, dref = x.buf, y.buf, pool_buf, ctypes.byref(d)
         self._use(xb, yb, pb)
         out_pos = y.N * y.positions
-        dv = int(self.lib.pasn_dwconv3d_variant(dref, self.code))
+        dv = int((self.lib.pasn_dwconv3d_pool_variant if pool else self.lib.pasn_dwconv3d_variant)(dref, self.code))
         self._note("dwconv", dwconv_kernel_name(dv, self.tname, act, pool, y.W),
                    (self._touched(x, y, k, s) + out_pos) * y.C * self.es + (y.N * pool_blocks * y.C * 4 if pool else 0),
                    2 * out_pos * y.C * taps, d)

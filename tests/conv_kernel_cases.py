@@ -257,10 +257,12 @@ def launch(built):
 
 
 # ------------------------------------------------------------------------------------------------- reference
-def conv64(x, w, s, p):
-    """Exact dense conv in fp64: for every tap one matrix product [M][Cin] x [Cin][Cout].  x (N,Cin,T,H,W), w (Cout,Cin,kt,kh,kw)."""
-    n, _, t, h, wd = x.shape
+def conv64(x, w, s, p, groups=1):
+    """Exact dense conv in fp64: for every tap one matrix product [M][Cin] x [Cin][Cout].  x (N,Cin,T,H,W), w (Cout,Cin,kt,kh,kw).
+    ``groups`` = Cin: the depthwise conv, w (C,1,kt,kh,kw), for every tap one product per channel."""
+    n, cin, t, h, wd = x.shape
     cout, _, kt, kh, kw = w.shape
+    assert groups == 1 or (groups == cin == cout and w.shape[1] == 1), "dense or depthwise"
     to, ho, wo = ((i + 2 * pp - kk) // ss + 1 for i, kk, ss, pp in zip((t, h, wd), (kt, kh, kw), s, p))
     xp = torch.nn.functional.pad(x, (p[2], p[2], p[1], p[1], p[0], p[0])).permute(0, 2, 3, 4, 1)  # channels last
     out = torch.zeros(n * to * ho * wo, cout, dtype=F64)
@@ -268,6 +270,9 @@ def conv64(x, w, s, p):
         for b in range(kh):
             for c in range(kw):
                 xs = xp[:, a:a + s[0] * (to - 1) + 1:s[0], b:b + s[1] * (ho - 1) + 1:s[1], c:c + s[2] * (wo - 1) + 1:s[2]]
+                if groups != 1:
+                    out += xs.reshape(-1, cin) * w[:, 0, a, b, c]
+                    continue
                 out += xs.reshape(-1, xs.shape[-1]) @ w[:, :, a, b, c].t()
     return out.view(n, to, ho, wo, cout).permute(0, 4, 1, 2, 3)
 

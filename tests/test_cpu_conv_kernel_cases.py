@@ -2,6 +2,7 @@
 (b) the table claims every instance ``PlanBuilder.conv`` emits in the default plans of the four trunks and in the prototype heads' plans
 (the ledger), (c) the fp64 reference agrees with torch's conv3d + eval-mode BatchNorm3d, (d) the bound holds for an fp32-accumulating
 emulation of the kernels on every row and FAILS on six ways a kernel goes subtly wrong."""
+import functools
 import os
 import sys
 
@@ -49,29 +50,42 @@ def test_rows_cover_what_the_table_promises():
 
 
 # ------------------------------------------------------------------------------------------------- (b) the ledger
-def _default_plan_names():
-    """{instance name: first plan that launches it} over the un-switched routing cases (the four trunks, both compute types) and the
-    add-on / occurrence chains of the prototype heads, which run through ``PlanBuilder.conv`` launch by launch."""
+@functools.lru_cache(maxsize=None)
+def default_plan_meta():
+    """[(routing case, ``meta`` row)] of every launch of the eight un-switched routing cases (the four trunks, both compute types), built on
+    the CPU with every ``PASN_*`` switch of the environment cleared.  The plan walk the ledgers share (tests/test_cpu_dw_kernel_cases.py)."""
     sys.path.insert(0, GOLDEN)
     import make_routing_snapshot as mrs
 
-    from protoasnet_amd import backbones, model_builder
-    from protoasnet_amd.plan import Act, PlanBuilder
+    from protoasnet_amd import _lib, backbones
+    from protoasnet_amd.plan import PlanBuilder
 
     dt = {"bf16": torch.bfloat16, "f32": torch.float32, "u8": torch.uint8}
     trunks = {"x3d_s": lambda: backbones.X3DFeatures("x3d_s"), "x3d_m": lambda: backbones.X3DFeatures("x3d_m"),
               "resnet2p1d_18": lambda: backbones.resnet2p1d_18(pretrained=False), "resnet18": backbones.ResNet18Features}
-    seen = {}
     default = [c for c in mrs.CASES if not c[5]]
     assert len(default) == 8
-    for name, arch, shape, dtype, in_dtype, _ in default:
-        trunk = trunks[arch]()
-        pb = PlanBuilder(torch.device("cpu"), dt[dtype], dt[in_dtype], trunk.input_affine)
-        with torch.no_grad():
-            trunk.build_plan(pb, pb.input(shape))
-        for m in pb.meta:
-            if m["kind"] == "conv":
-                seen.setdefault(m["kernel"], f"{name}: {m['shape']}")
+    rows = []
+    with _lib.tuning_env(**{k: None for k in os.environ if k.startswith("PASN_")}):
+        for name, arch, shape, dtype, in_dtype, _ in default:
+            trunk = trunks[arch]()
+            pb = PlanBuilder(torch.device("cpu"), dt[dtype], dt[in_dtype], trunk.input_affine)
+            with torch.no_grad():
+                trunk.build_plan(pb, pb.input(shape))
+            rows += [(name, m) for m in pb.meta]
+    return tuple(rows)
+
+
+def _default_plan_names():
+    """{instance name: first plan that launches it} over the un-switched routing cases (the four trunks, both compute types) and the
+    add-on / occurrence chains of the prototype heads, which run through ``PlanBuilder.conv`` launch by launch."""
+    from protoasnet_amd import model_builder
+    from protoasnet_amd.plan import Act, PlanBuilder
+
+    seen = {}
+    for name, m in default_plan_meta():
+        if m["kind"] == "conv":
+            seen.setdefault(m["kernel"], f"{name}: {m['shape']}")
     # head A (ProtoPNet add-on layers, both forms) and head B (add-on + occurrence module) behind the trunks' feature maps
     heads = (("ppnet", util.CFG_PPNET, (8, 1, 7, 7)), ("ppnet_bottleneck", util.CFG_PPNET_BOTTLENECK, (8, 1, 7, 7)), ("xprotonet", util.CFG_XPROTO, (8, 1, 7, 7)),
              ("video_x3d", util.CFG_VIDEO_X3D, (32, 16, 7, 7)), ("video_r2plus1d", util.CFG_VIDEO_R2P1D, (2, 8, 14, 14)))
