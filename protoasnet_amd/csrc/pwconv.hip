@@ -56,12 +56,28 @@ struct RawQuad<float> {
     }
 };
 
+// Timing ablations (PASN_PW_ABL, -DPASN_TUNING builds only; results are WRONG when a bit is set): 1 no input transform, 2 no shortcut MFMAs,
+// 4 no global stores, 8 no main MFMAs.  The product kernel has neither the argument nor the tests.
+#ifdef PASN_TUNING
+#define PASN_PW_ABL_PARAM , int abl
+#define PASN_PW_ABL_VALUE , pw_abl
+#else
+#define PASN_PW_ABL_PARAM
+#define PASN_PW_ABL_VALUE
+#endif
+
+// Occupancy hints: <2,4,false> wants its three waves; the gated 108 -> 48 + 24 -> 48 shortcut instance <8,2,false,2> is asked for TWO waves per
+// SIMD (240 registers since the shortcut rows share one buffer and its MFMAs come last; alone on its SIMD a wave had nothing to cover its
+// waits: 57.7 -> 40.8 us at 401 k rows).  Everywhere else the register allocator's own choice stands (profiles/README.md entry 58).
 template <typename T, int KS, int NT, bool RES, int KS2 = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 && NT == 4 && !RES) ? 3 : 1))) void pwconv_persist_kernel(const T* __restrict__ x, const T* __restrict__ w,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 && NT == 4 && !RES) ? 3 : (KS == 8 && NT == 2 && KS2 == 2) ? 2 : 1))) void pwconv_persist_kernel(const T* __restrict__ x, const T* __restrict__ w,
                                                              const float* __restrict__ scale, const float* __restrict__ bias,
                                                              const T* __restrict__ res, const float* __restrict__ gate,
                                                              T* __restrict__ y, long M, int S, int Cin_p, int Cout, int Cout_p,
-                                                             int w_kc, int act, int in_swish, int gate_rows, PwShort sc2) {
+                                                             int w_kc, int act, int in_swish, int gate_rows, PwShort sc2 PASN_PW_ABL_PARAM) {
+#ifndef PASN_TUNING
+    constexpr int abl = 0;
+#endif
     static_assert(KS2 == 0 || !RES, "the fused shortcut replaces the residual operand");
     constexpr int SB = KS2 ? 3 : 2;  // scale | bias (| scale2) arrays in LDS
     using frag = typename Traits<T>::frag;
@@ -109,7 +125,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
     const long ntiles = (M + 31) / 32;
     const long stride = (long)gridDim.x * 4;
     long tile = (long)blockIdx.x * 4 + wave;
-    const bool xform = (gate != nullptr) || (in_swish != 0);
+    const bool xform = ((gate != nullptr) || (in_swish != 0)) && !(abl & 1);
     // clip of this lane's row, kept incrementally (one 64-bit division here instead of one per tile: the gated layers
     // do 4-8 MFMAs per tile, a software division is of the same order)
     long cn = 0;   // clip index of row m = tile * 32 + c
@@ -121,22 +137,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
     }
     const long row_step = stride * 32;
 
+    // Columns this lane half holds: k = ks * KSTEP + h * CH < Cin_p  <=>  ks * KSTEP < kl.  ONE per-lane integer, made opaque where it is
+    // tested: written as `k < Cin_p`, hipcc hoists a lane mask per k-step and per use (clamped offset, zeroing, transform) out of the tile
+    // loop into SGPR pairs and spills them (18-44 spilled SGPRs in the KS = 8 instances, read back lane by lane every tile).
+    const int kl = Cin_p - h * CH;
+    const int kl2 = KS2 ? sc2.Cin2_p - h * CH : 0;
     frag Bc[KS], Bn[KS];
     // ISSUE ONLY: unconditional loads from clamped (existing) addresses; rows beyond M / columns beyond Cin_p are zeroed
     // when the fragments are consumed.  (`cond ? load : 0` puts every load in its own branch, and any use of the value
     // next to the load makes hipcc wait for it before issuing the next one.)
     auto load_rows = [&](long t, frag (&B)[KS]) {
         const long m = min(t * 32 + c, M - 1);
-        const T* xp = x + m * Cin_p;
+        const T* xp = x + m * Cin_p + h * CH;
+        int klo = kl;
+        asm volatile("" : "+v"(klo));
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int k = ks * KSTEP + h * CH;
-            B[ks] = load_frag<T>(xp + (k < Cin_p ? k : 0));
-        }
+        for (int ks = 0; ks < KS; ++ks) B[ks] = load_frag<T>(ks * KSTEP < klo ? xp + ks * KSTEP : xp - h * CH);
     };
     // shortcut rows: this lane's output position as (wo, ho, frame index n To + to), advanced by the tile stride with carries (one
-    // division chain here instead of three per tile)
-    frag B2c[KS2 ? KS2 : 1], B2n[KS2 ? KS2 : 1];
+    // division chain here instead of three per tile).  ONE buffer: the next tile's rows are requested into the same registers as soon as
+    // this tile's shortcut MFMAs have issued (a second buffer filled at the top of the tile is 8-16 more registers: what kept <8,2,false,2> at one wave per SIMD).
+    frag B2[KS2 ? KS2 : 1];
     int pwo = 0, pho = 0;
     long ptn = 0;
     int dwo = 0, dho = 0;
@@ -157,12 +178,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
     auto load_rows2 = [&](frag (&B)[KS2 ? KS2 : 1]) {  // rows of the position held in (pwo, pho, ptn); clamped like load_rows
         long row = (ptn * sc2.Hi + (long)pho * sc2.sh) * sc2.Wi + (long)pwo * sc2.sw;
         row = row < rows_in ? row : rows_in - 1;
-        const T* xp = x2 + row * sc2.Cin2_p;
+        const T* xp = x2 + row * sc2.Cin2_p + h * CH;
+        int klo = kl2;
+        asm volatile("" : "+v"(klo));
 #pragma unroll
-        for (int ks = 0; ks < (KS2 ? KS2 : 1); ++ks) {
-            const int k = ks * KSTEP + h * CH;
-            B[ks] = load_frag<T>(xp + (k < sc2.Cin2_p ? k : 0));
-        }
+        for (int ks = 0; ks < (KS2 ? KS2 : 1); ++ks) B[ks] = load_frag<T>(ks * KSTEP < klo ? xp + ks * KSTEP : xp - h * CH);
     };
     auto advance2 = [&]() {
         pwo += dwo;
@@ -176,7 +196,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
     if (tile < ntiles) {
         load_rows(tile, Bc);
         if (KS2) {
-            load_rows2(B2c);
+            load_rows2(B2);
             advance2();  // (pwo, pho, ptn) now names the NEXT tile's position
         }
     }
@@ -184,13 +204,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
     for (; tile < ntiles; tile += stride) {
         const long m = tile * 32 + c;
         const bool mv = m < M;
-        if (tile + stride < ntiles) {
-            load_rows(tile + stride, Bn);  // next tile's rows: in flight during everything below
-            if (KS2) {
-                load_rows2(B2n);
-                advance2();
-            }
-        }
+        const bool more = tile + stride < ntiles;
+        if (more) load_rows(tile + stride, Bn);  // next tile's rows: in flight during everything below
         // this tile's residual rows, requested before the MFMAs that hide them
         // raw (unconverted), unconditional, clamped: see load_rows.  Compile-time RES: expand convs pay no registers.
         // bf16: the tile's 32 residual rows are ONE contiguous range, like the output: whole 16-byte pieces, lane-contiguous (the quad
@@ -220,24 +235,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
                     rq[nt][g] = *reinterpret_cast<const typename RawQuad<T>::type*>(res + (ok ? m * Cout_p + co : 0));
                 }
         }
+        int klo = mv ? kl : 0;  // columns (of an existing row) this lane half holds: what load_rows clamped is zeroed, the rest transformed
+        asm volatile("" : "+v"(klo));
+        // The gate row is read through an LDS pointer or a global pointer, never through one pointer that may be either: such a
+        // read is a FLAT load, which counts on both memory counters and returns in no order, so hipcc waits for EVERYTHING in flight
+        // (`s_waitcnt vmcnt(0) lgkmcnt(0)`) after each -- the next tile's rows and the residual pieces just requested included.
+        // That wait, once per k-step, was most of what the fused transform cost.
+        const int goff = (int)(mv ? cn : 0) * Cin_p + h * CH;
+        f32x16 acc[NT];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)  // zero what load_rows clamped
-            if (!(mv && ks * KSTEP + h * CH < Cin_p)) Bc[ks] = zero_frag<T>();
-        if (KS2) {
+        for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int ks = 0; ks < KS2; ++ks)
-                if (!(mv && ks * KSTEP + h * CH < sc2.Cin2_p)) B2c[ks] = zero_frag<T>();
-        }
-        if (xform) {  // x' = swish(x * gate[n][ci]), rounded back to the MFMA input type
-            const long n = mv ? cn : 0;
-            const float* gp = gate ? (gate_rows ? gl : gate) + n * Cin_p + h * CH : nullptr;
+            for (int i = 0; i < 16; ++i) acc[nt][i] = 0.0f;
+        // k-step by k-step: x' = swish(x * gate[n][ci]), rounded back to the MFMA input type, then that step's MFMAs -- which run under
+        // the NEXT step's transform (independent instructions of one wave; as two loops the matrix pipe idled through the whole transform)
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if (ks * KSTEP + h * CH < Cin_p) {
+        for (int ks = 0; ks < KS; ++ks) {
+            if (!(ks * KSTEP < klo)) Bc[ks] = zero_frag<T>();
+            if (xform) {
+                if (ks * KSTEP < klo) {
                     float gv[CH];
 #pragma unroll
                     for (int j = 0; j < CH; j += 4) {
-                        const f32x4 q = gp ? *reinterpret_cast<const f32x4*>(gp + ks * KSTEP + j) : f32x4{1.0f, 1.0f, 1.0f, 1.0f};
+                        f32x4 q = {1.0f, 1.0f, 1.0f, 1.0f};
+                        if (gate_rows) q = *reinterpret_cast<const f32x4*>(gl + goff + ks * KSTEP + j);
+                        else if (gate) {  // (a gate tensor too large for LDS: no X3D layer at the benchmarked batch sizes)
+                            q = *reinterpret_cast<const f32x4*>(gate + goff + ks * KSTEP + j);
+                            asm volatile("" : "+v"(q));  // waited for HERE: pending at the join, it would put the vmcnt(0) on the LDS path as well
+                        }
                         gv[j] = q[0];
                         gv[j + 1] = q[1];
                         gv[j + 2] = q[2];
@@ -253,26 +278,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
                     for (int j = 0; j < CH; ++j) Bc[ks][j] = (T)gv[j];
                 }
             }
+            if (!(abl & 8)) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) mma32(acc[nt], A[nt][ks], Bc[ks]);
+            }
         }
-        f32x16 acc[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[nt][i] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) mma32(acc[nt], A[nt][ks], Bc[ks]);
+        // The shortcut's MFMAs LAST: its accumulators are then live in the epilogue only, not beside the transform's temporaries; the next
+        // tile's shortcut rows are requested into the same registers as soon as these MFMAs have issued.
         f32x16 acc2[KS2 ? NT : 1];
         if (KS2) {
+            int kl2o = mv ? kl2 : 0;  // zero what load_rows2 clamped
+            asm volatile("" : "+v"(kl2o));
+#pragma unroll
+            for (int ks = 0; ks < KS2; ++ks)
+                if (!(ks * KSTEP < kl2o)) B2[ks] = zero_frag<T>();
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc2[nt][i] = 0.0f;
+            if (!(abl & 2)) {
 #pragma unroll
-            for (int ks = 0; ks < KS2; ++ks)
+                for (int ks = 0; ks < KS2; ++ks)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) mma32(acc2[nt], A2[nt][ks], B2c[ks]);
+                    for (int nt = 0; nt < NT; ++nt) mma32(acc2[nt], A2[nt][ks], B2[ks]);
+            }
+            if (more) {
+                load_rows2(B2);
+                advance2();
+            }
         }
         // Epilogue.  The accumulator layout (position on the lane, 4 consecutive channels per quad) would give 8-byte
         // stores scattered at the row stride -- measured at ~1.7 TB/s of writes.  The 32 rows of a tile are ONE contiguous
@@ -283,12 +316,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
         auto epilogue = [&](auto actc) {
             constexpr int ACTC = decltype(actc)::value;
         T* st = stage + (size_t)wave * 32 * Cout_p;
+        // the channel counts the per-group tests read: opaque scalars, so each test is a scalar compare where it stands (as loop invariants
+        // hipcc keeps one lane mask per group and test in SGPR pairs, and `Cout - col` per group in a VGPR, across the whole tile loop)
+        int cout_t = Cout, coutp_t = Cout_p;
+        asm volatile("" : "+s"(cout_t), "+s"(coutp_t));
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int col = nt * 32 + 8 * g + 4 * h;
-                if (nt * 32 + 8 * g >= Cout_p) continue;  // wave-uniform (Cout_p is a multiple of 8: both lane halves of a group exist or neither)
+                if (nt * 32 + 8 * g >= coutp_t) continue;  // wave-uniform (Cout_p is a multiple of 8: both lane halves of a group exist or neither)
                 float o[4], sc[4], bs[4];
                 load4(sbl + col, sc);
                 load4(sbl + NT * 32 + col, bs);
@@ -311,8 +348,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
                     act_vec_c<ACTC>(o, act);
                     // only the group that holds padded channels pays the selects (wave-uniform test: as a per-lane one the compiler hoists a
                     // predicate per group out of the tile loop -- 30-150 spilled SGPRs per instance, read back lane by lane every tile)
-                    if (nt * 32 + 8 * g + 8 > Cout) {
-                        int left = Cout - col;
+                    if (nt * 32 + 8 * g + 8 > cout_t) {
+                        int left = cout_t - col;
                         asm volatile("" : "+v"(left));  // computed here, on the path that needs it (not hoisted per group and kept in SGPRs)
                         mask_tail(o, left);
                     }
@@ -342,12 +379,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
                             asm volatile("" : "+v"(left));
                             mask_tail(v, left);
                         }
-                        store8(reinterpret_cast<__bf16*>(y) + base + (long)q * CPL, v);
+                        if (!(abl & 4)) store8(reinterpret_cast<__bf16*>(y) + base + (long)q * CPL, v);
                     }
                 }
             } else {
                 for (int q = lane; q < pieces; q += 64) {
-                    if (base + (long)q * CPL < lim)
+                    if (base + (long)q * CPL < lim && !(abl & 4))
                         *reinterpret_cast<uint4*>(y + base + (long)q * CPL) = *reinterpret_cast<const uint4*>(st + (size_t)q * CPL);
                 }
             }
@@ -358,10 +395,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KS == 2 &&
         __builtin_amdgcn_wave_barrier();  // the image is reused by this wave's next tile
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) Bc[ks] = Bn[ks];
-        if (KS2) {
-#pragma unroll
-            for (int ks = 0; ks < KS2; ++ks) B2c[ks] = B2n[ks];
-        }
         if (gate) {  // advance the clip index to the next tile's row
             crem += row_step;
             while (crem >= S) {
@@ -443,7 +476,7 @@ int launch_pwconv(const void* x, const void* w, const float* scale, const float*
         long blocks = want_blocks < (long)n_cu * per_cu ? want_blocks : (long)n_cu * per_cu;                                  \
         const dim3 grid((unsigned)blocks, 1);                                                                                 \
         hipLaunchKernelGGL((pwconv_persist_kernel<T, KS_, NT_, RES_, KS2_>), grid, block, lds, s, (const T*)x, (const T*)w, scale, bias,   \
-                           (const T*)res, gate, (T*)y, M, S, d.Cin_p, d.Cout, d.Cout_p, d.w_kc, d.act, d.in_swish, gate_rows, SC_); \
+                           (const T*)res, gate, (T*)y, M, S, d.Cin_p, d.Cout, d.Cout_p, d.w_kc, d.act, d.in_swish, gate_rows, SC_ PASN_PW_ABL_VALUE); \
     } while (0)
 #define PASN_PW(KS_, NT_)                 \
     do {                                  \
@@ -451,6 +484,9 @@ int launch_pwconv(const void* x, const void* w, const float* scale, const float*
         else PASN_PW2(KS_, NT_, false);    \
     } while (0)
     const int KS = g.TM, NT = g.xrow;
+#ifdef PASN_TUNING
+    const int pw_abl = tune_dev("PASN_PW_ABL") ? atoi(tune_dev("PASN_PW_ABL")) : 0;
+#endif
     size_t lds = (size_t)(sc ? 3 : 2) * NT * 32 * 4 + (size_t)4 * 32 * d.Cout_p * sizeof(T);  // <= 64.5 KB (fp32, 128 channels)
     int gate_rows = 0;  // the whole gate tensor rides in LDS when it is small (it is: N x Cin_p floats)
     if (gate && (size_t)d.N * d.Cin_p * 4 <= 32 * 1024 && lds + (size_t)d.N * d.Cin_p * 4 <= 80 * 1024) {

@@ -102,6 +102,7 @@ static const TuneEntry kRegistry[] = {
     {"PASN_DWMFMA_ABL",       "dev",   "matrix-core stencil timing ablations (bit mask)"},
     {"PASN_EXPDW_ABL",        "dev",   "fused expand + stencil timing ablations (bit mask)"},
     {"PASN_HALO_ABL",         "dev",   "halo implicit GEMM timing ablations"},
+    {"PASN_PW_ABL",           "dev",   "persistent pointwise conv timing ablations (bit mask)"},
     {"PASN_WS_ABL",           "dev",   "weight-stationary conv timing ablations (needs -DPASN_WS_ABLATE too)"},
     {"PASN_EDP_STAMPS",       "dev",   "whole-block launch of the 7 x 7 stage: in-kernel phase stamps (tools/edp_bench.py)"},
     {"PASN_TZ_STAMPS",        "dev",   "Toeplitz expand + stencil launch: in-kernel phase stamps (tools/tz_bench.py)"},
