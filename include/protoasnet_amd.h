@@ -666,6 +666,51 @@ size_t pasn_roc_auc_workspace_bytes(long M, int K_real);
 int pasn_roc_auc_ovr(const float* probs, const int32_t* labels, long M, int K_real, double* auc, double* auc_per_class, void* workspace,
                      void* stream);
 
+/* Selective prediction (selective.py): what the abstention output is for.  The reference trains it (src/loss/loss.py:323-371) and has no
+ * code that evaluates it, so the definitions here are the specification.  Every call is stream-ordered: no host synchronisation.
+ *
+ * Uncertainty score of each row of logits [M][K] fp32 into u [M] fp32:
+ *   mode 0 (maxprob):         1 - max_k softmax(logits[.][0 .. K_real))[k]; bitwise 1.0f - the largest entry of the probs row that
+ *                             pasn_eval_batch_stats stores for the same logits (the same expf / division sequence)
+ *   mode 1 (alpha, joined):   softmax(logits[.][0 .. K))[K - 1] (loss.py:356); needs K == K_real + 1
+ *   mode 2 (alpha, separate): sigmoid(logits[.][K - 1]) (loss.py:358); needs K > K_real
+ * 2 <= K_real <= 16, K_real <= K <= 17, M >= 1; anything else returns PASN_ERR_ARG before any launch. */
+int pasn_uncertainty_scores(const float* logits, long M, int K, int K_real, int mode, float* u, void* stream);
+
+/* One prediction per group of rows (per cine, of its clips).  probs [M][K_real] fp32, u [M] fp32, labels [M] int32; the groups are CSR:
+ * group g owns the rows group_rows[group_offsets[g] .. group_offsets[g + 1]) (int32 row indices in [0, M), ascending within a group, not
+ * necessarily contiguous; offsets int64 [G + 1]).  The row indices are NOT checked: they are the caller's.  Per group of n rows, every sum
+ * in fp64 in the listed order, each add and multiply rounded on its own (two calls are bitwise equal):
+ *   p_mean [G][K_real] = sum p_i / n
+ *   p_conf [G][K_real] = sum (1 - u_i) p_i / sum (1 - u_i); p_mean where that denominator is 0
+ *   u_mean [G]         = sum u_i / n
+ *   g_label [G] int32  = the label of the group's first row (-1 for an empty group, whose means are NaN); g_count [G] int32 = n
+ *   status [2] int32   = {groups whose rows disagree on the label, rows holding a NaN}; zeroed by the call.  Nothing branches on them:
+ *                        a conflicting group is still averaged, and whoever reads the results decides.
+ * One launch: a wave per group of up to 64 rows, the block for a larger one.  G >= 1, 2 <= K_real <= 16. */
+int pasn_group_predictions(const float* probs, const float* u, const int32_t* labels, const int64_t* group_offsets,
+                           const int32_t* group_rows, int G, int K_real, double* p_mean, double* p_conf, double* u_mean, int32_t* g_label,
+                           int32_t* g_count, int32_t* status, void* stream);
+
+/* Risk-coverage curve.  probs [M][K_real] fp32, labels [M] int32, u [M] fp32.  A row with label < 0 is padding and is ignored, as in
+ * pasn_roc_auc_ovr (so is a row with label >= K_real); Mv is the number of the others.  The valid rows are ordered by ascending u; equal
+ * u (-0 = +0): the lower row index first; NaN u last, again by index.  A row's prediction is the first largest of its K_real
+ * probabilities.  For m = 1 .. Mv, with cm the confusion matrix [true][predicted] of the first m rows in that order:
+ *   order [M] int32      order[m - 1] = the row index of the m-th row
+ *   threshold [M] fp32   threshold[m - 1] = its u
+ *   acc [M] fp64         trace(cm) / m
+ *   bal_acc [M] fp64     the mean over the classes with support > 0 of tp_k / support_k
+ *   f1_mean [M] fp64     (1 / K_real) sum_k 2 tp_k / (support_k + predicted_k), 0 for a zero denominator
+ *   aurc [1] fp64        (1 / Mv) sum_m (1 - acc[m - 1]), added in a fixed tree order; NaN when Mv = 0
+ *   counts [2] int64     {Mv, valid rows whose u is NaN}
+ * Entries at and past Mv are left unwritten.  All prefix counts are integers (per-block histograms, block bases, a local scan): two calls
+ * are bitwise equal.  Five launches on `stream`; `workspace` holds pasn_risk_coverage_workspace_bytes(M, K_real) bytes (8-byte
+ * aligned) and needs no initialisation.  1 <= M <= 2^20 (the order is a rank by counting: M^2 comparisons), 2 <= K_real <= 16;
+ * anything else, or a NULL pointer, returns PASN_ERR_ARG before any launch (the size query returns 0). */
+size_t pasn_risk_coverage_workspace_bytes(long M, int K_real);
+int pasn_risk_coverage(const float* probs, const int32_t* labels, const float* u, long M, int K_real, int32_t* order, double* acc,
+                       double* bal_acc, double* f1_mean, float* threshold, double* aurc, int64_t* counts, void* workspace, void* stream);
+
 /* Global explanations: the k nearest clips of a split per prototype, kept on the device while a loader is swept (global_explain.py).
  * The reference ships only the raw material, the whole (clips, P) similarity matrix "for ranking prototypes"
  * (XProtoNet_Base.py:613-656 get_sim_scores / load_sim_scores; explain_global is a stub); the selection rule per batch is the push's

@@ -160,6 +160,11 @@ SIGNATURES = {
     "pasn_eval_batch_stats": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_float, c_long, c_long] + [c_void_p] * 7),
     "pasn_roc_auc_workspace_bytes": (c_size_t, [c_long, c_int]),
     "pasn_roc_auc_ovr": (c_int, [c_void_p, c_void_p, c_long, c_int] + [c_void_p] * 4),
+    # ---- selective prediction (selective.py)
+    "pasn_uncertainty_scores": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "pasn_group_predictions": (c_int, [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 7),
+    "pasn_risk_coverage_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "pasn_risk_coverage": (c_int, [c_void_p] * 3 + [c_long, c_int] + [c_void_p] * 9),
     # ---- the training loss recipe (losses.FusedCriterion)
     "pasn_proto_loss_fwd": (c_int, [c_void_p] * 13 + [POINTER(ProtoLossDesc), c_void_p]),
     "pasn_proto_loss_bwd": (c_int, [c_void_p] * 14 + [POINTER(ProtoLossDesc), c_void_p]),

@@ -1,0 +1,290 @@
+"""Selective prediction: what the abstention output is for (``csrc/selective.hip``).
+
+ProtoASNet's abstention class gives every clip a learned uncertainty ``alpha`` (``src/loss/loss.py:323-371``); the model is judged by how
+much its accuracy rises as the uncertain clips are set aside.  The reference trains that output and has no code that evaluates it, so the
+definitions below ("Selective prediction"; ``include/protoasnet_amd.h``) are the specification:
+
+* ``uncertainty(logits, abstain_class, score, ab_logitpath)``: one score per row -- ``maxprob`` = 1 - the largest real-class probability,
+  ``alpha`` = the abstention column of the joined softmax (``loss.py:356``) or the sigmoid of the abstention logit (``loss.py:358``).
+* ``build_groups(keys)`` / ``group_predictions(probs, u, labels, groups)``: one prediction per cine from its clips' rows -- the plain mean
+  ``p_mean``, the confidence-weighted mean ``p_conf`` (weights ``1 - u``) and the mean uncertainty ``u_mean``, fp64 sums in row order.
+* ``risk_coverage(probs, labels, u)``: the rows ordered by ascending uncertainty (ties: the lower index; NaN last) and, for every prefix
+  of that order, the accuracy, balanced accuracy and mean F1 of ``trainer.confusion_to_metrics``; ``aurc`` is the mean error over all
+  prefixes (the area under the risk-coverage curve), ``error_auroc`` the AUROC of ``u`` as a detector of the wrong predictions.
+* ``SelectiveEvaluator``: an ``EpochEvaluator(keep_logits=True)`` fed batch by batch together with the clips' file names; ``finish`` gives
+  the curve read at a few coverages, per clip or per cine, with ONE synchronising device-to-host copy.
+
+Everything runs on the device on the caller's stream; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import csv
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .metrics import EpochEvaluator, _f32, _require_cuda, roc_auc_ovr_weighted
+
+MAXPROB, ALPHA_JOINED, ALPHA_SEPARATE = 0, 1, 2  # the modes of pasn_uncertainty_scores
+MAX_ROWS = 1 << 20  # pasn_risk_coverage: a rank by counting
+DEFAULT_COVERAGES = (1.0, 0.9, 0.8, 0.7, 0.5)
+
+
+def score_mode(abstain_class: bool, score: str = "auto", ab_logitpath: str = "joined") -> int:
+    """The kernel mode of a score name: ``auto`` is ``alpha`` with an abstention class and ``maxprob`` without one."""
+    if score not in ("auto", "maxprob", "alpha"):
+        raise ValueError(f"score must be 'auto', 'maxprob' or 'alpha', got {score!r}")
+    if ab_logitpath not in ("joined", "separate"):
+        raise ValueError(f"ab_logitpath must be 'joined' or 'separate', got {ab_logitpath!r}")
+    if score == "auto":
+        score = "alpha" if abstain_class else "maxprob"
+    if score == "maxprob":
+        return MAXPROB
+    if not abstain_class:
+        raise ValueError("score='alpha' needs a model with an abstention class")
+    return ALPHA_JOINED if ab_logitpath == "joined" else ALPHA_SEPARATE
+
+
+def uncertainty(logits: torch.Tensor, abstain_class: bool, score: str = "auto", ab_logitpath: str = "joined") -> torch.Tensor:
+    """(M,) fp32 uncertainty of the rows of ``logits`` (M, K); the last column is the abstention logit when ``abstain_class``."""
+    mode = score_mode(abstain_class, score, ab_logitpath)
+    _require_cuda(logits)
+    if logits.dim() != 2:
+        raise ValueError("logits must be (M, K)")
+    M, K = logits.shape
+    u = torch.empty(M, dtype=torch.float32, device=logits.device)
+    if M > 0:
+        _lib.check(_lib.lib().pasn_uncertainty_scores(_lib.ptr(_f32(logits)), M, K, K - 1 if abstain_class else K, mode, _lib.ptr(u),
+                                                      _lib.current_stream()))
+    return u
+
+
+# ---- groups: one prediction per cine ---------------------------------------------------------------------------------------------------
+def build_groups(keys: Sequence) -> Tuple[np.ndarray, np.ndarray, list]:
+    """CSR groups of the rows that share a key (host only): ``(offsets int64 (G + 1,), rows int32 (M,), names)``.  Groups come in order of
+    first appearance, a group's rows ascending; equal keys need not be neighbours."""
+    index: Dict[object, int] = {}
+    members: List[List[int]] = []
+    for i, k in enumerate(keys):
+        g = index.setdefault(k, len(members))
+        if g == len(members):
+            members.append([])
+        members[g].append(i)
+    offsets = np.zeros(len(members) + 1, dtype=np.int64)
+    np.cumsum([len(m) for m in members], out=offsets[1:])
+    rows = np.fromiter((i for m in members for i in m), dtype=np.int32, count=int(offsets[-1]))
+    return offsets, rows, list(index)
+
+
+class GroupPredictions:
+    """Device results of ``group_predictions``: ``p_mean`` / ``p_conf`` (G, K_real) fp64, ``u_mean`` (G,) fp64, ``labels`` / ``counts``
+    (G,) int32, ``status`` (2,) int32 = {groups whose rows disagree on the label, rows holding a NaN}."""
+
+    def __init__(self, p_mean, p_conf, u_mean, labels, counts, status):
+        self.p_mean, self.p_conf, self.u_mean, self.labels, self.counts, self.status = p_mean, p_conf, u_mean, labels, counts, status
+
+    def check(self) -> "GroupPredictions":
+        """Reads the status words (a host synchronisation): ``ValueError`` when a group's rows disagree on the label."""
+        _raise_on_conflict(int(self.status[0].item()))
+        return self
+
+
+def _raise_on_conflict(n: int) -> None:
+    if n > 0:
+        raise ValueError(f"{n} group(s) hold rows with different labels: the rows of one cine must share its label")
+
+
+def group_predictions(probs: torch.Tensor, u: torch.Tensor, labels: torch.Tensor, groups, check: bool = True) -> GroupPredictions:
+    """One prediction per group of rows; ``groups`` is ``build_groups``' tuple (or its first two arrays).  ``check=True`` reads the status
+    and raises ``ValueError`` on a label conflict; ``check=False`` returns without a host synchronisation (``.check()`` later)."""
+    _require_cuda(probs, u, labels)
+    if probs.dim() != 2 or u.shape != probs.shape[:1] or labels.shape != probs.shape[:1]:
+        raise ValueError("probs must be (M, K_real), u and labels (M,)")
+    M, K_real = probs.shape
+    offsets = np.ascontiguousarray(groups[0], dtype=np.int64)
+    rows = np.ascontiguousarray(groups[1], dtype=np.int32)
+    G = offsets.size - 1
+    if G < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
+        raise ValueError("group offsets must start at 0, not decrease and end at the number of listed rows")
+    if rows.size and (rows.min() < 0 or rows.max() >= M):  # the kernel does not check: these indices address device memory
+        raise ValueError(f"group rows must lie in [0, {M})")
+    dev = probs.device
+    d_off, d_rows = torch.from_numpy(offsets).to(dev), torch.from_numpy(rows).to(dev)
+    p_mean, p_conf = torch.empty(G, K_real, dtype=torch.float64, device=dev), torch.empty(G, K_real, dtype=torch.float64, device=dev)
+    u_mean = torch.empty(G, dtype=torch.float64, device=dev)
+    g_label, g_count = torch.empty(G, dtype=torch.int32, device=dev), torch.empty(G, dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pasn_group_predictions(
+        _lib.ptr(_f32(probs)), _lib.ptr(_f32(u)), _lib.ptr(labels.to(torch.int32).contiguous()), _lib.ptr(d_off), _lib.ptr(d_rows), G, K_real,
+        _lib.ptr(p_mean), _lib.ptr(p_conf), _lib.ptr(u_mean), _lib.ptr(g_label), _lib.ptr(g_count), _lib.ptr(status), _lib.current_stream()))
+    res = GroupPredictions(p_mean, p_conf, u_mean, g_label, g_count, status)
+    return res.check() if check else res
+
+
+# ---- risk-coverage -----------------------------------------------------------------------------------------------------------------------
+def coverage_rows(coverages: Sequence[float], Mv):
+    """The number of rows ``m`` kept at each coverage ``c``: ``ceil(c * Mv)``, at least one row and at most ``Mv``.  ``c * Mv`` is an fp64
+    product, so 1e-9 of a row is taken off before the ceiling (0.7 * 10 is 7.000000000000001, and means 7).  Works on numpy values and
+    on device tensors alike (``Mv`` a 0-d tensor): the host and the device take the same IEEE steps."""
+    if isinstance(Mv, torch.Tensor):
+        c = torch.as_tensor(list(coverages), dtype=torch.float64, device=Mv.device)
+        return torch.minimum(torch.ceil(c * Mv.double() - 1e-9).clamp(min=1.0), Mv.double().clamp(min=1.0)).to(torch.int64)
+    c = np.asarray(list(coverages), dtype=np.float64)
+    return np.minimum(np.maximum(np.ceil(c * np.float64(Mv) - 1e-9), 1.0), max(float(Mv), 1.0)).astype(np.int64)
+
+
+def _check_coverages(coverages) -> List[float]:
+    cs = [float(c) for c in coverages]
+    if not cs or any(not (0.0 < c <= 1.0) for c in cs):
+        raise ValueError(f"coverages must lie in (0, 1], got {list(coverages)}")
+    return cs
+
+
+class RiskCoverage:
+    """The device curves of ``risk_coverage``: ``order`` (M,) int32, ``acc`` / ``bal_acc`` / ``f1_mean`` (M,) fp64, ``threshold`` (M,)
+    fp32 -- entries at and past ``counts[0]`` (the valid rows, Mv) are unwritten --, ``aurc`` (1,) fp64, ``counts`` (2,) int64 = {Mv, rows
+    whose uncertainty is NaN}, and ``error_auroc`` (0-d fp64; NaN when every row is right, every row is wrong, or a ``u`` is NaN)."""
+
+    def __init__(self, order, acc, bal_acc, f1_mean, threshold, aurc, counts, error_auroc):
+        self.order, self.acc, self.bal_acc, self.f1_mean, self.threshold = order, acc, bal_acc, f1_mean, threshold
+        self.aurc, self.counts, self.error_auroc = aurc, counts, error_auroc
+
+    def packed(self, coverages) -> torch.Tensor:
+        """fp64 device vector [acc, bal_acc, f1_mean, threshold, rows kept (one each per coverage), aurc, error_auroc, Mv, NaN rows]."""
+        n = coverage_rows(coverages, self.counts[0])
+        i = (n - 1).clamp(min=0)
+        return torch.cat([self.acc[i], self.bal_acc[i], self.f1_mean[i], self.threshold[i].double(), n.double(), self.aurc,
+                          self.error_auroc.reshape(1), self.counts.double()])
+
+    @staticmethod
+    def unpack(host: torch.Tensor, coverages) -> Dict[str, object]:
+        nc = len(coverages)
+        v = host.tolist()
+        Mv = int(v[5 * nc + 2])
+        nan = float("nan")
+        cut = (lambda a: a) if Mv > 0 else (lambda a: [nan] * nc)  # no valid row: the curve is empty
+        return {"coverage": list(coverages), "accuracy": cut(v[:nc]), "bal_accuracy": cut(v[nc: 2 * nc]), "f1_mean": cut(v[2 * nc: 3 * nc]),
+                "threshold": cut(v[3 * nc: 4 * nc]), "rows": [int(x) if Mv > 0 else 0 for x in v[4 * nc: 5 * nc]], "aurc": v[5 * nc],
+                "error_auroc": v[5 * nc + 1], "valid_rows": Mv, "nan_rows": int(v[5 * nc + 3])}
+
+    def at(self, coverages) -> Dict[str, object]:
+        """The curve read at row ``m = coverage_rows(c, Mv)`` for each coverage, with ``aurc`` and ``error_auroc``: ONE device-to-host
+        copy.  ``{coverage, accuracy, bal_accuracy, f1_mean, threshold, rows (lists), aurc, error_auroc, valid_rows, nan_rows}``."""
+        cs = _check_coverages(coverages)
+        return self.unpack(self.packed(cs).cpu(), cs)
+
+
+def first_largest(probs: torch.Tensor) -> torch.Tensor:
+    """The index of the first largest entry of each row (``argmax`` does not promise the first on the device)."""
+    return ((probs == probs.amax(dim=1, keepdim=True)).cumsum(dim=1) == 0).sum(dim=1)
+
+
+def risk_coverage(probs: torch.Tensor, labels: torch.Tensor, u: torch.Tensor) -> RiskCoverage:
+    """The risk-coverage curves of ``probs`` (M, K_real) fp32, ``labels`` (M,) (< 0: a padding row, ignored) and ``u`` (M,) fp32.  No host
+    synchronisation."""
+    _require_cuda(probs, labels, u)
+    if probs.dim() != 2 or labels.shape != probs.shape[:1] or u.shape != probs.shape[:1]:
+        raise ValueError("probs must be (M, K_real), labels and u (M,)")
+    M, K_real = probs.shape
+    if not 1 <= M <= MAX_ROWS:
+        raise ValueError(f"risk_coverage takes 1 .. {MAX_ROWS} rows, got {M}")
+    dev = probs.device
+    probs, u, labels = _f32(probs), _f32(u), labels.to(torch.int32).contiguous()
+    order = torch.empty(M, dtype=torch.int32, device=dev)
+    curves = torch.empty(3, M, dtype=torch.float64, device=dev)
+    threshold = torch.empty(M, dtype=torch.float32, device=dev)
+    aurc = torch.empty(1, dtype=torch.float64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(_lib.lib().pasn_risk_coverage_workspace_bytes(M, K_real)) // 8 + 1, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().pasn_risk_coverage(_lib.ptr(probs), _lib.ptr(labels), _lib.ptr(u), M, K_real, _lib.ptr(order), _lib.ptr(curves[0]),
+                                             _lib.ptr(curves[1]), _lib.ptr(curves[2]), _lib.ptr(threshold), _lib.ptr(aurc), _lib.ptr(counts),
+                                             _lib.ptr(ws), _lib.current_stream()))
+    # u as a detector of the wrong predictions: the binary AUC of the scores [1 - u, u] against the wrong (1) / right (0) flag
+    valid = (labels >= 0) & (labels < K_real)
+    wrong = torch.where(valid, (first_largest(probs) != labels).to(torch.int32), torch.full_like(labels, -1))
+    _, per = roc_auc_ovr_weighted(torch.stack([1.0 - u, u], dim=1), wrong, 2, per_class=True)
+    return RiskCoverage(order, curves[0], curves[1], curves[2], threshold, aurc, counts, per[1])
+
+
+# ---- the evaluator -----------------------------------------------------------------------------------------------------------------------
+class SelectiveEvaluator:
+    """Selective-prediction metrics of one sweep of ``model`` (the surface ``EpochEvaluator`` reads).
+
+    ``update(logits, sim, target, keys)``: one ``EpochEvaluator.update`` (its launch, no host synchronisation); ``keys`` are the rows'
+    group names -- the clips' file names -- kept on the host.  ``finish(coverages, level)``: ``level="clip"`` scores every row with
+    ``uncertainty(...)``; ``level="cine"`` first reduces the rows of each key to one prediction (``p_conf``, uncertainty ``u_mean``) and
+    scores those.  Returns ``{aurc, error_auroc, accuracy@c, bal_accuracy@c, f1_mean@c, threshold@c (c as in "0.9"), rows, nan_rows}`` and
+    at cine level also ``groups``, the confusion metrics ``accuracy`` / ``f1`` / ``f1_mean`` and ``auc`` / ``auc_per_class`` of the cine
+    predictions, and ``cines``: one ``{filename, target_AS, n_clips, probs, uncertainty, pred}`` per cine.  One synchronising read."""
+
+    def __init__(self, model, abstain_class: bool, score: str = "auto", ab_logitpath: str = "joined", capacity: int = 0):
+        self.abstain, self.score, self.ab_logitpath = bool(abstain_class), score, ab_logitpath
+        score_mode(self.abstain, score, ab_logitpath)  # a bad name fails here, not after the sweep
+        self.ev = EpochEvaluator(model, keep_logits=True, abstain_class=self.abstain, capacity=capacity)
+        self.keys: list = []
+
+    def update(self, logits: torch.Tensor, sim: torch.Tensor, target: torch.Tensor, keys: Sequence) -> None:
+        keys = list(keys)
+        if len(keys) != logits.shape[0]:
+            raise ValueError(f"{len(keys)} keys for {logits.shape[0]} rows")
+        self.ev.update(logits, sim, target)
+        self.keys += keys
+
+    def finish(self, coverages=DEFAULT_COVERAGES, level: str = "clip") -> Dict[str, object]:
+        if level not in ("clip", "cine"):
+            raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
+        cs = _check_coverages(coverages)
+        ev, K = self.ev, self.ev.K_real
+        if ev.rows == 0:
+            raise ValueError("no rows: call update() first")
+        probs, labels = ev.probs[: ev.rows], ev.labels[: ev.rows]
+        u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
+        if level == "clip":
+            host = risk_coverage(probs, labels, u).packed(cs).cpu()
+            return self._result(RiskCoverage.unpack(host, cs))
+        offsets, rows, names = build_groups(self.keys)
+        G = len(names)
+        gp = group_predictions(probs, u, labels, (offsets, rows), check=False)
+        p, gl = gp.p_conf.float(), gp.labels
+        pred = first_largest(p)
+        cm = torch.bincount(gl.long().clamp(0, K - 1) * K + pred.clamp(max=K - 1), minlength=K * K)
+        auc, auc_k = roc_auc_ovr_weighted(p, gl, K, per_class=True)
+        rc = risk_coverage(p, gl, gp.u_mean.float())
+        tail = [gp.status.double(), cm.double(), auc.reshape(1), auc_k, gp.p_conf.flatten(), gp.u_mean, gl.double(), gp.counts.double(), pred.double()]
+        host = torch.cat([rc.packed(cs)] + tail).cpu()  # the one read
+        n_rc = 5 * len(cs) + 4
+        res = self._result(RiskCoverage.unpack(host[:n_rc], cs))
+        t = host[n_rc:]
+        _raise_on_conflict(int(t[0]))
+        from .trainer import confusion_to_metrics
+
+        res.update(confusion_to_metrics(t[2: 2 + K * K].view(K, K)))
+        o = 2 + K * K
+        res.update({"groups": G, "nan_clip_rows": int(t[1]), "auc": float(t[o]), "auc_per_class": t[o + 1: o + 1 + K].tolist()})
+        o += 1 + K
+        pc = t[o: o + G * K].view(G, K).tolist()  # whole columns at once: per-element reads of a tensor would dominate the call
+        um, lab, cnt, prd = (t[o + G * K + j * G: o + G * K + (j + 1) * G] for j in range(4))
+        res["cines"] = [{"filename": n, "target_AS": l, "n_clips": c, "probs": p, "uncertainty": x, "pred": d}
+                        for n, l, c, p, x, d in zip(names, lab.long().tolist(), cnt.long().tolist(), pc, um.tolist(), prd.long().tolist())]
+        return res
+
+    @staticmethod
+    def _result(at: Dict[str, object]) -> Dict[str, object]:
+        res = {"aurc": at["aurc"], "error_auroc": at["error_auroc"], "rows": at["valid_rows"], "nan_rows": at["nan_rows"]}
+        for j, c in enumerate(at["coverage"]):
+            for name in ("accuracy", "bal_accuracy", "f1_mean", "threshold"):
+                res[f"{name}@{c:g}"] = at[name][j]
+        return res
+
+
+def write_cine_log(path: str, cines: Sequence[dict], class_names: Sequence[str]) -> None:
+    """One CSV row per cine: ``filename, target_AS, n_clips, prob_<label>..., uncertainty, pred`` (``cines`` as ``finish`` returns them)."""
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n", quoting=csv.QUOTE_MINIMAL)
+        w.writerow(["filename", "target_AS", "n_clips"] + [f"prob_{n}" for n in class_names] + ["uncertainty", "pred"])
+        for c in cines:
+            if len(c["probs"]) != len(class_names):
+                raise ValueError(f"{len(c['probs'])} probabilities for {len(class_names)} class names")
+            w.writerow([c["filename"], c["target_AS"], c["n_clips"]] + [repr(float(p)) for p in c["probs"]] + [repr(float(c["uncertainty"])), c["pred"]])

@@ -445,6 +445,49 @@ class DPTrainer:
             raise ValueError("evaluate runs an evaluation epoch: val, val_push or test")
         return self.run_epoch(self.current_epoch, mode)
 
+    def evaluate_selective(self, mode: str = "test", level: str = "cine", coverages=(1.0, 0.9, 0.8, 0.7, 0.5), score: str = "auto") -> Dict[str, object]:
+        """Selective-prediction metrics of ``data_loaders[mode]`` (``protoasnet_amd.selective``): an eval-mode, forward-only sweep (no
+        loss; the ``staged`` / ``prepare_input`` path of ``run_epoch``), the clips grouped by ``sample["filename"]`` -- with
+        ``iterate_intervals`` every cardiac cycle of a cine is a row of its own -- and ``SelectiveEvaluator.finish(coverages, level)``'s
+        dict: the risk-coverage curve read at ``coverages``, ``aurc``, ``error_auroc`` and, at cine level, one prediction per cine.  The
+        uncertainty is ``score`` (``auto``: the abstention output when the config has ``abstain_class``, else 1 - the largest
+        probability; ``CeLossAbstain``'s ``ab_logitpath`` says how the abstention logit is read).  With ``save_dir`` set and
+        ``level="cine"`` it writes ``save_dir/csv_<mode>_cine/e<epoch>.csv``: ``filename, target_AS, n_clips, prob_<label>...,
+        uncertainty, pred``.
+
+        It issues NO collectives: each rank that calls it sweeps the loader it was given and reports on those rows alone (call it on one
+        rank with the full loader, or on every rank for per-shard figures; ranks need not call it together).  The model is left in the
+        mode it was in; no training or epoch state is touched."""
+        from . import selective
+        from .explain import _is_xproto
+
+        if not _is_xproto(self.model):
+            raise NotImplementedError("selective evaluation covers XProtoNet and Video_XProtoNet")
+        if self.device.type != "cuda":
+            raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
+        abstain = bool(self.config.get("abstain_class"))
+        loader = self.data_loaders[mode]
+        cap = len(loader) * int(getattr(loader, "batch_size", 0) or 0) if hasattr(loader, "__len__") else 0
+        path = self.CeLoss.ab_logitpath if abstain else "joined"
+        sel = selective.SelectiveEvaluator(self.model, abstain, score=score, ab_logitpath=path, capacity=cap)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                for sample in self.staged(loader):
+                    logit, similarities, _ = self.model(self.prepare_input(sample["cine"]))
+                    sel.update(logit, similarities, sample["target_AS"].to(self.device, non_blocking=True), list(sample["filename"]))
+            res = sel.finish(coverages, level)
+        finally:
+            self.model.train(was_training)
+        self.log(f"Epoch: {self.current_epoch} | {mode} | selective ({level}) | AURC {res['aurc']:.4f} | error AUROC {res['error_auroc']:.4f}")
+        if level == "cine" and self.config.get("save_dir"):
+            d = os.path.join(self.config["save_dir"], f"csv_{mode}_cine")
+            os.makedirs(d, exist_ok=True)
+            names = metrics_mod.logit_names(self.num_real_classes, False, self.config.get("class_labels"))
+            selective.write_cine_log(os.path.join(d, f"e{self.current_epoch:02d}.csv"), res["cines"], names)
+        return res
+
     def push(self, replace_prototypes: bool = True):
         abstain = bool(self.config.get("abstain_class"))
         self.sync_norm_buffers()  # every shard of the sweep must see the same eval-mode statistics
