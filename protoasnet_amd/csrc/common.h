@@ -519,6 +519,32 @@ __device__ __forceinline__ void act_vec(float (&v)[N], int act) {
             break;
     }
 }
+// The same with the activation known at COMPILE time: exactly one arm of the switch above, no compare and no branch.  An epilogue picks it
+// once per tile (ACT = -1: the run-time switch); inside an unrolled group loop the switch makes every group its own chain of basic blocks
+// that carries the dead sigmoid / Swish arms along, and nothing of one group is scheduled under another.
+template <int ACT, int N>
+__device__ __forceinline__ void act_vec(float (&v)[N], int act = ACT) {
+    static_assert(ACT >= -1 && ACT <= PASN_ACT_ABS, "a PASN_ACT_* value, or -1");
+    if constexpr (ACT == -1) {
+        act_vec(v, act);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            if constexpr (ACT == PASN_ACT_RELU) v[j] = relu_f32(v[j]);
+            else if constexpr (ACT == PASN_ACT_SIGMOID) v[j] = sigmoidf_(v[j]);
+            else if constexpr (ACT == PASN_ACT_SWISH) v[j] = v[j] * sigmoidf_(v[j]);
+            else if constexpr (ACT == PASN_ACT_ABS) v[j] = fabsf(v[j]);
+        }
+    }
+}
+// Branch-free tail mask for epilogues that may not branch between their groups: element j lives iff `first + j < nvalid`, `nvalid` ONE
+// per-lane count (channels left from the lane's first one) that the caller keeps opaque, so that the compares stand where they are used
+// instead of being hoisted, a lane mask per group, out of the tile loop.  The values are those of mask_tail(v, nvalid - first).
+template <int N>
+__device__ __forceinline__ void mask_tail_sel(float (&v)[N], int nvalid, int first) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = first + j < nvalid ? v[j] : 0.0f;
+}
 // Zero the elements of a channel vector that lie at or beyond the real channel count (`nvalid` = C - first channel).
 template <int N>
 __device__ __forceinline__ void mask_tail(float (&v)[N], int nvalid) {

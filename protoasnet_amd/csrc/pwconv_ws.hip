@@ -22,6 +22,7 @@
 //     scale / bias / residual (16-byte ds_read of the staged residual tile) / activation / one 16-byte buffer store per piece
 //     (rows beyond M and channels beyond Cout_p dropped by the range check).
 #include "common.h"
+#include <type_traits>
 
 namespace pasn {
 
@@ -101,7 +102,6 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
         if (bias) load8(bias + chc, bs[pr]);
         yoff[pr] = ok ? (unsigned)(pt * MT * 32 + c) * yrow + (unsigned)ch * 2u : BUF_OOB;
     }
-    const bool tail = live && ct * 32 + 32 > Cout;  // wave-uniform: this tile holds channels beyond the real count (stored as zeros)
     // ---- pair mode: the second conv's stationary weights and epilogue constants (channel tile = wave) ----------------------------------
     const int ctiles2 = KS2 ? (pr2.Cout2_p + 31) >> 5 : 0;
     const bool live2 = KS2 && wave < ctiles2;
@@ -130,10 +130,10 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
             if (pr2.bias2) load8(pr2.bias2 + chc, bs2[pr]);
             y2off[pr] = ok ? (unsigned)c * y2row + (unsigned)ch * 2u : BUF_OOB;
         }
-        // the handed-over tile's pad slot and the k columns beyond the first conv's channels stay zero: cleared once, never written
+        // the k columns of the handed-over tile beyond the first conv's channels stay zero: cleared once, never written (the pad slot of a row
+        // is never read: it takes the pieces of lanes that have none, see the epilogue)
         for (int i = threadIdx.x; i < BM * Y1PL; i += NW * 64) reinterpret_cast<uint4*>(y1t)[i] = uint4{0u, 0u, 0u, 0u};
     }
-    const bool tail2 = live2 && wave * 32 + 32 > pr2.Cout2;
 
     // ---- DMA roles.  Instruction j of a region covers its LDS slots 64 j .. 64 j + 63; wave `wave` issues j = wave, wave + NW, ... -------
     const int nix = (abl & 4) ? 0 : (BM * PPRL + 63) >> 6;
@@ -309,6 +309,21 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
         transform(0, 0);
     }
 
+    // ---- epilogue control: NOTHING may branch between the (sub-tile, piece) groups of an epilogue.  A branch ends hipcc's scheduling region:
+    // with one inside the unrolled group loop every group is its own chain of basic blocks, and the residual read, the lane swaps and the FMAs
+    // of a group no longer run under the previous group's tail or under MFMAs still in flight -- each group pays its own LDS round trip
+    // and MFMA-result latency, at one or two waves per SIMD.  So (a) the activation is dispatched ONCE per tile, ReLU (every X3D / ResNet
+    // pointwise unit) compiled in, everything else on another copy of the tile body with the run-time switch; (b) the tail mask is a select
+    // per element against ONE per-lane channel count (made opaque per tile: as loop invariants hipcc would keep a lane mask per group and
+    // element in SGPR pairs across the tile loop) -- and compiled OUT of the ReLU copy a launch without padded channels runs (every
+    // weight-stationary launch of the X3D plans: the selects are 16 vector instructions per group, measured at + 1 .. 1.4 us per launch on the
+    // instances with four or five waves per SIMD, which are bound by vector issue); (c) lanes without a channel piece write their hand-over
+    // piece to the row's pad slot instead of skipping the write; (d) masked stores carry BUF_OOB and are issued all the same (the counted
+    // waits rely on that anyway).
+    const bool relu_tile = act == PASN_ACT_RELU && (!KS2 || pr2.act2 == PASN_ACT_RELU);  // block-uniform
+    const bool any_tail = Cout != Cout_p || (KS2 && pr2.Cout2 != pr2.Cout2_p);             // block-uniform
+    int nv1 = Cout - (ct * 32 + 8 * h);                         // real channels left from this lane's first one: piece pr, element e lives iff 16 pr + e < nv1
+    int nv2 = KS2 ? pr2.Cout2 - (wave * 32 + 8 * h) : 0;  // the same for the second conv (channel tile = wave)
     int stg = 0;
 #pragma unroll 1
     for (int i = 0; i < nt; ++i) {
@@ -331,6 +346,10 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
         const unsigned m0 = row0 + (unsigned)i * (unsigned)BM;
         // (A phase stagger -- waves 4-7 transforming the next tile BEFORE their MFMAs, waves 0-3 after their epilogue, so that the two waves of
         // a SIMD sit in opposite phases -- was measured at +-0: 9664 vs 9643 clips/s, profiles/README round-3 entry 62.)
+        auto tile = [&](auto actc, auto tailc) {  // the tile body with the activation of BOTH epilogues compiled in (ACTC = -1: the run-time switch)
+        constexpr int ACTC = decltype(actc)::value;
+        constexpr bool TAIL = decltype(tailc)::value;  // false: no padded output channels anywhere in the launch
+        if (TAIL) asm volatile("" : "+v"(nv1), "+v"(nv2));
         if (live) {
             f32x16 acc[MT];
 #pragma unroll
@@ -370,15 +389,17 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] += r8[e];
                     }
-                    act_vec(v, act);
-                    if (tail) mask_tail(v, Cout - (ct * 32 + 16 * pr + 8 * h));
+                    act_vec<ACTC>(v, act);
+                    if (TAIL) mask_tail_sel(v, nv1, 16 * pr);
                     bf16x8 o;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
                     if (!(abl & 2))
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrsrc, (int)(yoff[pr] + (m0 + (unsigned)(mt * 32)) * yrow), 0, 0);
-                    if (KS2 && yoff[pr] != BUF_OOB)  // the same 8 channels of this position, as the second conv's operand
-                        *reinterpret_cast<bf16x8*>(y1t + ((pt * 32 + c) * Y1PL + ct * 4 + 2 * pr + h) * 16) = o;
+                    if (KS2) {  // the same 8 channels of this position, as the second conv's operand; a lane without the piece: the pad slot of its row
+                        const int sl = yoff[pr] != BUF_OOB ? ct * 4 + 2 * pr + h : 2 * KS2;
+                        *reinterpret_cast<bf16x8*>(y1t + ((pt * 32 + c) * Y1PL + sl) * 16) = o;
+                    }
                 }
             }
         }
@@ -412,8 +433,8 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
                         }
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] = v[e] * sc2[pr][e] + bs2[pr][e];
-                        act_vec(v, pr2.act2);
-                        if (tail2) mask_tail(v, pr2.Cout2 - (wave * 32 + 16 * pr + 8 * h));
+                        act_vec<ACTC>(v, pr2.act2);
+                        if (TAIL) mask_tail_sel(v, nv2, 16 * pr);
                         bf16x8 o;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
@@ -423,6 +444,10 @@ __global__ __launch_bounds__(512) void pwconv_ws_kernel(const __bf16* __restrict
                 }
             }
         }
+        };
+        if (relu_tile && !any_tail) tile(std::integral_constant<int, PASN_ACT_RELU>{}, std::false_type{});
+        else if (relu_tile) tile(std::integral_constant<int, PASN_ACT_RELU>{}, std::true_type{});
+        else tile(std::integral_constant<int, -1>{}, std::true_type{});
         if (XF && i + 1 < nt) transform(i + 1, nxt);
         stg = nxt;
     }

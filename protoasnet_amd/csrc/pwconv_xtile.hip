@@ -17,6 +17,7 @@
 //   * epilogue: scale/bias -> wave-private fp32 LDS image -> row-wise residual + activation + 16-byte stores.
 // No software pipeline across tiles: 90-200 VGPRs and 34-78 KB of LDS leave 2-4 blocks per CU in different phases.
 #include "common.h"
+#include <type_traits>
 
 namespace pasn {
 
@@ -34,6 +35,22 @@ __device__ __forceinline__ long xt_row(const XtStride& g, long m) {
     const int to = (int)(r % g.To);
     const long n = r / g.To;
     return ((n * g.Ti + (long)to * g.st) * g.Hi + (long)ho * g.sh) * g.Wi + (long)wo * g.sw;
+}
+
+// 8 channels as one (bf16) or two (fp32) 16-byte buffer stores, rounded as store8 rounds them; the descriptor's range check drops the
+// lanes whose offset lies beyond its end (BUF_OOB stays beyond it with the second store's + 16)
+template <typename T>
+__device__ __forceinline__ void xt_store8(__amdgpu_buffer_rsrc_t rs, unsigned off, const float (&v)[8]) {
+    if constexpr (sizeof(T) == 2) {
+        bf16x8 a;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = (__bf16)v[j];
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, a), rs, (int)off, 0, 0);
+    } else {
+        const f32x4 a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, a), rs, (int)off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, b), rs, (int)(off + 16u), 0, 0);
+    }
 }
 
 constexpr int XT_BM = 64;        // positions per tile
@@ -202,7 +219,19 @@ void pwconv_xtile_kernel(const T* __restrict__ x, const T* __restrict__ w,
         mma32(acc[1], A[ks], b1);
     }
     // ---- epilogue: the accumulator has the position on the lane and 4 consecutive channels per quad; bounce each 32 x 32
-    // tile through the wave's private fp32 image so that residual adds and stores are whole 8-channel pieces per lane
+    // tile through the wave's private fp32 image so that residual adds and stores are whole 8-channel pieces per lane.
+    // NOTHING branches between the four pieces of the epilogue: a branch ends hipcc's scheduling region, and with one per piece (the range
+    // test around it, the activation switch and the tail test inside it) every piece is its own chain of basic blocks that pays its own LDS
+    // round trip.  So the activation is dispatched ONCE per block (ReLU compiled in, everything else behind the run-time switch on a second
+    // copy), the tail mask is a select per element against one per-lane channel count, and the range test is the store's: a buffer
+    // descriptor of exactly this tile's rows (rows beyond M lie beyond its end) and BUF_OOB for a lane whose channels do not exist.
+    const int cg = lane & 3, n = co + cg * 8;  // this lane's 8 channels: the same for all four of its pieces
+    int left = Cout - n;                       // real channels left from the first of them
+    asm volatile("" : "+v"(left));
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(y + m0 * Cout_p, (unsigned)(min((long)XT_BM, M - m0) * Cout_p * (long)sizeof(T)));
+    const unsigned yoff = n < Cout_p ? (unsigned)(((lane >> 2) * Cout_p + n) * (int)sizeof(T)) : BUF_OOB;
+    auto epilogue = [&](auto actc) {
+    constexpr int ACTC = decltype(actc)::value;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -215,26 +244,24 @@ void pwconv_xtile_kernel(const T* __restrict__ x, const T* __restrict__ w,
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int q = lane + 64 * i;
-            const int row = q >> 2, cg = q & 3;
-            const long m = m0 + j * 32 + row;
-            const int n = co + cg * 8;
-            if (m < M && n < Cout_p) {
-                float v[8];
-                load8(scr + row * XT_SROW + cg * 8, v);
-                if (RES) {
-                    float r[8];
-                    raw_to_f8<T>(rr[j][i], r);
+            const int row = (lane >> 2) + 16 * i;
+            float v[8];
+            load8(scr + row * XT_SROW + cg * 8, v);
+            if (RES) {
+                float r[8];
+                raw_to_f8<T>(rr[j][i], r);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += r[e];
-                }
-                act_vec(v, act);
-                mask_tail(v, Cout - n);
-                store8(y + m * Cout_p + n, v);
+                for (int e = 0; e < 8; ++e) v[e] += r[e];
             }
+            act_vec<ACTC>(v, act);
+            mask_tail_sel(v, left, 0);
+            xt_store8<T>(yrsrc, yoff + (unsigned)((j * 32 + 16 * i) * Cout_p * (int)sizeof(T)), v);
         }
         __builtin_amdgcn_wave_barrier();  // the image is reused by the second position tile
     }
+    };
+    if (act == PASN_ACT_RELU) epilogue(std::integral_constant<int, PASN_ACT_RELU>{});
+    else epilogue(std::integral_constant<int, -1>{});
 }
 
 static bool xt_pointwise(const pasn_conv_desc& d) {  // any stride: a strided 1x1x1 conv is a row gather
