@@ -711,6 +711,58 @@ size_t pasn_risk_coverage_workspace_bytes(long M, int K_real);
 int pasn_risk_coverage(const float* probs, const int32_t* labels, const float* u, long M, int K_real, int32_t* order, double* acc,
                        double* bal_acc, double* f1_mean, float* threshold, double* aurc, int64_t* counts, void* workspace, void* stream);
 
+/* Grouped bootstrap of the evaluation statistics (bootstrap.py): B replicates of accuracy, balanced accuracy, mean F1, weighted
+ * one-vs-rest AUC, risk-coverage area and error-detection AUROC, resampling GROUPS of rows (the clips of one cine are correlated: the
+ * unit is the cine, or whatever key the caller grouped by).  The reference has no code for it; these definitions are the specification.
+ *
+ * Draws.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), key = (seed & 0xffffffff,
+ * seed >> 32).  Replicate b draws G units, G the number of groups: draw d (0 <= d < G) takes output word d & 3 of the call with counter
+ * (d >> 2, b, 0, 0) as a uint32 r, and the unit drawn is g = ((uint64) r * G) >> 32 (multiply-shift: a bias of at most G / 2^32, accepted).
+ * counts[b][g] is the number of draws that landed on g; a row of counts sums to G.  A replicate depends on (seed, b, G) and on nothing
+ * else: not on B, not on another replicate.
+ *
+ * pasn_bootstrap_counts: counts [B][G] int32 of the replicates b0 .. b0 + B.  1 <= G <= 2^20, 1 <= B <= 65 536, b0 >= 0.  One launch
+ * (G <= PASN_BOOTSTRAP_LDS_MAX_G: a block per replicate, the histogram in LDS) or a memset and one launch (above: global integer atomics);
+ * pasn_bootstrap_lds_max_groups() returns that bound.
+ *
+ * A replicate is the multiset of rows in which every row of group g appears counts[b][g] times, the rows in ascending row index.  Rows
+ * with label < 0 or >= K_real are padding and never enter (as in pasn_risk_coverage); neither does a row that no group lists.  Each
+ * statistic is the project's existing one applied to that expanded row list:
+ *   cm [K_real][K_real] int64   the confusion matrix [true][predicted]; a row's prediction is the first largest probability
+ *   acc, bal_acc, f1_mean       pasn_risk_coverage's formulas at full coverage (trace / W; the mean over the classes with support > 0 of
+ *                               tp / support; the mean over all classes of 2 tp / (support + predicted), 0 for a zero denominator)
+ *   u2 [K_real] int64           U2_k = sum over i positive (label k), j negative of w_i w_j (2 [s_j < s_i] + [s_j == s_i]), s = probs[.][k],
+ *                               w = the row's number of copies; n_pos_k, n_neg_k the weighted counts
+ *   auc                         sum_k n_pos_k (U2_k / (2 n_pos_k n_neg_k)) / sum_k n_pos_k: pasn_roc_auc_ovr on the expanded rows -- except
+ *                               that a replicate in which a class has no positive or no negative weight has auc = NaN, not 0.0 (a 0
+ *                               would poison an interval)
+ *   aurc (u given)              (1 / W) sum_m (1 - acc[m]) over the expanded rows in pasn_risk_coverage's order: ascending u, equal u to
+ *                               the lower row index (the copies of a row are adjacent), NaN last.  Each thread adds its positions in
+ *                               order, the threads in a fixed tree.
+ *   error_auroc (u given)       the AUROC of u as a detector of the wrong predictions: U2 / (2 W_wrong W_right); NaN when every row is
+ *                               right, every row is wrong, or a row of the replicate has a NaN u
+ * The point estimate is the same with every count equal to 1.
+ *
+ * pasn_bootstrap_metrics: probs [M][K_real] fp32, labels [M] int32, u [M] fp32 or NULL; the groups CSR as in pasn_group_predictions
+ * (int64 offsets [G + 1], int32 rows; the indices are the caller's and every row is listed at most once), or both NULL: every row is its
+ * own group and G == M.  Outputs (device memory), row b < B = replicate b, row B = the point estimate:
+ *   stats [B + 1][6] fp64 = acc, bal_acc, f1_mean, auc, aurc, error_auroc (the last two NaN without u)
+ *   cm [B + 1][K_real][K_real], u2 [B + 1][K_real], n_pos [B + 1][K_real], n_neg [B + 1][K_real] int64
+ * The expanded rows of a replicate must number less than 2^31 (G times the largest group does: the Python wrapper checks that).  NaN
+ * probabilities: unspecified.  2 <= K_real <= 16, 1 <= M <= 2^20, 1 <= G <= M, 1 <= B <= 65 536; anything else, or a NULL required
+ * pointer, returns PASN_ERR_ARG before any launch (the size query returns 0).  Stream-ordered, no host synchronisation: up to three
+ * memsets and six launches whatever B is -- the orders (a rank by counting per class column and for u) are shared by all replicates; a
+ * block owns a replicate: counts in LDS for G <= PASN_BOOTSTRAP_LDS_MAX_G, above in a slice of the workspace, the blocks looping over
+ * the replicates.  Two calls are bitwise equal.  `workspace`: pasn_bootstrap_workspace_bytes(M, G, K_real, B) bytes, 16-byte aligned,
+ * no initialisation. */
+#define PASN_BOOTSTRAP_LDS_MAX_G 16384
+int pasn_bootstrap_lds_max_groups(void);
+int pasn_bootstrap_counts(int32_t* counts, long G, int B, uint64_t seed, int b0, void* stream);
+size_t pasn_bootstrap_workspace_bytes(long M, long G, int K_real, int B);
+int pasn_bootstrap_metrics(const float* probs, const int32_t* labels, const float* u, const int64_t* group_offsets,
+                           const int32_t* group_rows, long M, long G, int K_real, int B, uint64_t seed, double* stats, int64_t* cm,
+                           int64_t* u2, int64_t* n_pos, int64_t* n_neg, void* workspace, void* stream);
+
 /* Global explanations: the k nearest clips of a split per prototype, kept on the device while a loader is swept (global_explain.py).
  * The reference ships only the raw material, the whole (clips, P) similarity matrix "for ranking prototypes"
  * (XProtoNet_Base.py:613-656 get_sim_scores / load_sim_scores; explain_global is a stub); the selection rule per batch is the push's

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_uint, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_uint, c_uint64, c_void_p
 
 F32, BF16, U8, I32 = 0, 1, 2, 3
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "swish": 3, "abs": 4}
@@ -165,6 +165,11 @@ SIGNATURES = {
     "pasn_group_predictions": (c_int, [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 7),
     "pasn_risk_coverage_workspace_bytes": (c_size_t, [c_long, c_int]),
     "pasn_risk_coverage": (c_int, [c_void_p] * 3 + [c_long, c_int] + [c_void_p] * 9),
+    # ---- bootstrap confidence intervals (bootstrap.py)
+    "pasn_bootstrap_lds_max_groups": (c_int, []),
+    "pasn_bootstrap_counts": (c_int, [c_void_p, c_long, c_int, c_uint64, c_int, c_void_p]),
+    "pasn_bootstrap_workspace_bytes": (c_size_t, [c_long, c_long, c_int, c_int]),
+    "pasn_bootstrap_metrics": (c_int, [c_void_p] * 5 + [c_long, c_long, c_int, c_int, c_uint64] + [c_void_p] * 7),
     # ---- the training loss recipe (losses.FusedCriterion)
     "pasn_proto_loss_fwd": (c_int, [c_void_p] * 13 + [POINTER(ProtoLossDesc), c_void_p]),
     "pasn_proto_loss_bwd": (c_int, [c_void_p] * 14 + [POINTER(ProtoLossDesc), c_void_p]),

@@ -1,0 +1,526 @@
+// bootstrap.hip -- grouped bootstrap replicates of the evaluation statistics (accuracy, balanced accuracy, mean F1, weighted one-vs-rest
+// AUC, risk-coverage area, error-detection AUROC).  The resampling unit is a group of rows (a cine's clips); include/protoasnet_amd.h holds
+// the definitions, tests/bootstrap_cases.py their float64 / int64 restatement.
+//
+// pasn_bootstrap_counts: the draws alone.  Draw d of replicate b is output word d & 3 of Philox4x32-10 at counter (d >> 2, b, 0, 0); the
+// unit is (r * G) >> 32.  G <= BOOT_LDS_MAX_G: a block per replicate histograms into uint16 pairs in LDS (integer LDS atomics) and writes the
+// row out; above, the threads add straight into the zeroed output (global integer atomics).
+//
+// pasn_bootstrap_metrics: what all replicates share is computed once, in five launches:
+//   1. gid: the group of every listed row (a wave per group), -1 for the others
+//   2. info: per row (group | label << 20 | first largest probability << 24), negative for a row that never enters
+//   3. rank: the rank by counting of order_key.h for every class column (ascending probability) and for u (ascending, NaN last)
+//   4. scatter: per order and position the word (group | POS | NAN) and the key; POS marks the positives of the order (label == k for
+//      column k, a wrong prediction for u)
+//   5. ties: TIE marks the first position of every run of equal keys
+// and one launch does the replicates, a block each (replicate B is the point estimate: every count 1).  The block draws its counts (LDS
+// uint16 for G <= BOOT_LDS_MAX_G; above, an int32 slice of the workspace owned by the block, blocks looping over the replicates), adds the
+// confusion matrix with integer LDS atomics, and sweeps every order in chunks of 2048 positions, eight per thread: a block-wide scan of
+// the (negative, positive) weight packed in 64 bits gives each position the weights before it, a second scan carries the prefix AT THE
+// START OF ITS TIE RUN forward, and
+//   U2 = Wp Wn + sum_{i pos} w_i Nlt_i - sum_{j neg} w_j Plt_j        (Nlt / Plt: negative / positive weight with a strictly smaller key)
+// which is sum w_i w_j (2 [s_j < s_i] + [s_j == s_i]) over the pairs, in integers.  The u order also adds the risk terms 1 - acc[m] of
+// every copy of a row, each thread its positions in order, the threads in a fixed tree.  One barrier per chunk (wave summaries in a
+// double-buffered LDS table).
+#include "common.h"
+#include "order_key.h"
+#include "philox.h"
+
+namespace pasn {
+
+constexpr int BOOT_MAX_K = 16;
+constexpr long BOOT_MAX_M = 1L << 20;
+constexpr int BOOT_MAX_B = 65536;
+constexpr int BOOT_LDS_MAX_G = PASN_BOOTSTRAP_LDS_MAX_G;  // uint16 counts: 32 KiB of LDS, four blocks per CU
+constexpr int BOOT_NT = 256, BOOT_E = 8, BOOT_CHUNK = BOOT_NT * BOOT_E;
+constexpr size_t BOOT_SLOT_BYTES = 256ull << 20;  // the count slices of the global path together
+constexpr int BOOT_MAX_SLOTS = 512;
+constexpr uint32_t BOOT_EMPTY = 0xFFFFFFFFu, BOOT_TIE = 1u << 31, BOOT_POS = 1u << 30, BOOT_NAN = 1u << 29, BOOT_GID = 0xFFFFFu;
+
+// ---- draws -------------------------------------------------------------------------------------------------------------------------------
+// counts of replicate b as uint16 pairs in s_cnt[(G + 1) / 2]; ones: the point estimate.  Ends with a barrier.
+__device__ __forceinline__ void boot_draw_lds(uint32_t* s_cnt, int G, uint32_t b, uint32_t k0, uint32_t k1, bool ones) {
+    const int tid = threadIdx.x;
+    for (int w = tid; w < (G + 1) / 2; w += BOOT_NT) s_cnt[w] = ones ? 0x00010001u : 0u;
+    __syncthreads();
+    if (!ones)
+        for (int q = tid; q < (G + 3) / 4; q += BOOT_NT) {
+            uint32_t r[4];
+            philox4x32_10((uint32_t)q, b, 0u, 0u, k0, k1, r);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * q + j < G) {
+                    const uint32_t g = philox_unit(r[j], (uint32_t)G);  // a count never exceeds G < 2^16: no carry into the neighbour
+                    atomicAdd(&s_cnt[g >> 1], 1u << (16 * (g & 1)));
+                }
+        }
+    __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t boot_count_lds(const uint32_t* s_cnt, uint32_t g) { return (s_cnt[g >> 1] >> (16 * (g & 1))) & 0xFFFFu; }
+
+// the same into an int32 slice of global memory that this block owns.  The adds happen in L2; boot_count_global reads there too.
+__device__ __forceinline__ void boot_draw_global(int32_t* cg, long G, uint32_t b, uint32_t k0, uint32_t k1, bool ones) {
+    const int tid = threadIdx.x;
+    for (long g = tid; g < G; g += BOOT_NT) cg[g] = ones ? 1 : 0;
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores have reached L2 before another wave's atomic finds the word
+    __syncthreads();
+    if (!ones)
+        for (long q = tid; q < (G + 3) / 4; q += BOOT_NT) {
+            uint32_t r[4];
+            philox4x32_10((uint32_t)q, b, 0u, 0u, k0, k1, r);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * q + j < G) atomicAdd(&cg[philox_unit(r[j], (uint32_t)G)], 1);
+        }
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t boot_count_global(const int32_t* cg, uint32_t g) {
+    return (uint32_t)__hip_atomic_load(cg + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(BOOT_NT) void boot_counts_lds_kernel(int32_t* __restrict__ counts, int G, int B, uint32_t k0, uint32_t k1, int b0) {
+    extern __shared__ uint32_t boot_lds[];
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        __syncthreads();  // the row before has been read
+        boot_draw_lds(boot_lds, G, (uint32_t)(b0 + b), k0, k1, false);
+        for (int g = threadIdx.x; g < G; g += BOOT_NT) counts[(long)b * G + g] = (int32_t)boot_count_lds(boot_lds, g);
+    }
+}
+
+// grid (blocks of 256 Philox calls, replicates); counts is zero
+__global__ __launch_bounds__(BOOT_NT) void boot_counts_global_kernel(int32_t* __restrict__ counts, long G, int B, uint32_t k0, uint32_t k1, int b0) {
+    const long q = (long)blockIdx.x * BOOT_NT + threadIdx.x;
+    if (q >= (G + 3) / 4) return;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)q, (uint32_t)(b0 + b), 0u, 0u, k0, k1, r);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * q + j < G) atomicAdd(&counts[(long)b * G + philox_unit(r[j], (uint32_t)G)], 1);
+    }
+}
+
+// ---- what the replicates share -----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void boot_gid_kernel(const int64_t* __restrict__ offs, const int32_t* __restrict__ rows, long G, long M,
+                                                       int32_t* __restrict__ gid) {
+    const long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= G) return;
+    const int64_t lo = offs[g], hi = offs[g + 1];
+    for (int64_t r = lo + (threadIdx.x & 63); r < hi; r += 64) {
+        const long i = rows[r];
+        if (i >= 0 && i < M) gid[i] = (int32_t)g;
+    }
+}
+
+__global__ __launch_bounds__(256) void boot_info_kernel(const float* __restrict__ probs, const int32_t* __restrict__ labels,
+                                                        const int32_t* __restrict__ gid, long M, int K, int32_t* __restrict__ info) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const int L = labels[i];
+    const int g = gid ? gid[i] : (int)i;
+    int v = -1;
+    if (L >= 0 && L < K && g >= 0) {
+        const float* p = probs + i * K;
+        int pred = 0;
+        float best = p[0];
+        for (int k = 1; k < K; ++k)
+            if (p[k] > best) {  // the first largest
+                best = p[k];
+                pred = k;
+            }
+        v = g | (L << 20) | (pred << 24);
+    }
+    info[i] = v;
+}
+
+struct BootGeom {
+    int gx, gy, chunk;  // row blocks, row-j chunks and their length (a multiple of the tile)
+    long Mp;            // positions of an order, padded to whole sweep chunks
+};
+
+static BootGeom boot_geom(long M) {
+    BootGeom g;
+    g.gx = ceil_div(M, RANK_TILE);
+    const long c = std::max(1024L, (long)ceil_div(M, 64));  // at most 64 chunks of >= 1024 rows
+    g.chunk = (int)(((c + RANK_TILE - 1) / RANK_TILE) * RANK_TILE);
+    g.gy = ceil_div(M, g.chunk);
+    g.Mp = (long)ceil_div(M, BOOT_CHUNK) * BOOT_CHUNK;
+    return g;
+}
+
+// key of row j in order c: column c of probs, or u for c == K; a row that never enters is padding
+__device__ __forceinline__ uint32_t boot_key(const float* __restrict__ probs, const float* __restrict__ u, const int32_t* __restrict__ info,
+                                             long j, int K, int c) {
+    if (info[j] < 0) return RC_KEY_PAD;
+    return rc_key(c < K ? probs[j * K + c] : u[j]);
+}
+
+// grid (gx, gy, orders); rank [orders][M] is zero
+__global__ __launch_bounds__(256) void boot_rank_kernel(const float* __restrict__ probs, const float* __restrict__ u,
+                                                        const int32_t* __restrict__ info, long M, int K, BootGeom g,
+                                                        int32_t* __restrict__ rank) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_key[RANK_TILE];
+    const int tid = threadIdx.x, c = blockIdx.z;
+    const long i0 = (long)blockIdx.x * RANK_TILE, i = i0 + tid;
+    const uint32_t ki = i < M ? boot_key(probs, u, info, i, K, c) : RC_KEY_PAD;
+    const bool valid = ki != RC_KEY_PAD;
+    int cnt = 0;
+    const long j0 = (long)blockIdx.y * g.chunk, j1 = min(M, j0 + (long)g.chunk);
+    for (long jt = j0; jt < j1; jt += RANK_TILE) {
+        __syncthreads();
+        const long j = jt + tid;
+        s_key[tid] = j < j1 ? boot_key(probs, u, info, j, K, c) : RC_KEY_PAD;  // the tail of a short tile counts for nobody
+        __syncthreads();
+        if (valid) cnt += rank_count_tile(s_key, ki, jt, i0, tid);
+    }
+    if (valid && cnt) atomicAdd(&rank[(long)c * M + i], cnt);
+}
+
+// grid (gx, orders); og [orders][Mp] is BOOT_EMPTY everywhere
+__global__ __launch_bounds__(256) void boot_scatter_kernel(const float* __restrict__ probs, const float* __restrict__ u,
+                                                           const int32_t* __restrict__ info, long M, int K, long Mp,
+                                                           const int32_t* __restrict__ rank, uint32_t* __restrict__ og,
+                                                           uint32_t* __restrict__ skey) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    if (i >= M) return;
+    const int v = info[i];
+    if (v < 0) return;
+    const uint32_t key = boot_key(probs, u, info, i, K, c);
+    const int L = (v >> 20) & 15, P = (v >> 24) & 15;
+    const bool pos = c < K ? L == c : L != P;
+    const long r = rank[(long)c * M + i];  // < the number of rows that enter <= M
+    og[(long)c * Mp + r] = ((uint32_t)v & BOOT_GID) | (pos ? BOOT_POS : 0u) | (c == K && key == RC_KEY_NAN ? BOOT_NAN : 0u);
+    skey[(long)c * Mp + r] = key;
+}
+
+__global__ __launch_bounds__(256) void boot_ties_kernel(long M, long Mp, uint32_t* __restrict__ og, const uint32_t* __restrict__ skey) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    const long at = (long)blockIdx.y * Mp + p;
+    if (p >= M || og[at] == BOOT_EMPTY) return;
+    if (p == 0 || skey[at] != skey[at - 1]) og[at] |= BOOT_TIE;
+}
+
+// ---- the replicates ----------------------------------------------------------------------------------------------------------------------
+struct BootArgs {
+    const int32_t* info;
+    const uint32_t* og;
+    int32_t* slots;
+    long M, Mp, G;
+    int K, orders, B;
+    uint32_t k0, k1;
+    double* stats;
+    int64_t *cm, *u2, *n_pos, *n_neg;
+};
+
+struct BootWave {  // a wave's summary of one chunk
+    unsigned long long tot, snap;
+    int flag;
+};
+
+__device__ __forceinline__ long long boot_block_sum(long long v, long long* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// One order of one replicate.  Returns (block-wide) sum_{pos} w Nlt - sum_{neg} w Plt; AURC: *risk = the sum of 1 - acc[m] over the
+// expanded rows (negatives are the right predictions), *nan_seen set when a row with weight has the NAN mark.
+template <bool LDSC, bool AURC>
+__device__ __forceinline__ long long boot_sweep(const uint32_t* __restrict__ og, long Mp, const uint32_t* s_cnt, const int32_t* cg,
+                                                BootWave (*s_ws)[4], long long* s_red, double* s_redd, double* risk, int* nan_seen) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long carry = 0ull, carry_snap = 0ull;  // (negative | positive << 32) weight before the chunk / before its open tie run
+    long long S = 0;
+    double dsum = 0.0;
+    int par = 0;
+    for (long c0 = 0; c0 < Mp; c0 += BOOT_CHUNK, par ^= 1) {
+        const uint4* src = reinterpret_cast<const uint4*>(og + c0 + (long)tid * BOOT_E);
+        const uint4 a = src[0], b = src[1];
+        const uint32_t word[BOOT_E] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        uint32_t w[BOOT_E];
+        unsigned long long tot = 0ull, rel_snap = 0ull;
+        int hf = 0;
+#pragma unroll
+        for (int e = 0; e < BOOT_E; ++e) {
+            w[e] = word[e] == BOOT_EMPTY ? 0u : (LDSC ? boot_count_lds(s_cnt, word[e] & BOOT_GID) : boot_count_global(cg, word[e] & BOOT_GID));
+            if (word[e] & BOOT_TIE) {
+                hf = 1;
+                rel_snap = tot;
+            }
+            tot += (word[e] & BOOT_POS) ? (unsigned long long)w[e] << 32 : (unsigned long long)w[e];
+        }
+        unsigned long long inc = tot;  // inclusive scan over the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long v = __shfl_up(inc, o);
+            if (lane >= o) inc += v;
+        }
+        const unsigned long long ex_w = inc - tot;
+        unsigned long long ps = ex_w + rel_snap;  // the latest tie start at or before this thread's last position, relative to the wave
+        int pf = hf;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long s = __shfl_up(ps, o);
+            const int f = __shfl_up(pf, o);
+            if (lane >= o && !pf) {
+                ps = s;
+                pf = f;
+            }
+        }
+        unsigned long long in_s = __shfl_up(ps, 1);
+        int in_f = __shfl_up(pf, 1);
+        if (lane == 0) in_f = 0;
+        if (lane == 63) {
+            s_ws[par][wave].tot = inc;
+            s_ws[par][wave].snap = ps;
+            s_ws[par][wave].flag = pf;
+        }
+        __syncthreads();  // (the table of the chunk before is free again once every wave has passed this barrier)
+        unsigned long long off = carry, snap = carry_snap, woff = carry, wsnap = carry_snap;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const BootWave t = s_ws[par][v];
+            if (t.flag) snap = off + t.snap;
+            off += t.tot;
+            if (v + 1 == wave) {
+                woff = off;
+                wsnap = snap;
+            }
+        }
+        if (wave == 0) {
+            woff = carry;
+            wsnap = carry_snap;
+        }
+        carry = off;
+        carry_snap = snap;
+        unsigned long long run = woff + ex_w, cur = in_f ? woff + in_s : wsnap;
+#pragma unroll
+        for (int e = 0; e < BOOT_E; ++e) {
+            if (word[e] & BOOT_TIE) cur = run;
+            const bool pos = (word[e] & BOOT_POS) != 0u;
+            if (w[e]) {
+                if (pos) S += (long long)w[e] * (long long)(cur & 0xFFFFFFFFull);
+                else S -= (long long)w[e] * (long long)(cur >> 32);
+                if (AURC) {
+                    if (word[e] & BOOT_NAN) *nan_seen = 1;
+                    const long long C = (long long)(run & 0xFFFFFFFFull), T = C + (long long)(run >> 32);
+                    for (uint32_t t = 1; t <= w[e]; ++t) dsum += 1.0 - (double)(C + (pos ? 0 : (long long)t)) / (double)(T + t);
+                }
+            }
+            run += pos ? (unsigned long long)w[e] << 32 : (unsigned long long)w[e];
+        }
+    }
+    if (AURC) {
+        for (int o = 32; o > 0; o >>= 1) dsum += __shfl_xor(dsum, o);
+        __syncthreads();
+        if (lane == 0) s_redd[wave] = dsum;
+        __syncthreads();
+        *risk = (s_redd[0] + s_redd[1]) + (s_redd[2] + s_redd[3]);
+    }
+    return boot_block_sum(S, s_red);
+}
+
+template <bool LDSC>
+__global__ __launch_bounds__(BOOT_NT) void boot_metrics_kernel(BootArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ uint32_t boot_lds[];
+    __shared__ uint32_t s_cm[BOOT_MAX_K * BOOT_MAX_K];
+    __shared__ BootWave s_ws[2][4];
+    __shared__ long long s_red[4];
+    __shared__ double s_redd[4];
+    __shared__ long long s_s[BOOT_MAX_K + 1];
+    __shared__ int s_nan;
+    const int tid = threadIdx.x, K = a.K;
+    int32_t* cg = LDSC ? nullptr : a.slots + (long)blockIdx.x * a.G;
+    for (int b = blockIdx.x; b <= a.B; b += gridDim.x) {
+        __syncthreads();  // the replicate before is finished with the counts and the tables
+        if (LDSC) boot_draw_lds(boot_lds, (int)a.G, (uint32_t)b, a.k0, a.k1, b == a.B);
+        else boot_draw_global(cg, a.G, (uint32_t)b, a.k0, a.k1, b == a.B);
+        if (tid < K * K) s_cm[tid] = 0u;
+        if (tid == 0) s_nan = 0;
+        __syncthreads();
+        for (long i = tid; i < a.M; i += BOOT_NT) {
+            const int v = a.info[i];
+            if (v < 0) continue;
+            const uint32_t w = LDSC ? boot_count_lds(boot_lds, v & BOOT_GID) : boot_count_global(cg, v & BOOT_GID);
+            if (w) atomicAdd(&s_cm[((v >> 20) & 15) * K + ((v >> 24) & 15)], w);
+        }
+        __syncthreads();
+        double risk = 0.0;
+        for (int c = 0; c < a.orders; ++c) {
+            const uint32_t* og = a.og + (long)c * a.Mp;
+            const long long s = c < K ? boot_sweep<LDSC, false>(og, a.Mp, boot_lds, cg, s_ws, s_red, s_redd, nullptr, nullptr)
+                                      : boot_sweep<LDSC, true>(og, a.Mp, boot_lds, cg, s_ws, s_red, s_redd, &risk, &s_nan);
+            if (tid == 0) s_s[c] = s;
+        }
+        __syncthreads();
+        if (tid != 0) continue;
+        long long W = 0, trace = 0;
+        for (int e = 0; e < K * K; ++e) {
+            W += s_cm[e];
+            a.cm[(long)b * K * K + e] = s_cm[e];
+        }
+        double rsum = 0.0, fsum = 0.0, num = 0.0, den = 0.0;
+        int present = 0;
+        bool defined = true;
+        for (int k = 0; k < K; ++k) {
+            long long sup = 0, prd = 0;
+            for (int j = 0; j < K; ++j) {
+                sup += s_cm[k * K + j];
+                prd += s_cm[j * K + k];
+            }
+            const long long tp = s_cm[k * K + k], nneg = W - sup, u2 = sup * nneg + s_s[k];
+            trace += tp;
+            if (sup > 0) {
+                rsum += (double)tp / (double)sup;
+                ++present;
+            }
+            if (sup + prd > 0) fsum += 2.0 * (double)tp / (double)(sup + prd);
+            a.u2[(long)b * K + k] = u2;
+            a.n_pos[(long)b * K + k] = sup;
+            a.n_neg[(long)b * K + k] = nneg;
+            if (sup > 0 && nneg > 0) {
+                num += (double)sup * ((double)u2 / (2.0 * (double)sup * (double)nneg));
+                den += (double)sup;
+            } else {
+                defined = false;  // a class the replicate lost: no AUC, and a 0 would poison the interval
+            }
+        }
+        const double nan = __builtin_nan("");
+        double* st = a.stats + (long)b * 6;
+        st[0] = W > 0 ? (double)trace / (double)W : 0.0;
+        st[1] = present > 0 ? rsum / (double)present : 0.0;
+        st[2] = fsum / (double)K;
+        st[3] = defined ? num / den : nan;
+        st[4] = nan;
+        st[5] = nan;
+        if (a.orders > K) {
+            const long long wrong = W - trace;
+            st[4] = W > 0 ? risk / (double)W : nan;
+            if (!s_nan && wrong > 0 && trace > 0) st[5] = (double)(wrong * trace + s_s[K]) / (2.0 * (double)wrong * (double)trace);
+        }
+    }
+}
+
+struct BootWorkspace {
+    uint32_t *og, *skey;
+    int32_t *rank, *gid, *info, *slots;
+    int nslots;
+    size_t bytes;
+};
+
+static int boot_slots(long G, int B) {
+    if (G <= BOOT_LDS_MAX_G) return 0;
+    const long fit = std::max(1L, (long)(BOOT_SLOT_BYTES / ((size_t)G * sizeof(int32_t))));
+    return (int)std::min({(long)B + 1, (long)BOOT_MAX_SLOTS, fit});
+}
+
+static BootWorkspace boot_workspace(void* ws, long M, long G, int K, int B, const BootGeom& g) {
+    BootWorkspace w;
+    char* p = static_cast<char*>(ws);
+    const size_t orders = (size_t)K + 1;
+    w.og = reinterpret_cast<uint32_t*>(p);
+    p += orders * g.Mp * sizeof(uint32_t);
+    w.skey = reinterpret_cast<uint32_t*>(p);
+    p += orders * g.Mp * sizeof(uint32_t);
+    w.rank = reinterpret_cast<int32_t*>(p);
+    p += orders * M * sizeof(int32_t);
+    w.gid = reinterpret_cast<int32_t*>(p);
+    p += (size_t)M * sizeof(int32_t);
+    w.info = reinterpret_cast<int32_t*>(p);
+    p += (size_t)M * sizeof(int32_t);
+    w.nslots = boot_slots(G, B);
+    w.slots = reinterpret_cast<int32_t*>(p);
+    p += (size_t)w.nslots * G * sizeof(int32_t);
+    w.bytes = (size_t)(p - static_cast<char*>(ws));
+    return w;
+}
+
+static bool boot_sizes_ok(long M, long G, int K, int B) {
+    return K >= 2 && K <= BOOT_MAX_K && M >= 1 && M <= BOOT_MAX_M && G >= 1 && G <= M && B >= 1 && B <= BOOT_MAX_B;
+}
+
+}  // namespace pasn
+
+using namespace pasn;
+
+extern "C" int pasn_bootstrap_lds_max_groups(void) { return BOOT_LDS_MAX_G; }
+
+extern "C" int pasn_bootstrap_counts(int32_t* counts, long G, int B, uint64_t seed, int b0, void* stream) {
+    PASN_REQUIRE(counts, "counts is required");
+    PASN_REQUIRE(G >= 1 && G <= BOOT_MAX_M, "G must lie in [1, 2^20]");
+    PASN_REQUIRE(B >= 1 && B <= BOOT_MAX_B, "B must lie in [1, 65536]");
+    PASN_REQUIRE(b0 >= 0 && (long)b0 + B <= (1L << 31) - 1, "b0 must not be negative, and b0 + B must fit an int32");
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
+    if (G <= BOOT_LDS_MAX_G) {
+        hipLaunchKernelGGL(boot_counts_lds_kernel, dim3(B), dim3(BOOT_NT), (size_t)((G + 1) / 2) * sizeof(uint32_t), s, counts, (int)G, B, k0, k1, b0);
+    } else {
+        if (hipMemsetAsync(counts, 0, (size_t)B * G * sizeof(int32_t), s) != hipSuccess) return check_launch("bootstrap_counts (zeroing)");
+        hipLaunchKernelGGL(boot_counts_global_kernel, dim3(ceil_div((G + 3) / 4, BOOT_NT), std::min(B, 4096)), dim3(BOOT_NT), 0, s, counts, G, B, k0,
+                           k1, b0);
+    }
+    return check_launch("bootstrap_counts");
+}
+
+extern "C" size_t pasn_bootstrap_workspace_bytes(long M, long G, int K_real, int B) {
+    if (!boot_sizes_ok(M, G, K_real, B)) return 0;
+    return boot_workspace(nullptr, M, G, K_real, B, boot_geom(M)).bytes;
+}
+
+extern "C" int pasn_bootstrap_metrics(const float* probs, const int32_t* labels, const float* u, const int64_t* group_offsets,
+                                      const int32_t* group_rows, long M, long G, int K_real, int B, uint64_t seed, double* stats, int64_t* cm,
+                                      int64_t* u2, int64_t* n_pos, int64_t* n_neg, void* workspace, void* stream) {
+    PASN_REQUIRE(probs && labels, "probs and labels are required");
+    PASN_REQUIRE(stats && cm && u2 && n_pos && n_neg, "every output is required");
+    PASN_REQUIRE(workspace, "workspace is required");
+    PASN_REQUIRE((group_offsets == nullptr) == (group_rows == nullptr), "group_offsets and group_rows come together");
+    PASN_REQUIRE(K_real >= 2 && K_real <= BOOT_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(M >= 1 && M <= BOOT_MAX_M, "M must lie in [1, 2^20]");
+    PASN_REQUIRE(G >= 1 && G <= M, "G must lie in [1, M]");
+    PASN_REQUIRE(group_offsets || G == M, "without groups every row is its own group: G must equal M");
+    PASN_REQUIRE(B >= 1 && B <= BOOT_MAX_B, "B must lie in [1, 65536]");
+    PASN_REQUIRE(((uintptr_t)workspace & 15) == 0, "misaligned workspace");
+    const BootGeom g = boot_geom(M);
+    const BootWorkspace w = boot_workspace(workspace, M, G, K_real, B, g);
+    const int orders = u ? K_real + 1 : K_real;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(w.og, 0xFF, (size_t)orders * g.Mp * sizeof(uint32_t), s) != hipSuccess ||
+        hipMemsetAsync(w.rank, 0, (size_t)orders * M * sizeof(int32_t), s) != hipSuccess ||
+        (group_offsets && hipMemsetAsync(w.gid, 0xFF, (size_t)M * sizeof(int32_t), s) != hipSuccess))
+        return check_launch("bootstrap_metrics (zeroing)");
+    if (group_offsets) hipLaunchKernelGGL(boot_gid_kernel, dim3(ceil_div(G, 4)), dim3(256), 0, s, group_offsets, group_rows, G, M, w.gid);
+    hipLaunchKernelGGL(boot_info_kernel, dim3(g.gx), dim3(256), 0, s, probs, labels, group_offsets ? w.gid : nullptr, M, K_real, w.info);
+    hipLaunchKernelGGL(boot_rank_kernel, dim3(g.gx, g.gy, orders), dim3(256), 0, s, probs, u, w.info, M, K_real, g, w.rank);
+    hipLaunchKernelGGL(boot_scatter_kernel, dim3(g.gx, orders), dim3(256), 0, s, probs, u, w.info, M, K_real, g.Mp, w.rank, w.og, w.skey);
+    hipLaunchKernelGGL(boot_ties_kernel, dim3(g.gx, orders), dim3(256), 0, s, M, g.Mp, w.og, w.skey);
+    BootArgs a;
+    a.info = w.info;
+    a.og = w.og;
+    a.slots = w.slots;
+    a.M = M;
+    a.Mp = g.Mp;
+    a.G = G;
+    a.K = K_real;
+    a.orders = orders;
+    a.B = B;
+    a.k0 = (uint32_t)(seed & 0xffffffffull);
+    a.k1 = (uint32_t)(seed >> 32);
+    a.stats = stats;
+    a.cm = cm;
+    a.u2 = u2;
+    a.n_pos = n_pos;
+    a.n_neg = n_neg;
+    if (w.nslots == 0)
+        hipLaunchKernelGGL(boot_metrics_kernel<true>, dim3(B + 1), dim3(BOOT_NT), (size_t)((G + 1) / 2) * sizeof(uint32_t), s, a);
+    else
+        hipLaunchKernelGGL(boot_metrics_kernel<false>, dim3(w.nslots), dim3(BOOT_NT), 0, s, a);
+    return check_launch("bootstrap_metrics");
+}

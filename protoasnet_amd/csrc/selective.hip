@@ -23,15 +23,15 @@
 //      the order of arrival cannot matter.  The block also adds its (1 - acc) terms in a fixed tree.
 //   5. aurc: the blocks' partial sums in a fixed tree, over Mv.
 #include "common.h"
+#include "order_key.h"  // rc_key, rank_count_tile (shared with bootstrap.hip)
 
 namespace pasn {
 
 constexpr int SEL_MAX_K = 16;
-constexpr int SEL_TILE = 256;
+constexpr int SEL_TILE = RANK_TILE;
 constexpr int GP_WAVE_ROWS = 64;   // larger groups get the block
 constexpr int RC_SCAN = 1024;      // positions per scan block: 4 per thread
 constexpr long RC_MAX_M = 1L << 20;
-constexpr uint32_t RC_KEY_NAN = 0xFFFFFFFEu, RC_KEY_PAD = 0xFFFFFFFFu;
 
 // ---- uncertainty scores ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void uncertainty_scores_kernel(const float* __restrict__ logits, long M, int K, int K_real, int mode,
@@ -165,13 +165,6 @@ static RcGeom rc_geom(long M) {
     return g;
 }
 
-// a uint32 that orders as the floats do: -0 and +0 share a key, NaN lies above +inf (0xFF800000) and padding above NaN
-__device__ __forceinline__ uint32_t rc_key(float v) {
-    if (v != v) return RC_KEY_NAN;
-    const uint32_t b = v == 0.0f ? 0u : __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 __global__ __launch_bounds__(256) void rc_rank_kernel(const float* __restrict__ u, const int32_t* __restrict__ labels, long M, int K,
                                                       RcGeom g, int32_t* __restrict__ rank, unsigned long long* __restrict__ counts) {
     __shared__ __attribute__((aligned(16))) uint32_t s_key[SEL_TILE];
@@ -210,25 +203,7 @@ __global__ __launch_bounds__(256) void rc_rank_kernel(const float* __restrict__ 
         }
         __syncthreads();
         if (!valid) continue;
-        const uint4* s4 = reinterpret_cast<const uint4*>(s_key);
-        if (jt < i0) {  // every j of the tile lies before i: equal keys come first
-#pragma unroll 8
-            for (int t = 0; t < SEL_TILE / 4; ++t) {
-                const uint4 k4 = s4[t];
-                cnt += (k4.x <= ki) + (k4.y <= ki) + (k4.z <= ki) + (k4.w <= ki);
-            }
-        } else if (jt > i0) {
-#pragma unroll 8
-            for (int t = 0; t < SEL_TILE / 4; ++t) {
-                const uint4 k4 = s4[t];
-                cnt += (k4.x < ki) + (k4.y < ki) + (k4.z < ki) + (k4.w < ki);
-            }
-        } else {  // the block's own rows
-            for (int t = 0; t < SEL_TILE; ++t) {
-                const uint32_t kj = s_key[t];
-                cnt += (kj < ki) || (kj == ki && t < tid);
-            }
-        }
+        cnt += rank_count_tile(s_key, ki, jt, i0, tid);
     }
     if (valid && cnt) atomicAdd(&rank[i], cnt);
 }

@@ -12,7 +12,8 @@ definitions below ("Selective prediction"; ``include/protoasnet_
   of that order, the accuracy, balanced accuracy and mean F1 of ``trainer.confusion_to_metrics``; ``aurc`` is the mean error over all
   prefixes (the area under the risk-coverage curve), ``error_auroc`` the AUROC of ``u`` as a detector of the wrong predictions.
 * ``SelectiveEvaluator``: an ``EpochEvaluator(keep_logits=True)`` fed batch by batch together with the clips' file names; ``finish`` gives
-  the curve read at a few coverages, per clip or per cine, with ONE synchronising device-to-host copy.
+  the curve read at a few coverages, per clip or per cine, with ONE synchronising device-to-host copy; ``finish(bootstrap=B)`` adds
+  grouped-bootstrap confidence intervals (``bootstrap.py``) to the same read.
 
 Everything runs on the device on the caller's stream; there is no CPU fallback.
 """
@@ -232,9 +233,24 @@ class SelectiveEvaluator:
         self.ev.update(logits, sim, target)
         self.keys += keys
 
-    def finish(self, coverages=DEFAULT_COVERAGES, level: str = "clip") -> Dict[str, object]:
+    def finish(self, coverages=DEFAULT_COVERAGES, level: str = "clip", bootstrap: int = 0, seed: int = 0, confidence: float = 0.95,
+               unit: str = "cine") -> Dict[str, object]:
+        """``bootstrap=B > 0`` adds ``res["ci"]``: ``bootstrap.intervals`` of ``B`` grouped replicates (``seed``, ``confidence``) of the
+        rows the level scores -- at cine level the cine predictions, the unit the cine; at clip level the clips, the unit the cine
+        (``build_groups`` of the keys) or, with ``unit="clip"``, the clip.  Still one synchronising read; ``bootstrap=0`` is the call
+        without it, launch for launch."""
         if level not in ("clip", "cine"):
             raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
+        if unit not in ("clip", "cine"):
+            raise ValueError(f"unit must be 'clip' or 'cine', got {unit!r}")
+        if isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer)) or bootstrap < 0:
+            raise ValueError(f"bootstrap must be a non-negative integer, got {bootstrap!r}")
+        boot = None
+        if bootstrap:
+            from . import bootstrap as boot
+
+            boot.check_confidence(confidence)
+            boot._check_B_seed(bootstrap, seed)
         cs = _check_coverages(coverages)
         ev, K = self.ev, self.ev.K_real
         if ev.rows == 0:
@@ -242,8 +258,14 @@ class SelectiveEvaluator:
         probs, labels = ev.probs[: ev.rows], ev.labels[: ev.rows]
         u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
         if level == "clip":
-            host = risk_coverage(probs, labels, u).packed(cs).cpu()
-            return self._result(RiskCoverage.unpack(host, cs))
+            packed = risk_coverage(probs, labels, u).packed(cs)
+            if boot is None:
+                return self._result(RiskCoverage.unpack(packed.cpu(), cs))
+            rep = boot.replicates(probs, labels, u, build_groups(self.keys)[:2] if unit == "cine" else None, bootstrap, seed)
+            host = torch.cat([packed, rep.stats.flatten()]).cpu()  # the one read
+            res = self._result(RiskCoverage.unpack(host[: packed.numel()], cs))
+            res["ci"] = boot.intervals_of(host[packed.numel():].view(bootstrap + 1, 6).numpy(), confidence)
+            return res
         offsets, rows, names = build_groups(self.keys)
         G = len(names)
         gp = group_predictions(probs, u, labels, (offsets, rows), check=False)
@@ -253,6 +275,8 @@ class SelectiveEvaluator:
         auc, auc_k = roc_auc_ovr_weighted(p, gl, K, per_class=True)
         rc = risk_coverage(p, gl, gp.u_mean.float())
         tail = [gp.status.double(), cm.double(), auc.reshape(1), auc_k, gp.p_conf.flatten(), gp.u_mean, gl.double(), gp.counts.double(), pred.double()]
+        if boot is not None:  # the rows are the cine predictions: every row is its own unit
+            tail.append(boot.replicates(p, gl, gp.u_mean.float(), None, bootstrap, seed).stats.flatten())
         host = torch.cat([rc.packed(cs)] + tail).cpu()  # the one read
         n_rc = 5 * len(cs) + 4
         res = self._result(RiskCoverage.unpack(host[:n_rc], cs))
@@ -268,6 +292,8 @@ class SelectiveEvaluator:
         um, lab, cnt, prd = (t[o + G * K + j * G: o + G * K + (j + 1) * G] for j in range(4))
         res["cines"] = [{"filename": n, "target_AS": l, "n_clips": c, "probs": p, "uncertainty": x, "pred": d}
                         for n, l, c, p, x, d in zip(names, lab.long().tolist(), cnt.long().tolist(), pc, um.tolist(), prd.long().tolist())]
+        if boot is not None:
+            res["ci"] = boot.intervals_of(t[o + G * K + 4 * G:].view(bootstrap + 1, 6).numpy(), confidence)
         return res
 
     @staticmethod

@@ -445,7 +445,8 @@ class DPTrainer:
             raise ValueError("evaluate runs an evaluation epoch: val, val_push or test")
         return self.run_epoch(self.current_epoch, mode)
 
-    def evaluate_selective(self, mode: str = "test", level: str = "cine", coverages=(1.0, 0.9, 0.8, 0.7, 0.5), score: str = "auto") -> Dict[str, object]:
+    def evaluate_selective(self, mode: str = "test", level: str = "cine", coverages=(1.0, 0.9, 0.8, 0.7, 0.5), score: str = "auto",
+                           bootstrap: int = 0, seed: int = 0, confidence: float = 0.95, unit: str = "cine") -> Dict[str, object]:
         """Selective-prediction metrics of ``data_loaders[mode]`` (``protoasnet_amd.selective``): an eval-mode, forward-only sweep (no
         loss; the ``staged`` / ``prepare_input`` path of ``run_epoch``), the clips grouped by ``sample["filename"]`` -- with
         ``iterate_intervals`` every cardiac cycle of a cine is a row of its own -- and ``SelectiveEvaluator.finish(coverages, level)``'s
@@ -453,7 +454,8 @@ class DPTrainer:
         uncertainty is ``score`` (``auto``: the abstention output when the config has ``abstain_class``, else 1 - the largest
         probability; ``CeLossAbstain``'s ``ab_logitpath`` says how the abstention logit is read).  With ``save_dir`` set and
         ``level="cine"`` it writes ``save_dir/csv_<mode>_cine/e<epoch>.csv``: ``filename, target_AS, n_clips, prob_<label>...,
-        uncertainty, pred``.
+        uncertainty, pred``.  ``bootstrap=B > 0`` adds ``res["ci"]``: grouped-bootstrap confidence intervals of the level's rows
+        (``SelectiveEvaluator.finish``; ``protoasnet_amd.bootstrap``), each rank on its own loader's rows.
 
         It issues NO collectives: each rank that calls it sweeps the loader it was given and reports on those rows alone (call it on one
         rank with the full loader, or on every rank for per-shard figures; ranks need not call it together).  The model is left in the
@@ -477,7 +479,7 @@ class DPTrainer:
                 for sample in self.staged(loader):
                     logit, similarities, _ = self.model(self.prepare_input(sample["cine"]))
                     sel.update(logit, similarities, sample["target_AS"].to(self.device, non_blocking=True), list(sample["filename"]))
-            res = sel.finish(coverages, level)
+            res = sel.finish(coverages, level, bootstrap=bootstrap, seed=seed, confidence=confidence, unit=unit)
         finally:
             self.model.train(was_training)
         self.log(f"Epoch: {self.current_epoch} | {mode} | selective ({level}) | AURC {res['aurc']:.4f} | error AUROC {res['error_auroc']:.4f}")
