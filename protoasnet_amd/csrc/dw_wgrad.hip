@@ -1,5 +1,11 @@
 // dw_wgrad.hip -- the depthwise convs' backward: input gradient (any window / stride, and the 3x3x3 stride-(1,2,2) patch form) and the
-// five weight-gradient kernels (row partials, strip, two T-marching cuts, temporal) with their host ladder.
+// five weight-gradient kernels (row partials, strip, two T-marching cuts, temporal) with their host ladder.  Every weight-gradient kernel
+// leaves one partial row per block through block_reduce_rows (block_reduce.h: the fixed summation order shared with train.hip), and
+// dw_wgrad_reduce_kernel combines the rows in index order; the two marching kernels share their tap FMA against the gradient ring
+// (march_row_fma).
+#include <type_traits>
+
+#include "block_reduce.h"
 #include "common.h"
 
 namespace pasn {
@@ -89,33 +95,10 @@ __global__ __launch_bounds__(256) void dw_wgrad_partial_kernel(const T* __restri
         }
     }
     const int taps = d.kt * KP;
-    float* out = partial + ((size_t)blockIdx.x * taps + (size_t)a * KP) * d.Cout_p;
-#pragma unroll
-    for (int p = 0; p < 9; ++p) {
-        if (p < KP) {
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = acc[p][j];
-            __syncthreads();
-            for (int t = threadIdx.x; t < CGb * 8; t += 256) {
-                const int g2 = t >> 3, j = t & 7;
-                if (g2 < CG) {
-                    float s = 0.0f;
-                    for (int q = 0; q < RL; ++q) s += red[(q * CGb + g2) * 8 + j];
-                    out[(size_t)p * d.Cout_p + g2 * 8 + j] = s;
-                }
-            }
-        }
-    }
+    block_reduce_rows(acc, red, partial + ((size_t)blockIdx.x * taps + (size_t)a * KP) * d.Cout_p, d.Cout_p, CG, CGb, KP);
 }
 
 __global__ void dw_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int chunks, int taps, int C, int Cp);
-
-static int pow2_at_least(int v) {  // a block's channel groups, padded so that they divide its 256 threads
-    int b = 1;
-    while (b < v) b <<= 1;
-    return b;
-}
 
 static long dw_wgrad_rows_per_chunk(const pasn_conv_desc& d) {
     const long R = (long)d.N * d.To * d.Ho * d.Wo;
@@ -131,20 +114,10 @@ using namespace pasn;
 // 3x3x3, stride (1,2,2), pad 1 (the first block of every X3D stage): a thread owns a 2x2 input patch.  Even rows / columns
 // see only the centre tap, odd ones the two outer taps, so the four pixels need dy[to][i..i+1][j..j+1] for the three temporal
 // taps -- 12 loads and 27 FMAs per channel for 4 outputs, no divergent tap loop.
-template <int CH, typename T>
-__device__ __forceinline__ void dg_load(const T* p, float (&v)[CH]) {
-    if constexpr (CH == 8) load8(p, v);
-    else load4(p, v);
-}
-template <int CH, typename T>
-__device__ __forceinline__ void dg_store(T* p, const float (&v)[CH]) {
-    if constexpr (CH == 8) store8(p, v);
-    else store4(p, v);
-}
-
-template <typename T, int CH>  // CH channels per thread: 4 keeps the patch + taps + gradients at ~130 registers (8: 330, one wave per SIMD)
+template <typename T>
 __global__ __launch_bounds__(256) void dw_dgrad_s2_kernel(const T* __restrict__ dy, const float* __restrict__ w, T* __restrict__ dx,
                                                           pasn_conv_desc d) {
+    constexpr int CH = 4;  // channels per thread: 4 keeps the patch + taps + gradients at ~130 registers (8: 330, one wave per SIMD)
     // the 27 x Cp taps in LDS, staged once per block (the first version read its 27 weight vectors per patch from global memory: 864
     // bytes of weights for 192 bytes of gradients per thread)
     extern __shared__ __attribute__((aligned(16))) float wl[];  // [27][Cp]
@@ -180,7 +153,7 @@ __global__ __launch_bounds__(256) void dw_dgrad_s2_kernel(const T* __restrict__ 
                 for (int b = 0; b < 2; ++b) {
                     const int ho = i + a, wo = j + b;
                     const bool ok = tok && ho < d.Ho && wo < d.Wo;
-                    dg_load<CH>(dy + ((((size_t)n * d.To + (tok ? to : 0)) * d.Ho + (ok ? ho : 0)) * d.Wo + (ok ? wo : 0)) * d.Cout_p + cg * CH, g[kt][a][b]);
+                    load4(dy + ((((size_t)n * d.To + (tok ? to : 0)) * d.Ho + (ok ? ho : 0)) * d.Wo + (ok ? wo : 0)) * d.Cout_p + cg * CH, g[kt][a][b]);
                     okbits |= (ok ? 1u : 0u) << (kt * 4 + a * 2 + b);
                 }
         }
@@ -197,7 +170,7 @@ __global__ __launch_bounds__(256) void dw_dgrad_s2_kernel(const T* __restrict__ 
             const float* wk = wl + kt * 9 * d.Cout_p + cg * CH;
             float wv[9][CH];
 #pragma unroll
-            for (int tp = 0; tp < 9; ++tp) dg_load<CH>(wk + tp * d.Cout_p, wv[tp]);
+            for (int tp = 0; tp < 9; ++tp) load4(wk + tp * d.Cout_p, wv[tp]);
             // input (2i+a, 2j+b) <- output (ho, wo) through tap (kh, kw) with 2*ho - 1 + kh = 2i + a
 #pragma unroll
             for (int e = 0; e < CH; ++e) {
@@ -213,30 +186,38 @@ __global__ __launch_bounds__(256) void dw_dgrad_s2_kernel(const T* __restrict__ 
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 const int hi = 2 * i + a, wi = 2 * j + b;
-                if (hi < d.Hi && wi < d.Wi) dg_store<CH>(dx + ((((size_t)n * d.Ti + ti) * d.Hi + hi) * d.Wi + wi) * d.Cin_p + cg * CH, o[a][b]);
+                if (hi < d.Hi && wi < d.Wi) store4(dx + ((((size_t)n * d.Ti + ti) * d.Hi + hi) * d.Wi + wi) * d.Cin_p + cg * CH, o[a][b]);
             }
     }
+}
+
+// f((T*)nullptr) with T the element type of `dtype`; in f: `using T = elem_t<decltype(tag)>`
+template <typename F>
+static void with_dtype(int dtype, F f) {
+    if (dtype == PASN_BF16) f((__bf16*)nullptr);
+    else f((float*)nullptr);
+}
+template <typename P>
+using elem_t = std::remove_pointer_t<P>;
+// one launch of 256-thread blocks
+template <typename K, typename... A>
+static void launch256(K kernel, dim3 grid, size_t lds, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, args...);
 }
 
 extern "C" int pasn_dwconv3d_dgrad(const void* dy, const float* w, void* dx, const pasn_conv_desc* d, int dtype, void* stream) {
     PASN_REQUIRE(dy && w && dx && d, "null pointer");
     PASN_REQUIRE(d->Cin_p == d->Cout_p && d->Cin_p % 8 == 0, "depthwise conv keeps the channel stride");
-    if (d->kt == 3 && d->kh == 3 && d->kw == 3 && d->st == 1 && d->sh == 2 && d->sw == 2 && d->pt == 1 && d->ph == 1 && d->pw == 1 &&
-        d->Cout_p <= 512 && !tune("PASN_NO_DGRAD_S2")) {
-        const size_t items = (size_t)d->N * d->Ti * ((d->Hi + 1) / 2) * ((d->Wi + 1) / 2) * (d->Cin_p / 4);
-        const int nb = (int)std::min<size_t>((items + 255) / 256, 4096);  // grid-stride: the weight staging amortises over many patches
-        const size_t wlds = (size_t)27 * d->Cout_p * sizeof(float);  // <= 55 KB (Cout_p <= 512 checked above)
-        if (dtype == PASN_BF16)
-            hipLaunchKernelGGL((dw_dgrad_s2_kernel<__bf16, 4>), dim3(nb), dim3(256), wlds, (hipStream_t)stream, (const __bf16*)dy, w, (__bf16*)dx, *d);
-        else
-            hipLaunchKernelGGL((dw_dgrad_s2_kernel<float, 4>), dim3(nb), dim3(256), wlds, (hipStream_t)stream, (const float*)dy, w, (float*)dx, *d);
-        return check_launch("dwconv3d_dgrad");
-    }
-    const size_t total = (size_t)d->N * d->Ti * d->Hi * d->Wi * (d->Cin_p / 8);
-    const int blocks = (int)std::min<size_t>((total + 255) / 256, 1 << 20);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == PASN_BF16) hipLaunchKernelGGL(dw_dgrad_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)dy, w, (__bf16*)dx, *d);
-    else hipLaunchKernelGGL(dw_dgrad_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)dy, w, (float*)dx, *d);
+    const bool s2 = d->kt == 3 && d->kh == 3 && d->kw == 3 && d->st == 1 && d->sh == 2 && d->sw == 2 && d->pt == 1 && d->ph == 1 && d->pw == 1 &&
+                    d->Cout_p <= 512 && !tune("PASN_NO_DGRAD_S2");
+    // the patch form is grid-stride (its weight staging amortises over many patches), 27 x Cp taps in LDS: <= 55 KB (Cout_p <= 512 checked above)
+    const size_t items = s2 ? (size_t)d->N * d->Ti * ((d->Hi + 1) / 2) * ((d->Wi + 1) / 2) * (d->Cin_p / 4) : (size_t)d->N * d->Ti * d->Hi * d->Wi * (d->Cin_p / 8);
+    const int blocks = (int)std::min<size_t>((items + 255) / 256, s2 ? 4096 : 1 << 20);
+    const size_t lds = s2 ? (size_t)27 * d->Cout_p * sizeof(float) : 0;
+    with_dtype(dtype, [&](auto tag) {
+        using T = elem_t<decltype(tag)>;
+        launch256(s2 ? dw_dgrad_s2_kernel<T> : dw_dgrad_kernel<T>, dim3(blocks), lds, (hipStream_t)stream, (const T*)dy, w, (T*)dx, *d);
+    });
     return check_launch("dwconv3d_dgrad");
 }
 
@@ -247,19 +228,14 @@ extern "C" int pasn_dwconv3d_dgrad(const void* dy, const float* w, void* dx, con
 // division per row); the item decomposition is done once.  Partials per block, fixed-order combine by dw_wgrad_reduce_kernel.
 namespace pasn {
 
-template <int CH, typename T>
-__device__ __forceinline__ void loadc(const T* p, float (&v)[CH]) {
-    if constexpr (CH == 8) load8(p, v);
-    else load4(p, v);
-}
-
-// CH channels per thread (4: half the registers of 8, twice the resident waves -- the kernel is bound by load latency, not by
+// CH = 4 channels per thread (half the registers of 8, twice the resident waves -- the kernel is bound by load latency, not by
 // bytes per load instruction); CGb = lanes per position (power of two >= Cp / CH)
 // NA = temporal taps handled by one thread: 1 (one tap per blockIdx.z: x and dy stream from HBM once per tap) or 3 (all three in
 // one pass: a third of the HBM traffic, three times the accumulators)
-template <typename T, int SW, int WT, int CH, int NA>
+template <typename T, int SW, int WT, int NA>
 __global__ __launch_bounds__(256) void dw_wgrad_strip_kernel(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ partial,
                                                              pasn_conv_desc d, int CG, int CGb, int strips, int HR, int hgroups, long items) {
+    constexpr int CH = 4;
     __shared__ float red[256 * CH];
     constexpr int IW = (WT - 1) * SW + 3;
     const int cg = threadIdx.x % CGb, pl = threadIdx.x / CGb, PL = 256 / CGb;
@@ -288,7 +264,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_strip_kernel(const T* __restrict
                 for (int j = 0; j < WT; ++j) {
                     const int wo = wo0 + j;
                     const bool ok = wo < d.Wo;
-                    loadc<CH>(gp + ((size_t)ho * d.Wo + (ok ? wo : 0)) * d.Cout_p, g[j]);
+                    load4(gp + ((size_t)ho * d.Wo + (ok ? wo : 0)) * d.Cout_p, g[j]);
                     gok |= (ok ? 1u : 0u) << j;
                 }
 #pragma unroll
@@ -308,7 +284,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_strip_kernel(const T* __restrict
                     for (int i = 0; i < IW; ++i) {
                         const int wi = wi0 + i;
                         const bool ok = hok && wi >= 0 && wi < d.Wi;
-                        loadc<CH>(xp + ((size_t)(hok ? hi : 0) * d.Wi + (ok ? wi : 0)) * d.Cin_p, xr[dh][i]);
+                        load4(xp + ((size_t)(hok ? hi : 0) * d.Wi + (ok ? wi : 0)) * d.Cin_p, xr[dh][i]);
                         xok |= (ok ? 1u : 0u) << (dh * IW + i);
                     }
                 }
@@ -341,23 +317,30 @@ __global__ __launch_bounds__(256) void dw_wgrad_strip_kernel(const T* __restrict
         }
     }
     const int taps = d.kt * 9;
-    float* out = partial + ((size_t)blockIdx.x * taps + (size_t)(NA == 1 ? blockIdx.z : 0) * 9) * d.Cout_p;
-#pragma unroll
-    for (int p = 0; p < NA * 9; ++p) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < CH; ++j) red[threadIdx.x * CH + j] = acc[p][j];
-        __syncthreads();
-        for (int t = threadIdx.x; t < CGb * CH; t += 256) {
-            const int g2 = t / CH, j = t % CH;
-            if (g2 < CG) {
-                float s = 0.0f;
-                for (int q2 = 0; q2 < PL; ++q2) s += red[(q2 * CGb + g2) * CH + j];
-                out[(size_t)p * d.Cout_p + g2 * CH + j] = s;
-            }
-        }
-    }
+    block_reduce_rows(acc, red, partial + ((size_t)blockIdx.x * taps + (size_t)(NA == 1 ? blockIdx.z : 0) * 9) * d.Cout_p, d.Cout_p, CG, CGb);
 }
+
+// ---- the core of the two T-marching kernels below: E = float, or f32x2 (packed FMAs) --------------------------------------------------
+// Input row dh of frame ti (IW positions, converted) against the three-frame gradient ring -> the tap planes (a, dh, 0 .. 2) of acc.
+// Temporal tap a pairs input frame ti with output frame ti - a + 1: a = 0 -> g2, 1 -> g1, 2 -> g0.
+template <int SW, int WT, int IW, int N, typename E>
+__device__ __forceinline__ void march_row_fma(E (&acc)[27][N], const E (&xr)[IW][N], const E (&g0)[WT][N], const E (&g1)[WT][N],
+                                              const E (&g2)[WT][N], int dh) {
+    static_assert(IW == (WT - 1) * SW + 3, "a strip of WT outputs reads (WT - 1) * SW + 3 input columns");
+#pragma unroll
+    for (int dw_ = 0; dw_ < 3; ++dw_)
+#pragma unroll
+        for (int j = 0; j < WT; ++j)
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                const E xv = xr[j * SW + dw_][e];
+                acc[0 * 9 + dh * 3 + dw_][e] = __builtin_elementwise_fma(g2[j][e], xv, acc[0 * 9 + dh * 3 + dw_][e]);
+                acc[1 * 9 + dh * 3 + dw_][e] = __builtin_elementwise_fma(g1[j][e], xv, acc[1 * 9 + dh * 3 + dw_][e]);
+                acc[2 * 9 + dh * 3 + dw_][e] = __builtin_elementwise_fma(g0[j][e], xv, acc[2 * 9 + dh * 3 + dw_][e]);
+            }
+}
+// (The ring shift g0 <- g1 <- g2 after it stays a loop in each kernel: behind a helper, over the whole ring or one strip column per call,
+// the second marching kernel is scheduled differently -- 2-6 more VGPRs, or the same count and 0.4 % slower at 108 channels, 28 x 28.)
 
 // ---- depthwise 3x3x3 weight gradient, T-marching form (stride (1,s,s), pad 1) -------------------------------------------------------
 // The strip kernel above runs one temporal tap per blockIdx.z: every (frame, row) of x and dy is loaded and converted three times, 18
@@ -414,7 +397,7 @@ __global__ __launch_bounds__(256, 2) void dw_wgrad_march_kernel(const __bf16* __
         float g0[WT][CH], g1[WT][CH], g2[WT][CH];  // gradients of output frames ti-1, ti, ti+1
 #pragma unroll
         for (int j = 0; j < WT; ++j) {
-            loadc<CH>(gp + goff[j], g1[j]);
+            load4(gp + goff[j], g1[j]);
 #pragma unroll
             for (int e = 0; e < CH; ++e) {
                 g0[j][e] = 0.0f;
@@ -432,7 +415,7 @@ __global__ __launch_bounds__(256, 2) void dw_wgrad_march_kernel(const __bf16* __
                 for (int i = 0; i < IW; ++i) raw[dh][i] = *reinterpret_cast<const uint2*>(xp + (size_t)ti * xframe + xoff[dh][i]);
             const bool next = ti + 1 < d.To;
 #pragma unroll
-            for (int j = 0; j < WT; ++j) loadc<CH>(gp + (size_t)(next ? ti + 1 : ti) * gframe + goff[j], g2[j]);
+            for (int j = 0; j < WT; ++j) load4(gp + (size_t)(next ? ti + 1 : ti) * gframe + goff[j], g2[j]);
 #pragma unroll
             for (int j = 0; j < WT; ++j)
 #pragma unroll
@@ -451,17 +434,7 @@ __global__ __launch_bounds__(256, 2) void dw_wgrad_march_kernel(const __bf16* __
                     xr[i][2] = __uint_as_float(hi << 16);
                     xr[i][3] = __uint_as_float(hi & 0xffff0000u);
                 }
-#pragma unroll
-                for (int dw_ = 0; dw_ < 3; ++dw_)
-#pragma unroll
-                    for (int j = 0; j < WT; ++j)
-#pragma unroll
-                        for (int e = 0; e < CH; ++e) {
-                            const float xv = xr[j * SW + dw_][e];
-                            acc[0 * 9 + dh * 3 + dw_][e] = fmaf(g2[j][e], xv, acc[0 * 9 + dh * 3 + dw_][e]);
-                            acc[1 * 9 + dh * 3 + dw_][e] = fmaf(g1[j][e], xv, acc[1 * 9 + dh * 3 + dw_][e]);
-                            acc[2 * 9 + dh * 3 + dw_][e] = fmaf(g0[j][e], xv, acc[2 * 9 + dh * 3 + dw_][e]);
-                        }
+                march_row_fma<SW>(acc, xr, g0, g1, g2, dh);
             }
 #pragma unroll
             for (int j = 0; j < WT; ++j)
@@ -472,22 +445,7 @@ __global__ __launch_bounds__(256, 2) void dw_wgrad_march_kernel(const __bf16* __
                 }
         }
     }
-    float* out = partial + (size_t)blockIdx.x * 27 * d.Cout_p;
-#pragma unroll
-    for (int p = 0; p < 27; ++p) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < CH; ++j) red[threadIdx.x * CH + j] = acc[p][j];
-        __syncthreads();
-        for (int t = threadIdx.x; t < CGb * CH; t += 256) {
-            const int g2i = t / CH, j = t % CH;
-            if (g2i < CG) {
-                float s = 0.0f;
-                for (int q2 = 0; q2 < PL; ++q2) s += red[(q2 * CGb + g2i) * CH + j];
-                out[(size_t)p * d.Cout_p + g2i * CH + j] = s;
-            }
-        }
-    }
+    block_reduce_rows(acc, red, partial + (size_t)blockIdx.x * 27 * d.Cout_p, d.Cout_p, CG, CGb);
 }
 
 // ---- T-marching form, second cut (round 4) --------------------------------------------------------------------------------------------
@@ -589,18 +547,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_march2_kernel(const __bf16* __re
             }
             // temporal tap a pairs input frame ti with output frame ti - a + 1: a = 0 -> g2, 1 -> g1, 2 -> g0
 #pragma unroll
-            for (int dh = 0; dh < 3; ++dh)
-#pragma unroll
-                for (int dw_ = 0; dw_ < 3; ++dw_)
-#pragma unroll
-                    for (int j = 0; j < WT; ++j)
-#pragma unroll
-                        for (int c = 0; c < CW; ++c) {
-                            const f32x2 xvv = xc[dh][j * SW + dw_][c];
-                            acc[0 * 9 + dh * 3 + dw_][c] = __builtin_elementwise_fma(g2[j][c], xvv, acc[0 * 9 + dh * 3 + dw_][c]);
-                            acc[1 * 9 + dh * 3 + dw_][c] = __builtin_elementwise_fma(g1[j][c], xvv, acc[1 * 9 + dh * 3 + dw_][c]);
-                            acc[2 * 9 + dh * 3 + dw_][c] = __builtin_elementwise_fma(g0[j][c], xvv, acc[2 * 9 + dh * 3 + dw_][c]);
-                        }
+            for (int dh = 0; dh < 3; ++dh) march_row_fma<SW>(acc, xc[dh], g0, g1, g2, dh);
 #pragma unroll
             for (int j = 0; j < WT; ++j)
 #pragma unroll
@@ -610,23 +557,8 @@ __global__ __launch_bounds__(256) void dw_wgrad_march2_kernel(const __bf16* __re
                 }
         }
     }
-    float* out = partial + (size_t)blockIdx.x * 27 * Cp;
-#pragma unroll
-    for (int p = 0; p < 27; ++p) {
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            red[threadIdx.x * CH + 2 * c] = acc[p][c][0];
-            red[threadIdx.x * CH + 2 * c + 1] = acc[p][c][1];
-        }
-        __syncthreads();
-        for (int t = threadIdx.x; t < CG * CH; t += 256) {
-            const int g2i = t / CH, j = t % CH;
-            float s = 0.0f;
-            for (int q2 = 0; q2 < PL; ++q2) s += red[(q2 * CG + g2i) * CH + j];
-            out[(size_t)p * Cp + g2i * CH + j] = s;
-        }
-    }
+    // no padded lanes here (lanes per position = CG), so the reduce needs no lane guard
+    block_reduce_rows<27, CH, false>([&](int p, int j) { return acc[p][j / 2][j % 2]; }, red, partial + (size_t)blockIdx.x * 27 * Cp, Cp, CG, CG, PL);
 }
 
 // dw[c][tap] = sum_chunks partial[chunk][tap*Cp + c]: 64 columns x 4 parts per block, parts combined in a fixed order
@@ -682,24 +614,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_temporal_kernel(const T* __restr
             }
         }
     }
-    float* out = partial + (size_t)blockIdx.x * d.kt * d.Cout_p;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (k < d.kt) {
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = acc[k][j];
-            __syncthreads();
-            for (int t = threadIdx.x; t < CGb * 8; t += 256) {
-                const int g2 = t >> 3, j = t & 7;
-                if (g2 < CG) {
-                    float sum = 0.0f;
-                    for (int q2 = 0; q2 < PL; ++q2) sum += red[(q2 * CGb + g2) * 8 + j];
-                    out[(size_t)k * d.Cout_p + g2 * 8 + j] = sum;
-                }
-            }
-        }
-    }
+    block_reduce_rows(acc, red, partial + (size_t)blockIdx.x * d.kt * d.Cout_p, d.Cout_p, CG, CGb, d.kt);
 }
 
 static bool dw_temporal_ok(const pasn_conv_desc& d) {
@@ -822,50 +737,39 @@ extern "C" int pasn_dwconv3d_wgrad(const void* x, const void* dy, float* ws, flo
     hipStream_t s = (hipStream_t)stream;
     const DwWgRoute r = dw_wgrad_route(*d, dtype);
     const DwWgGeom& g = r.g;
-    const bool bf16 = dtype == PASN_BF16, na3 = d->kt == 3 && tune("PASN_DWWG_FUSED") && atoi(tune("PASN_DWWG_FUSED")) != 0;
+    const DwWgMarch2& m = r.m;
+    const bool na3 = d->kt == 3 && tune("PASN_DWWG_FUSED") && atoi(tune("PASN_DWWG_FUSED")) != 0;
     const int CG = d->Cout_p / 8, CGb = pow2_at_least(CG);  // TEMPORAL, GENERIC: 8 channels per thread
-    const dim3 one((unsigned)r.blocks), per_tap((unsigned)r.blocks, 1, d->kt), block(256);
-    const __bf16 *xb = (const __bf16*)x, *dyb = (const __bf16*)dy;
-    const float *xf = (const float*)x, *dyf = (const float*)dy;
-#define DWM2(SWv, WTv, CHv) hipLaunchKernelGGL((dw_wgrad_march2_kernel<SWv, WTv, CHv>), one, block, 0, s, xb, dyb, ws, *d, r.m.CG, r.m.PL, r.m.strips, r.m.items)
-#define DWM(SWv, WTv) hipLaunchKernelGGL((dw_wgrad_march_kernel<SWv, WTv>), one, block, 0, s, xb, dyb, ws, *d, g.CG, g.CGb, g.strips, (long)d->N * d->Ho * g.strips)
-#define DWS(T, X, DY, SWv, WTv, NA) \
-    hipLaunchKernelGGL((dw_wgrad_strip_kernel<T, SWv, WTv, 4, NA>), NA == 3 ? one : per_tap, block, 0, s, X, DY, ws, *d, g.CG, g.CGb, g.strips, g.HR, g.hgroups, g.items)
-#define DWS_NA(T, X, DY, SWv, WTv)           \
-    if (na3) DWS(T, X, DY, SWv, WTv, 3); \
-    else DWS(T, X, DY, SWv, WTv, 1)
+    const dim3 one((unsigned)r.blocks), per_tap((unsigned)r.blocks, 1, d->kt);
+    const __bf16 *xb = (const __bf16*)x, *dyb = (const __bf16*)dy;  // the marching kernels are bf16 only
+    auto march2 = [&](auto kernel) { launch256(kernel, one, 0, s, xb, dyb, ws, *d, m.CG, m.PL, m.strips, m.items); };
+    auto march = [&](auto kernel) { launch256(kernel, one, 0, s, xb, dyb, ws, *d, g.CG, g.CGb, g.strips, (long)d->N * d->Ho * g.strips); };
     switch (r.arm) {
-        case DwWgRoute::TEMPORAL:
-            if (bf16) hipLaunchKernelGGL(dw_wgrad_temporal_kernel<__bf16>, one, block, 0, s, xb, dyb, ws, *d, CG, CGb, (long)d->N * d->Hi * d->Wi);
-            else hipLaunchKernelGGL(dw_wgrad_temporal_kernel<float>, one, block, 0, s, xf, dyf, ws, *d, CG, CGb, (long)d->N * d->Hi * d->Wi);
-            break;
         case DwWgRoute::MARCH2:
-            if (r.m.SW == 2 && r.m.CH == 2) DWM2(2, 2, 2);
-            else if (r.m.SW == 2) DWM2(2, 2, 4);
-            else if (r.m.WT == 3 && r.m.CH == 2) DWM2(1, 3, 2);
-            else if (r.m.WT == 3) DWM2(1, 3, 4);
-            else if (r.m.CH == 2) DWM2(1, 2, 2);
-            else DWM2(1, 2, 4);
+            switch (m.SW * 100 + m.WT * 10 + m.CH) {
+                case 222: march2(dw_wgrad_march2_kernel<2, 2, 2>); break;
+                case 224: march2(dw_wgrad_march2_kernel<2, 2, 4>); break;
+                case 132: march2(dw_wgrad_march2_kernel<1, 3, 2>); break;
+                case 134: march2(dw_wgrad_march2_kernel<1, 3, 4>); break;
+                case 122: march2(dw_wgrad_march2_kernel<1, 2, 2>); break;
+                default: march2(dw_wgrad_march2_kernel<1, 2, 4>); break;
+            }
             break;
         case DwWgRoute::MARCH:
-            if (g.SW == 1) DWM(1, 3);
-            else DWM(2, 2);
+            if (g.SW == 1) march(dw_wgrad_march_kernel<1, 3>);
+            else march(dw_wgrad_march_kernel<2, 2>);
             break;
-        case DwWgRoute::STRIP:
-            if (bf16 && g.SW == 1) { DWS_NA(__bf16, xb, dyb, 1, 3); }
-            else if (bf16) { DWS_NA(__bf16, xb, dyb, 2, 2); }
-            else if (g.SW == 1) { DWS_NA(float, xf, dyf, 1, 3); }
-            else { DWS_NA(float, xf, dyf, 2, 2); }
-            break;
-        case DwWgRoute::GENERIC:
-            if (bf16) hipLaunchKernelGGL(dw_wgrad_partial_kernel<__bf16>, per_tap, block, 0, s, xb, dyb, ws, *d, CG, CGb, r.rpc);
-            else hipLaunchKernelGGL(dw_wgrad_partial_kernel<float>, per_tap, block, 0, s, xf, dyf, ws, *d, CG, CGb, r.rpc);
-            break;
+        default:
+            with_dtype(dtype, [&](auto tag) {
+                using T = elem_t<decltype(tag)>;
+                const T *xt = (const T*)x, *dyt = (const T*)dy;
+                auto strip = [&](auto fused, auto tap) { launch256(na3 ? fused : tap, na3 ? one : per_tap, 0, s, xt, dyt, ws, *d, g.CG, g.CGb, g.strips, g.HR, g.hgroups, g.items); };
+                if (r.arm == DwWgRoute::TEMPORAL) launch256(dw_wgrad_temporal_kernel<T>, one, 0, s, xt, dyt, ws, *d, CG, CGb, (long)d->N * d->Hi * d->Wi);
+                else if (r.arm == DwWgRoute::GENERIC) launch256(dw_wgrad_partial_kernel<T>, per_tap, 0, s, xt, dyt, ws, *d, CG, CGb, r.rpc);
+                else if (g.SW == 1) strip(dw_wgrad_strip_kernel<T, 1, 3, 3>, dw_wgrad_strip_kernel<T, 1, 3, 1>);
+                else strip(dw_wgrad_strip_kernel<T, 2, 2, 3>, dw_wgrad_strip_kernel<T, 2, 2, 1>);
+            });
     }
-#undef DWS_NA
-#undef DWS
-#undef DWM
-#undef DWM2
-    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(ceil_div((long)r.taps * d->Cout_p, 64)), block, 0, s, ws, dw, (int)r.blocks, r.taps, d->Cout, d->Cout_p);
+    launch256(dw_wgrad_reduce_kernel, dim3(ceil_div((long)r.taps * d->Cout_p, 64)), 0, s, ws, dw, (int)r.blocks, r.taps, d->Cout, d->Cout_p);
     return check_launch("dwconv3d_wgrad");
 }

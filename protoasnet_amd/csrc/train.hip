@@ -6,6 +6,7 @@
 // Reference semantics: torch.nn.BatchNorm{2,3}d in train mode (biased batch variance for normalisation, unbiased for
 // the running estimate, momentum 0.1) as instantiated at resnet_features.py:140,180 and by every trunk the reference
 // trains (agents call model.train(): Video_XProtoNet_e2e.py:118); autograd's derivative of the same expressions.
+#include "block_reduce.h"
 #include "common.h"
 
 namespace pasn {
@@ -23,9 +24,7 @@ struct RowGeom {
 static RowGeom row_geom(int N, int S, int Cp) {
     RowGeom g;
     g.CG = Cp / 8;
-    g.LPR = 1;
-    while (g.LPR < g.CG) g.LPR <<= 1;
-    if (tune_is("PASN_TRAIN_ROWS_CONTIG", '1')) g.LPR = g.CG;
+    g.LPR = tune_is("PASN_TRAIN_ROWS_CONTIG", '1') ? g.CG : pow2_at_least(g.CG);
     g.RL = 256 / g.LPR;
     int blocks = 1024;
     if (const char* e = tune("PASN_TRAIN_BLOCKS")) blocks = std::max(256, atoi(e));
@@ -79,28 +78,6 @@ __device__ __forceinline__ void store8(__amdgpu_buffer_rsrc_t rs, unsigned off, 
 __device__ __forceinline__ void store8(__amdgpu_buffer_rsrc_t rs, unsigned off, const float (&v)[8], const float*) {
     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, rs, (int)off, 0, 0);
     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, rs, (int)off + 16, 0, 0);
-}
-
-// Sum the per-thread 8-channel accumulators `acc[W][8]` over the row lanes of the block (fixed order) and store them
-// at out[w * Cp + cg*8 + j].
-template <int W>
-__device__ __forceinline__ void block_reduce_rows(float (&acc)[W][8], float* red, float* out, int Cp, int CG, int LPR) {
-    const int tid = threadIdx.x, RL = 256 / LPR;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[w][j];
-        __syncthreads();
-        for (int t = tid; t < LPR * 8; t += 256) {
-            const int cg = t >> 3, j = t & 7;
-            if (cg < CG) {
-                float s = 0.0f;
-                for (int rl = 0; rl < RL; ++rl) s += red[(rl * LPR + cg) * 8 + j];
-                out[(size_t)w * Cp + cg * 8 + j] = s;
-            }
-        }
-    }
 }
 
 // ---- batch statistics ---------------------------------------------------------------------------------------------

@@ -401,9 +401,16 @@ def test_first_conv_wgrad(in_dtype):
         _rel(dw.view_as(wt2), wt2.grad, 2e-3 if in_dtype == torch.float32 else 1e-4, "dW (bf16 dy)")
 
 
-@pytest.mark.parametrize("c,k,s,p,shape", [(54, (3, 3, 3), (1, 1, 1), (1, 1, 1), (2, 3, 6, 7)), (54, (3, 3, 3), (1, 2, 2), (1, 1, 1), (2, 3, 9, 8)),
-                                           (24, (5, 1, 1), (1, 1, 1), (2, 0, 0), (2, 6, 4, 5)), (432, (3, 3, 3), (1, 2, 2), (1, 1, 1), (1, 2, 5, 5))])
-def test_depthwise_dgrad_wgrad(c, k, s, p, shape):
+DW_DGRAD_CASES = [(54, (3, 3, 3), (1, 1, 1), (1, 1, 1), (2, 3, 6, 7)), (54, (3, 3, 3), (1, 2, 2), (1, 1, 1), (2, 3, 9, 8)),
+                  (24, (5, 1, 1), (1, 1, 1), (2, 0, 0), (2, 6, 4, 5)), (432, (3, 3, 3), (1, 2, 2), (1, 1, 1), (1, 2, 5, 5))]
+
+
+# the fp32 run carries the bare id of its case; bf16 (what training runs) is the dtype of the dgrad half only
+@pytest.mark.parametrize("c,k,s,p,shape,dtype", [pytest.param(*case, dtype, id=f"{case[0]}-k{i}-s{i}-p{i}-shape{i}" + ("-bf16" if dtype == BF else ""))
+                                                 for i, case in enumerate(DW_DGRAD_CASES) for dtype in (FP32, BF)])
+def test_depthwise_dgrad_wgrad(c, k, s, p, shape, dtype):
+    """dx in fp32 and bf16 (dw_dgrad_kernel, dw_dgrad_s2_kernel), dW in fp32, against autograd.  bf16: dy is rounded before the reference is
+    taken, and dx is one fp32 accumulation of at most 27 products behind one bf16 store (tk.tol_stores)."""
     lib = _lib.lib()
     n, t, h, w = shape
     g = torch.Generator().manual_seed(c + k[0])
@@ -411,15 +418,17 @@ def test_depthwise_dgrad_wgrad(c, k, s, p, shape):
     wt = torch.randn(c, 1, *k, generator=g).requires_grad_()
     y = F.conv3d(x, wt, stride=s, padding=p, groups=c)
     dy = torch.randn(y.shape, generator=g)
+    dyr = dy.to(dtype).float()
+    (dx_ref,) = torch.autograd.grad(y, x, dyr, retain_graph=True)
     y.backward(dy)
     d = _desc(x, y, k, s, p)
     taps, cp = k[0] * k[1] * k[2], d.Cout_p
     wp = torch.zeros(taps, cp, device=DEV)
     wp[:, :c] = wt.detach().reshape(c, taps).t().to(DEV)
-    xd, dyd = _cl(x.detach()), _cl(dy)
-    dx = torch.empty_like(xd)
-    _lib.check(lib.pasn_dwconv3d_dgrad(dyd.data_ptr(), wp.data_ptr(), dx.data_ptr(), ctypes.byref(d), F32, _st()))
-    _rel(_ncl(dx, c), x.grad, 1e-5, "dx")
+    xd, dyd, dyt = _cl(x.detach()), _cl(dy), _cl(dyr, dtype=dtype)
+    dx = torch.empty_like(xd, dtype=dtype)
+    _lib.check(lib.pasn_dwconv3d_dgrad(dyt.data_ptr(), wp.data_ptr(), dx.data_ptr(), ctypes.byref(d), _lib.dtype_code(dtype), _st()))
+    _rel(_ncl(dx, c), dx_ref, tk.tol_stores(1e-5, 1, dtype), "dx")
     ws = torch.zeros(lib.pasn_dwconv3d_wgrad_workspace_floats(ctypes.byref(d)), device=DEV)
     dw = torch.zeros(c, taps, device=DEV)
     _lib.check(lib.pasn_dwconv3d_wgrad(xd.data_ptr(), dyd.data_ptr(), ws.data_ptr(), dw.data_ptr(), ctypes.byref(d), F32, _st()))
@@ -715,7 +724,11 @@ def test_depthwise_wgrad_march_bf16(c, s, shape, monkeypatch):
 
 _S1, _S2 = ((3, 3, 3), 1, (1, 3, 9, 10)), ((3, 3, 3), 2, (1, 3, 12, 14))
 _MARCH1, _NO_MARCH, _NO_STRIP = {"PASN_DWWG_MARCH2": "0"}, {"PASN_NO_DWWG_MARCH": "1"}, {"PASN_NO_DWWG_STRIP": "1"}
-# (arm of pasn_dwconv3d_wgrad's ladder, dtype, (window, spatial stride, (n, t, h, w)), switches): every arm once, 24 channels, ragged strips
+_FUSED, _FUSED_NO_MARCH = {"PASN_DWWG_FUSED": "1"}, {"PASN_DWWG_FUSED": "1", "PASN_NO_DWWG_MARCH": "1"}
+# (arm of pasn_dwconv3d_wgrad's ladder, dtype, (window, spatial stride, (n, t, h, w)), switches): every arm once, 24 channels (6 lanes of 4
+# padded to 8), ragged strips (widths 10 and 7 at 3 and 2 outputs per strip), T = 3 (both temporal borders and an interior frame).
+# strip-fused: the four strip instances with all three temporal taps in one pass; generic-313: neither the temporal nor the strip arm takes
+# a (3,1,3) window, so the row-partial kernel runs with 3 of its 9 spatial taps live.
 DW_WGRAD_ARMS = [
     ("temporal", FP32, ((3, 1, 1), 1, (1, 4, 5, 6)), {}), ("temporal", BF, ((3, 1, 1), 1, (1, 4, 5, 6)), {}),
     ("march2", BF, _S1, {}), ("march2", BF, _S2, {}), ("march2-ch2-wt3", BF, _S1, {"PASN_DWWG_CH": "2", "PASN_DWWG_WT": "3"}),
@@ -723,6 +736,8 @@ DW_WGRAD_ARMS = [
     ("strip", FP32, _S1, {}), ("strip", FP32, _S2, {}), ("strip", BF, _S1, _NO_MARCH), ("strip", BF, _S2, _NO_MARCH),
     ("strip-133", FP32, ((1, 3, 3), 1, (1, 2, 9, 10)), {}),
     ("generic", FP32, _S1, _NO_STRIP), ("generic", BF, _S1, _NO_STRIP),
+    ("strip-fused", FP32, _S1, _FUSED), ("strip-fused", FP32, _S2, _FUSED), ("strip-fused", BF, _S1, _FUSED_NO_MARCH), ("strip-fused", BF, _S2, _FUSED_NO_MARCH),
+    ("generic-313", FP32, ((3, 1, 3), 1, (1, 3, 5, 6)), {}),
 ]
 
 
