@@ -763,6 +763,64 @@ int pasn_bootstrap_metrics(const float* probs, const int32_t* labels, const floa
                            const int32_t* group_rows, long M, long G, int K_real, int B, uint64_t seed, double* stats, int64_t* cm,
                            int64_t* u2, int64_t* n_pos, int64_t* n_neg, void* workspace, void* stream);
 
+/* Calibration (calibration.py): are the numbers probabilities?  Reliability bins and the statistics read from them, for the sample and
+ * for grouped-bootstrap replicates of it, and temperature scaling.  The reference has no code for it; these definitions are the
+ * specification.  Every call is stream-ordered: no host synchronisation.
+ *
+ * Rows.  probs [M][K_real] fp32, labels [M] int32.  A row is valid when 0 <= label < K_real; every other row is padding and never
+ * enters.  A row's prediction is its first largest probability.
+ * Weights.  Output row r = B is the point estimate: w_i = 1.  Output row b < B is replicate b: w_i = counts[b][unit_i], with
+ * unit_i = row_unit[i] (int32 [M]), or unit_i = i and G == M for row_unit == NULL.  A row whose unit is not in [0, G) (-1: no group
+ * lists it) never enters, the point estimate included, as in pasn_bootstrap_metrics.  counts [B][G] int32 holds the resamples exactly as
+ * pasn_bootstrap_counts defines them; this call reads them, it does not draw.  NULL exactly when B == 0.
+ * Confidence and bin.  c_i = conf[i] when conf [M] fp32 is given, else the row's largest probability.  A valid row with c NaN, c < 0 or
+ * c > 1 is not binned: it is counted, weighted, in skipped[r].  Bin j = min(n_bins - 1, (int)((double)c * n_bins)): intervals [lo, hi),
+ * c = 1 in the last bin.  q_i = (uint64)((double)c * 4294967296.0); every sum below is an integer sum, exact and independent of order.
+ * The expanded rows of a replicate number less than 2^31 (as for the bootstrap), so qsum stays below 2^63.
+ *   n, hit [B + 1][n_bins] int64     sum w, sum w [pred == label];   qsum [B + 1][n_bins] uint64   sum w q
+ *   cn, cpos [B + 1][K_real][n_bins] int64, cq uint64: the same per class k with the confidence probs[i][k] (never `conf`) and the
+ *                                    positives label == k; a probability outside [0, 1] is not binned (NaN: unspecified)
+ *   skipped [B + 1] int64
+ *   stats [B + 1][6] fp64, with conf_j = (double)qsum_j * 0x1p-32, W = sum_j n_j and Wv = W + skipped (the weight of all valid rows):
+ *     ece      sum_j |hit_j - conf_j| / W, j ascending
+ *     mce      the largest |hit_j - conf_j| / n_j over the bins with n_j > 0
+ *     cw_ece   (1 / K_real) sum_k sum_j |cpos_kj - cconf_kj| / Wv
+ *     brier    sum_i w_i sum_k (p_ik - [label_i == k])^2 / Wv, every term fp64
+ *     nll      -sum_i w_i log(max(p_i,label, FLT_MIN)) / Wv, fp64 log
+ *     conf_gap sum_j (conf_j - hit_j) / W; positive: over-confident
+ *   W == 0 gives NaN for ece, mce and conf_gap, Wv == 0 for the other three.  The brier and nll sums run in a fixed order (each thread
+ *   its rows in order, the threads in a fixed tree): two calls are bitwise equal in every output.
+ * Two launches whatever B is: the row words shared by all replicates, then a block per output row (the blocks loop past 2048 rows), its
+ * histogram in LDS (64-bit integer LDS atomics).  Output row B is written last in memory order only: a caller that splits its replicates
+ * into chunks passes the chunk's counts and output pointers advanced by the chunk's first replicate, and the next chunk overwrites the
+ * point row this one left behind.  `workspace`: pasn_calibration_workspace_bytes(...) bytes, 16-byte aligned, no initialisation.
+ * 2 <= K_real <= 16, 1 <= M <= 2^20, 1 <= G <= M, 1 <= n_bins <= 64, 0 <= B <= 65 536; anything else, or a NULL required pointer,
+ * returns PASN_ERR_ARG before any launch (the size query returns 0).
+ *
+ * Temperature.  Over the valid rows, z = logits[.][0 .. K_real) widened to fp64 (logits [M][K] fp32, K_real <= K <= 17):
+ *   g(beta) = sum_i [logsumexp_k(beta z_ik) - beta z_i,label],  beta = 1 / T in [1/64, 64]
+ * g is convex: g' = sum_i (E_beta[z_i] - z_i,label), g'' = sum_i Var_beta[z_i] >= 0.  fit [4] fp64 = {beta, g(1) / Mv, g(beta) / Mv, status}:
+ *   status 3  no valid row: beta = 1 (both means NaN)
+ *   status 1  g'(1/64) >= 0 (this includes rows that are all flat): beta = 1/64
+ *   status 2  g'(64) <= 0 (separable data): beta = 64
+ *   status 0  otherwise: the root of g', by safeguarded Newton from beta = 1 in PASN_TEMPERATURE_STEPS steps whatever the data: a step
+ *             evaluates (g', g'') at beta, shrinks the bracket by the sign of g' (g' == 0 closes it) and takes the Newton point where it
+ *             lies strictly inside the bracket and g'' > 0, else the midpoint.
+ * Per-row terms are fp64; the rows of a block are added in a fixed tree, the blocks' partials in index order: two calls are bitwise
+ * equal.  3 + PASN_TEMPERATURE_STEPS + 1 launches; the iteration crosses launch boundaries and no block ever waits for another.
+ * `workspace`: pasn_temperature_workspace_bytes(M, K_real) bytes, 16-byte aligned, no initialisation.
+ *
+ * pasn_temperature_probs: probs [M][K_real] fp32, p_k = exp(beta (z_k - z_max)) / sum_k exp(beta (z_k - z_max)) in fp64, rounded once to
+ * fp32; u [M] fp32 (or NULL) = 1.0f - the row's largest p, bitwise.  beta [1] fp64 is DEVICE memory (fit, or the caller's 1 / T). */
+#define PASN_TEMPERATURE_STEPS 48
+size_t pasn_calibration_workspace_bytes(long M, long G, int K_real, int n_bins, int B);
+int pasn_calibration_bins(const float* probs, const int32_t* labels, const float* conf, const int32_t* row_unit, const int32_t* counts,
+                          long M, long G, int K_real, int n_bins, int B, int64_t* n, int64_t* hit, uint64_t* qsum, int64_t* cn,
+                          int64_t* cpos, uint64_t* cq, int64_t* skipped, double* stats, void* workspace, void* stream);
+size_t pasn_temperature_workspace_bytes(long M, int K_real);
+int pasn_temperature_fit(const float* logits, const int32_t* labels, long M, int K, int K_real, double* fit, void* workspace, void* stream);
+int pasn_temperature_probs(const float* logits, long M, int K, int K_real, const double* beta, float* probs, float* u, void* stream);
+
 /* Global explanations: the k nearest clips of a split per prototype, kept on the device while a loader is swept (global_explain.py).
  * The reference ships only the raw material, the whole (clips, P) similarity matrix "for ranking prototypes"
  * (XProtoNet_Base.py:613-656 get_sim_scores / load_sim_scores; explain_global is a stub); the selection rule per batch is the push's

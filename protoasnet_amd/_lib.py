@@ -170,6 +170,12 @@ SIGNATURES = {
     "pasn_bootstrap_counts": (c_int, [c_void_p, c_long, c_int, c_uint64, c_int, c_void_p]),
     "pasn_bootstrap_workspace_bytes": (c_size_t, [c_long, c_long, c_int, c_int]),
     "pasn_bootstrap_metrics": (c_int, [c_void_p] * 5 + [c_long, c_long, c_int, c_int, c_uint64] + [c_void_p] * 7),
+    # ---- calibration: reliability bins and temperature scaling (calibration.py)
+    "pasn_calibration_workspace_bytes": (c_size_t, [c_long, c_long, c_int, c_int, c_int]),
+    "pasn_calibration_bins": (c_int, [c_void_p] * 5 + [c_long, c_long, c_int, c_int, c_int] + [c_void_p] * 10),
+    "pasn_temperature_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "pasn_temperature_fit": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "pasn_temperature_probs": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     # ---- the training loss recipe (losses.FusedCriterion)
     "pasn_proto_loss_fwd": (c_int, [c_void_p] * 13 + [POINTER(ProtoLossDesc), c_void_p]),
     "pasn_proto_loss_bwd": (c_int, [c_void_p] * 14 + [POINTER(ProtoLossDesc), c_void_p]),

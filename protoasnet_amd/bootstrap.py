@@ -124,15 +124,16 @@ def check_confidence(confidence) -> float:
     return c
 
 
-def intervals_of(stats, confidence: float = 0.95) -> Dict[str, Dict[str, float]]:
-    """``intervals`` on a host array / tensor ``(B + 1, 6)`` (row B the point estimate): no device work."""
+def intervals_of(stats, confidence: float = 0.95, names=STAT_NAMES) -> Dict[str, Dict[str, float]]:
+    """``intervals`` on a host array / tensor ``(B + 1, 6)`` (row B the point estimate): no device work.  ``names``: the columns' names
+    (``calibration.STAT_NAMES`` for the calibration statistics: the same arithmetic)."""
     c = check_confidence(confidence)
     s = np.asarray(stats, dtype=np.float64)
-    if s.ndim != 2 or s.shape[0] < 2 or s.shape[1] != len(STAT_NAMES):
-        raise ValueError(f"stats must be (B + 1, {len(STAT_NAMES)})")
+    if s.ndim != 2 or s.shape[0] < 2 or s.shape[1] != len(names):
+        raise ValueError(f"stats must be (B + 1, {len(names)})")
     out = {}
     nan = float("nan")
-    for j, name in enumerate(STAT_NAMES):
+    for j, name in enumerate(names):
         v = s[:-1, j]
         v = v[np.isfinite(v)]
         lo, hi, se = nan, nan, nan

@@ -44,4 +44,15 @@ __device__ __forceinline__ void block_reduce_rows(const float (&acc)[W][CH], flo
     block_reduce_rows<W, CH, true>([&](int p, int j) { return acc[p][j]; }, red, out, Cp, CG, LPR, 256 / LPR, nlive);
 }
 
+// The sum of one fp64 value per thread of a 256-thread block, the same in every thread and in every run: a butterfly within each wave
+// (a + b == b + a, so every lane holds the same bits), then the four waves as (0 + 1) + (2 + 3) through red[4].  Two barriers: the first
+// frees red from whoever read it before, the second publishes it -- LDS traffic issued before the call is complete after it.
+__device__ __forceinline__ double block_sum_fixed(double v, double* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 }  // namespace pasn

@@ -13,7 +13,8 @@ definitions below ("Selective prediction"; ``include/protoasnet_
   prefixes (the area under the risk-coverage curve), ``error_auroc`` the AUROC of ``u`` as a detector of the wrong predictions.
 * ``SelectiveEvaluator``: an ``EpochEvaluator(keep_logits=True)`` fed batch by batch together with the clips' file names; ``finish`` gives
   the curve read at a few coverages, per clip or per cine, with ONE synchronising device-to-host copy; ``finish(bootstrap=B)`` adds
-  grouped-bootstrap confidence intervals (``bootstrap.py``) to the same read.
+  grouped-bootstrap confidence intervals (``bootstrap.py``) to the same read, ``finish(calibration=n_bins, temperature=...)`` reliability
+  bins, ECE and temperature-scaled probabilities (``calibration.py``).
 
 Everything runs on the device on the caller's stream; there is no CPU fallback.
 """
@@ -234,11 +235,19 @@ class SelectiveEvaluator:
         self.keys += keys
 
     def finish(self, coverages=DEFAULT_COVERAGES, level: str = "clip", bootstrap: int = 0, seed: int = 0, confidence: float = 0.95,
-               unit: str = "cine") -> Dict[str, object]:
+               unit: str = "cine", calibration: int = 0, temperature=None) -> Dict[str, object]:
         """``bootstrap=B > 0`` adds ``res["ci"]``: ``bootstrap.intervals`` of ``B`` grouped replicates (``seed``, ``confidence``) of the
         rows the level scores -- at cine level the cine predictions, the unit the cine; at clip level the clips, the unit the cine
         (``build_groups`` of the keys) or, with ``unit="clip"``, the clip.  Still one synchronising read; ``bootstrap=0`` is the call
-        without it, launch for launch."""
+        without it, launch for launch.
+
+        ``temperature`` (a ``calibration.TemperatureFit`` or a float ``T > 0``): the class probabilities scored everywhere in the call
+        are ``calibration.scaled_probs`` of the kept logits, and the ``maxprob`` uncertainty follows them (it is 1 - the largest scored
+        probability by definition); the ``alpha`` modes keep reading the raw logits.  ``calibration=n_bins > 0`` adds
+        ``res["calibration"]``: ``calibration.reliability(...).summary()`` of the level's rows (the clips; at cine level ``p_conf`` with
+        the cine's label), and under ``["selective"]`` the same with ``conf = 1 - u`` -- is the uncertainty an honest probability of
+        error? -- (``ece``, ``mce``, ``conf_gap``, ``bins``); with ``bootstrap=B`` ``res["ci"]`` gains the six calibration statistics, from
+        the same seed and units and therefore the same resamples.  Still one read; the defaults are the call without either."""
         if level not in ("clip", "cine"):
             raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
         if unit not in ("clip", "cine"):
@@ -251,20 +260,42 @@ class SelectiveEvaluator:
 
             boot.check_confidence(confidence)
             boot._check_B_seed(bootstrap, seed)
+        if isinstance(calibration, bool) or not isinstance(calibration, (int, np.integer)) or calibration < 0:
+            raise ValueError(f"calibration must be a non-negative integer (the number of bins), got {calibration!r}")
+        cal = None
+        if calibration or temperature is not None:
+            from . import calibration as cal
+
+            if calibration:
+                cal.check_bins(calibration)
+            if temperature is not None:
+                cal._check_temperature(temperature)
+        n_bins = int(calibration)
         cs = _check_coverages(coverages)
         ev, K = self.ev, self.ev.K_real
         if ev.rows == 0:
             raise ValueError("no rows: call update() first")
         probs, labels = ev.probs[: ev.rows], ev.labels[: ev.rows]
-        u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
+        if temperature is None:
+            u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
+        elif score_mode(self.abstain, self.score, self.ab_logitpath) == MAXPROB:
+            probs, u = cal.scaled_probs(ev.logits[: ev.rows], K, temperature, with_u=True)
+        else:
+            probs = cal.scaled_probs(ev.logits[: ev.rows], K, temperature)
+            u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
         if level == "clip":
             packed = risk_coverage(probs, labels, u).packed(cs)
-            if boot is None:
+            if boot is None and not n_bins:
                 return self._result(RiskCoverage.unpack(packed.cpu(), cs))
-            rep = boot.replicates(probs, labels, u, build_groups(self.keys)[:2] if unit == "cine" else None, bootstrap, seed)
-            host = torch.cat([packed, rep.stats.flatten()]).cpu()  # the one read
+            groups = build_groups(self.keys)[:2] if bootstrap and unit == "cine" else None
+            parts = [packed]
+            if boot is not None:
+                parts.append(boot.replicates(probs, labels, u, groups, bootstrap, seed).stats.flatten())
+            if n_bins:
+                parts += self._calibration_parts(cal, probs, labels, u, groups, n_bins, bootstrap, seed)
+            host = torch.cat(parts).cpu()  # the one read
             res = self._result(RiskCoverage.unpack(host[: packed.numel()], cs))
-            res["ci"] = boot.intervals_of(host[packed.numel():].view(bootstrap + 1, 6).numpy(), confidence)
+            self._add_intervals(res, host[packed.numel():], boot, cal, n_bins, bootstrap, confidence)
             return res
         offsets, rows, names = build_groups(self.keys)
         G = len(names)
@@ -277,6 +308,8 @@ class SelectiveEvaluator:
         tail = [gp.status.double(), cm.double(), auc.reshape(1), auc_k, gp.p_conf.flatten(), gp.u_mean, gl.double(), gp.counts.double(), pred.double()]
         if boot is not None:  # the rows are the cine predictions: every row is its own unit
             tail.append(boot.replicates(p, gl, gp.u_mean.float(), None, bootstrap, seed).stats.flatten())
+        if n_bins:
+            tail += self._calibration_parts(cal, p, gl, gp.u_mean.float(), None, n_bins, bootstrap, seed)
         host = torch.cat([rc.packed(cs)] + tail).cpu()  # the one read
         n_rc = 5 * len(cs) + 4
         res = self._result(RiskCoverage.unpack(host[:n_rc], cs))
@@ -292,9 +325,30 @@ class SelectiveEvaluator:
         um, lab, cnt, prd = (t[o + G * K + j * G: o + G * K + (j + 1) * G] for j in range(4))
         res["cines"] = [{"filename": n, "target_AS": l, "n_clips": c, "probs": p, "uncertainty": x, "pred": d}
                         for n, l, c, p, x, d in zip(names, lab.long().tolist(), cnt.long().tolist(), pc, um.tolist(), prd.long().tolist())]
-        if boot is not None:
-            res["ci"] = boot.intervals_of(t[o + G * K + 4 * G:].view(bootstrap + 1, 6).numpy(), confidence)
+        self._add_intervals(res, t[o + G * K + 4 * G:], boot, cal, n_bins, bootstrap, confidence)
         return res
+
+    @staticmethod
+    def _calibration_parts(cal, probs, labels, u, groups, n_bins: int, B: int, seed: int) -> List[torch.Tensor]:
+        """The device vectors ``calibration=n_bins`` adds to the one read: the summary of the class probabilities, the summary of
+        ``1 - u`` as a claimed probability of being right, and with ``B`` replicates their statistics."""
+        rel = cal.reliability(probs, labels, n_bins, None, groups, B, seed)
+        parts = [rel.packed(), cal.reliability(probs, labels, n_bins, 1.0 - u).packed()]
+        return parts + [rel.stats.flatten()] if B else parts
+
+    @staticmethod
+    def _add_intervals(res, host, boot, cal, n_bins: int, B: int, confidence: float) -> None:
+        """``host``: what followed the level's own numbers in the read -- the bootstrap's replicates, then ``_calibration_parts``."""
+        if boot is not None:
+            res["ci"] = boot.intervals_of(host[: (B + 1) * 6].view(B + 1, 6).numpy(), confidence)
+            host = host[(B + 1) * 6:]
+        if n_bins:
+            w = 7 + 3 * n_bins
+            res["calibration"] = cal.Reliability.unpack(host[:w], n_bins)
+            sel = cal.Reliability.unpack(host[w: 2 * w], n_bins)
+            res["calibration"]["selective"] = {k: sel[k] for k in ("ece", "mce", "conf_gap", "bins")}
+            if boot is not None:
+                res["ci"].update(boot.intervals_of(host[2 * w:].view(B + 1, 6).numpy(), confidence, names=cal.STAT_NAMES))
 
     @staticmethod
     def _result(at: Dict[str, object]) -> Dict[str, object]:

@@ -93,6 +93,7 @@ class DPTrainer:
         self.local_accumulation = acc // world_size
         self.device = next(model.parameters()).device
         self.current_epoch, self.current_iteration, self.best_metric = 0, 0, 0.0
+        self.temperature_fit = None  # calibration.TemperatureFit of the last fit_temperature()
         self.num_real_classes = model.num_classes - 1 if config.get("abstain_class") else model.num_classes
         self.get_criterion()
         self.get_optimizer()
@@ -446,7 +447,8 @@ class DPTrainer:
         return self.run_epoch(self.current_epoch, mode)
 
     def evaluate_selective(self, mode: str = "test", level: str = "cine", coverages=(1.0, 0.9, 0.8, 0.7, 0.5), score: str = "auto",
-                           bootstrap: int = 0, seed: int = 0, confidence: float = 0.95, unit: str = "cine") -> Dict[str, object]:
+                           bootstrap: int = 0, seed: int = 0, confidence: float = 0.95, unit: str = "cine", calibration: int = 0,
+                           temperature=None) -> Dict[str, object]:
         """Selective-prediction metrics of ``data_loaders[mode]`` (``protoasnet_amd.selective``): an eval-mode, forward-only sweep (no
         loss; the ``staged`` / ``prepare_input`` path of ``run_epoch``), the clips grouped by ``sample["filename"]`` -- with
         ``iterate_intervals`` every cardiac cycle of a cine is a row of its own -- and ``SelectiveEvaluator.finish(coverages, level)``'s
@@ -455,11 +457,47 @@ class DPTrainer:
         probability; ``CeLossAbstain``'s ``ab_logitpath`` says how the abstention logit is read).  With ``save_dir`` set and
         ``level="cine"`` it writes ``save_dir/csv_<mode>_cine/e<epoch>.csv``: ``filename, target_AS, n_clips, prob_<label>...,
         uncertainty, pred``.  ``bootstrap=B > 0`` adds ``res["ci"]``: grouped-bootstrap confidence intervals of the level's rows
-        (``SelectiveEvaluator.finish``; ``protoasnet_amd.bootstrap``), each rank on its own loader's rows.
+        (``SelectiveEvaluator.finish``; ``protoasnet_amd.bootstrap``), each rank on its own loader's rows.  ``calibration=n_bins > 0``
+        adds ``res["calibration"]`` (``protoasnet_amd.calibration``: reliability bins, ECE, MCE, class-wise ECE, Brier, NLL, confidence
+        gap; with ``save_dir`` also ``save_dir/csv_<mode>_reliability/e<epoch>.csv``: ``bin, lo, hi, n, accuracy, confidence``), and
+        ``temperature`` -- a float ``T > 0``, a ``calibration.TemperatureFit`` or ``"fitted"``: what ``fit_temperature`` left in
+        ``self.temperature_fit`` -- rescales the class probabilities the call scores.
 
         It issues NO collectives: each rank that calls it sweeps the loader it was given and reports on those rows alone (call it on one
         rank with the full loader, or on every rank for per-shard figures; ranks need not call it together).  The model is left in the
         mode it was in; no training or epoch state is touched."""
+        if isinstance(temperature, str):
+            if temperature != "fitted":
+                raise ValueError(f"temperature must be a number, a TemperatureFit or 'fitted', got {temperature!r}")
+            if self.temperature_fit is None:
+                raise ValueError("temperature='fitted' needs fit_temperature() first")
+            temperature = self.temperature_fit
+        res = self._selective_sweep(mode, score).finish(coverages, level, bootstrap=bootstrap, seed=seed, confidence=confidence, unit=unit,
+                                                        calibration=calibration, temperature=temperature)
+        self.log(f"Epoch: {self.current_epoch} | {mode} | selective ({level}) | AURC {res['aurc']:.4f} | error AUROC {res['error_auroc']:.4f}")
+        if level == "cine" and self.config.get("save_dir"):
+            d = os.path.join(self.config["save_dir"], f"csv_{mode}_cine")
+            os.makedirs(d, exist_ok=True)
+            names = metrics_mod.logit_names(self.num_real_classes, False, self.config.get("class_labels"))
+            from . import selective
+
+            selective.write_cine_log(os.path.join(d, f"e{self.current_epoch:02d}.csv"), res["cines"], names)
+        if calibration and self.config.get("save_dir"):
+            import csv
+
+            d = os.path.join(self.config["save_dir"], f"csv_{mode}_reliability")
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, f"e{self.current_epoch:02d}.csv"), "w", newline="") as f:
+                w = csv.writer(f, lineterminator="\n")
+                w.writerow(["bin", "lo", "hi", "n", "accuracy", "confidence"])
+                for j, b in enumerate(res["calibration"]["bins"]):
+                    w.writerow([j, repr(b["lo"]), repr(b["hi"]), b["n"], repr(b["accuracy"]), repr(b["confidence"])])
+        return res
+
+    def _selective_sweep(self, mode: str, score: str = "auto"):
+        """The eval-mode, forward-only sweep of ``data_loaders[mode]`` behind ``evaluate_selective`` and ``fit_temperature``: a
+        ``SelectiveEvaluator`` holding every row's logits, probabilities, label and file name.  The model is left in the mode it was in;
+        no collectives, no training or epoch state."""
         from . import selective
         from .explain import _is_xproto
 
@@ -479,15 +517,24 @@ class DPTrainer:
                 for sample in self.staged(loader):
                     logit, similarities, _ = self.model(self.prepare_input(sample["cine"]))
                     sel.update(logit, similarities, sample["target_AS"].to(self.device, non_blocking=True), list(sample["filename"]))
-            res = sel.finish(coverages, level, bootstrap=bootstrap, seed=seed, confidence=confidence, unit=unit)
         finally:
             self.model.train(was_training)
-        self.log(f"Epoch: {self.current_epoch} | {mode} | selective ({level}) | AURC {res['aurc']:.4f} | error AUROC {res['error_auroc']:.4f}")
-        if level == "cine" and self.config.get("save_dir"):
-            d = os.path.join(self.config["save_dir"], f"csv_{mode}_cine")
-            os.makedirs(d, exist_ok=True)
-            names = metrics_mod.logit_names(self.num_real_classes, False, self.config.get("class_labels"))
-            selective.write_cine_log(os.path.join(d, f"e{self.current_epoch:02d}.csv"), res["cines"], names)
+        return sel
+
+    def fit_temperature(self, mode: str = "val") -> Dict[str, object]:
+        """Temperature scaling fitted on the clips of ``data_loaders[mode]`` (``calibration.fit_temperature``; the sweep of
+        ``evaluate_selective``): keeps the device result in ``self.temperature_fit`` -- ``evaluate_selective(temperature="fitted")``
+        applies it --, logs ``T`` and the NLL before and after, and returns ``{temperature, beta, nll_before, nll_after, status}``.  No
+        collectives; the model is left in the mode it was in; no training or epoch state is touched."""
+        from . import calibration
+
+        ev = self._selective_sweep(mode).ev
+        if ev.rows == 0:
+            raise ValueError("no rows: the loader is empty")
+        self.temperature_fit = calibration.fit_temperature(ev.logits[: ev.rows], ev.labels[: ev.rows], ev.K_real)
+        res = self.temperature_fit.read()
+        self.log(f"Epoch: {self.current_epoch} | {mode} | temperature {res['temperature']:.4f} ({res['status']}) | "
+                 f"NLL {res['nll_before']:.4f} -> {res['nll_after']:.4f}")
         return res
 
     def push(self, replace_prototypes: bool = True):
