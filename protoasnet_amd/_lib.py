@@ -234,6 +234,14 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def workspace(nbytes: int, device):
+    """Uninitialised device memory of at least ``nbytes`` bytes for a ``pasn_*_workspace_bytes`` size (fp64-backed: 8-byte elements on
+    the allocator's alignment)."""
+    import torch
+
+    return torch.empty(int(nbytes) // 8 + 1, dtype=torch.float64, device=device)
+
+
 def current_stream() -> int:
     import torch
 

@@ -24,10 +24,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .metrics import _f32, _require_cuda
+from .metrics import MAX_K, MAX_REPLICATES, MAX_ROWS, _f32, _require_cuda
+from .selective import check_groups
 
 STAT_NAMES = ("acc", "bal_acc", "f1_mean", "auc", "aurc", "error_auroc")  # the columns of ``stats``
-MAX_ROWS, MAX_REPLICATES, MAX_K = 1 << 20, 65536, 16
 
 
 def lds_max_groups() -> int:
@@ -35,9 +35,10 @@ def lds_max_groups() -> int:
     return int(_lib.lib().pasn_bootstrap_lds_max_groups())
 
 
-def _check_B_seed(B, seed) -> None:
-    if not isinstance(B, (int, np.integer)) or not 1 <= B <= MAX_REPLICATES:
-        raise ValueError(f"B must be an integer in [1, {MAX_REPLICATES}], got {B!r}")
+def _check_B_seed(B, seed, min_B: int = 1) -> None:
+    """``min_B=0``: ``calibration.reliability``, where no replicates is a call of its own."""
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not min_B <= B <= MAX_REPLICATES:
+        raise ValueError(f"B must be an integer in [{min_B}, {MAX_REPLICATES}], got {B!r}")
     if not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
         raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
 
@@ -89,19 +90,7 @@ def replicates(probs: torch.Tensor, labels: torch.Tensor, u: Optional[torch.Tens
     d_off = d_rows = None
     G = M
     if groups is not None:
-        offsets = np.ascontiguousarray(groups[0], dtype=np.int64)
-        rows = np.ascontiguousarray(groups[1], dtype=np.int32)
-        G = offsets.size - 1
-        if G < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
-            raise ValueError("group offsets must start at 0, not decrease and end at the number of listed rows")
-        if G > M:
-            raise ValueError(f"{G} groups for {M} rows")
-        if rows.size and (rows.min() < 0 or rows.max() >= M):  # these indices address device memory
-            raise ValueError(f"group rows must lie in [0, {M})")
-        if rows.size and np.bincount(rows, minlength=M).max() > 1:
-            raise ValueError("a row may be listed in one group only")
-        if G * int(np.diff(offsets).max()) >= 1 << 31:  # the expanded rows of a replicate are counted in 32 bits
-            raise ValueError("G times the largest group must stay below 2^31")
+        offsets, rows, G = check_groups(groups, M, exclusive=True)
         d_off, d_rows = torch.from_numpy(offsets).to(dev), torch.from_numpy(rows).to(dev)
     lib = _lib.lib()
     with torch.cuda.device(dev):
@@ -110,7 +99,7 @@ def replicates(probs: torch.Tensor, labels: torch.Tensor, u: Optional[torch.Tens
         stats = torch.empty(B + 1, 6, dtype=torch.float64, device=dev)
         cm = torch.empty(B + 1, K, K, dtype=torch.int64, device=dev)
         u2, n_pos, n_neg = (torch.empty(B + 1, K, dtype=torch.int64, device=dev) for _ in range(3))
-        ws = torch.empty(int(lib.pasn_bootstrap_workspace_bytes(M, G, K, B)) // 8 + 1, dtype=torch.float64, device=dev)
+        ws = _lib.workspace(lib.pasn_bootstrap_workspace_bytes(M, G, K, B), dev)
         _lib.check(lib.pasn_bootstrap_metrics(_lib.ptr(probs), _lib.ptr(labels), _lib.ptr(u), _lib.ptr(d_off), _lib.ptr(d_rows), M, G, K, int(B),
                                               int(seed), _lib.ptr(stats), _lib.ptr(cm), _lib.ptr(u2), _lib.ptr(n_pos), _lib.ptr(n_neg),
                                               _lib.ptr(ws), _lib.current_stream()))

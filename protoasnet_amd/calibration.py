@@ -25,11 +25,12 @@ import numpy as np
 import torch
 
 from . import _lib, bootstrap
-from .metrics import _f32, _require_cuda
+from .metrics import MAX_K, MAX_REPLICATES, MAX_ROWS, _f32, _require_cuda
+from .selective import check_groups
 
 STAT_NAMES = ("ece", "mce", "cw_ece", "brier", "nll", "conf_gap")  # the columns of ``stats``
 STATUS_NAMES = ("ok", "lower_bound", "upper_bound", "empty")  # fit[3]
-MAX_ROWS, MAX_REPLICATES, MAX_K, MAX_BINS = 1 << 20, 65536, 16, 64
+MAX_BINS = 64
 BETA_MIN, BETA_MAX = 1.0 / 64.0, 64.0
 CHUNK_BYTES = 64 << 20  # of bootstrap counts drawn at a time
 
@@ -74,7 +75,7 @@ def fit_temperature(logits: torch.Tensor, labels: torch.Tensor, num_real_classes
     lib = _lib.lib()
     with torch.cuda.device(logits.device):
         info = torch.empty(4, dtype=torch.float64, device=logits.device)
-        ws = torch.empty(int(lib.pasn_temperature_workspace_bytes(M, K_real)) // 8 + 1, dtype=torch.float64, device=logits.device)
+        ws = _lib.workspace(lib.pasn_temperature_workspace_bytes(M, K_real), logits.device)
         _lib.check(lib.pasn_temperature_fit(_lib.ptr(_f32(logits)), _lib.ptr(labels.to(torch.int32).contiguous()), M, K, K_real, _lib.ptr(info),
                                             _lib.ptr(ws), _lib.current_stream()))
     return TemperatureFit(info)
@@ -151,19 +152,7 @@ class Reliability:
 
 def _row_units(groups, M: int):
     """``(row_unit int32 (M,), G)`` of ``selective.build_groups``' tuple, with ``bootstrap.replicates``' checks."""
-    offsets = np.ascontiguousarray(groups[0], dtype=np.int64)
-    rows = np.ascontiguousarray(groups[1], dtype=np.int32)
-    G = offsets.size - 1
-    if G < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
-        raise ValueError("group offsets must start at 0, not decrease and end at the number of listed rows")
-    if G > M:
-        raise ValueError(f"{G} groups for {M} rows")
-    if rows.size and (rows.min() < 0 or rows.max() >= M):
-        raise ValueError(f"group rows must lie in [0, {M})")
-    if rows.size and np.bincount(rows, minlength=M).max() > 1:
-        raise ValueError("a row may be listed in one group only")
-    if G * int(np.diff(offsets).max()) >= 1 << 31:  # the expanded rows of a replicate are counted in 32 bits
-        raise ValueError("G times the largest group must stay below 2^31")
+    offsets, rows, G = check_groups(groups, M, exclusive=True)
     unit = np.full(M, -1, dtype=np.int32)
     unit[rows] = np.repeat(np.arange(G, dtype=np.int32), np.diff(offsets))
     return unit, G
@@ -177,10 +166,7 @@ def reliability(probs: torch.Tensor, labels: torch.Tensor, n_bins: int = 15, con
     its own unit.  The replicates are drawn in chunks of at most ``CHUNK_BYTES`` of counts; the result does not depend on the chunking.
     No host synchronisation."""
     n_bins = check_bins(n_bins)
-    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 0 <= B <= MAX_REPLICATES:
-        raise ValueError(f"B must be an integer in [0, {MAX_REPLICATES}], got {B!r}")
-    if not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    bootstrap._check_B_seed(B, seed, min_B=0)
     _require_cuda(probs, labels, conf)
     if probs.dim() != 2 or labels.shape != probs.shape[:1] or (conf is not None and conf.shape != probs.shape[:1]):
         raise ValueError("probs must be (M, K_real), labels and conf (M,)")
@@ -201,7 +187,7 @@ def reliability(probs: torch.Tensor, labels: torch.Tensor, n_bins: int = 15, con
         n, hit, qsum = (torch.empty(B + 1, n_bins, dtype=torch.int64, device=dev) for _ in range(3))
         cn, cpos, cq = (torch.empty(B + 1, K, n_bins, dtype=torch.int64, device=dev) for _ in range(3))
         skipped = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        ws = torch.empty(int(lib.pasn_calibration_workspace_bytes(M, G, K, n_bins, B)) // 8 + 1, dtype=torch.float64, device=dev)
+        ws = _lib.workspace(lib.pasn_calibration_workspace_bytes(M, G, K, n_bins, B), dev)
         outs = (n, hit, qsum, cn, cpos, cq, skipped, stats)
         step = max(1, min(B, CHUNK_BYTES // (4 * G))) if B else 1
         # a chunk writes its replicates at rows b0 .. and the point estimate behind them, where the next chunk's first replicate lands

@@ -1,6 +1,7 @@
 // block_reduce.h -- the fixed-order block reduce behind every two-stage sum of the training path (train.hip's row passes, the depthwise
-// weight-gradient kernels of dw_wgrad.hip).  DESIGN.md promises bitwise reproducible gradients; the summation order of the loop below keeps
-// that promise, which is why there is ONE copy of it.
+// weight-gradient kernels of dw_wgrad.hip) and behind every block sum of the evaluation kernels (eval_metrics, selective, bootstrap,
+// calibration).  DESIGN.md promises bitwise reproducible gradients and statistics; the summation order of the loops below keeps that
+// promise, which is why there is ONE copy of it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +54,15 @@ __device__ __forceinline__ double block_sum_fixed(double v, double* red) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// its int64 twin, with the same two barriers (integers: any order gives the same sum)
+__device__ __forceinline__ long long block_sum_i64(long long v, long long* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
 }
 
 }  // namespace pasn

@@ -9,7 +9,7 @@
 // pasn_bootstrap_metrics: what all replicates share is computed once, in five launches:
 //   1. gid: the group of every listed row (a wave per group), -1 for the others
 //   2. info: per row (group | label << 20 | first largest probability << 24), negative for a row that never enters
-//   3. rank: the rank by counting of order_key.h for every class column (ascending probability) and for u (ascending, NaN last)
+//   3. rank: rank_count_chunk of order_key.h for every class column (ascending probability) and for u (ascending, NaN last)
 //   4. scatter: per order and position the word (group | POS | NAN) and the key; POS marks the positives of the order (label == k for
 //      column k, a wrong prediction for u)
 //   5. ties: TIE marks the first position of every run of equal keys
@@ -20,22 +20,21 @@
 // START OF ITS TIE RUN forward, and
 //   U2 = Wp Wn + sum_{i pos} w_i Nlt_i - sum_{j neg} w_j Plt_j        (Nlt / Plt: negative / positive weight with a strictly smaller key)
 // which is sum w_i w_j (2 [s_j < s_i] + [s_j == s_i]) over the pairs, in integers.  The u order also adds the risk terms 1 - acc[m] of
-// every copy of a row, each thread its positions in order, the threads in a fixed tree.  One barrier per chunk (wave summaries in a
-// double-buffered LDS table).
+// every copy of a row, each thread its positions in order, the threads in the tree of block_sum_fixed.  One barrier per chunk (wave
+// summaries in a double-buffered LDS table).  Thread 0 turns the confusion matrix into accuracy, balanced accuracy and mean F1 with the
+// ClassTally of eval_common.h, the arithmetic of rc_curve_kernel (selective.hip).
 #include "common.h"
-#include "order_key.h"
+#include "eval_common.h"
 #include "philox.h"
 
 namespace pasn {
 
-constexpr int BOOT_MAX_K = 16;
-constexpr long BOOT_MAX_M = 1L << 20;
-constexpr int BOOT_MAX_B = 65536;
 constexpr int BOOT_LDS_MAX_G = PASN_BOOTSTRAP_LDS_MAX_G;  // uint16 counts: 32 KiB of LDS, four blocks per CU
 constexpr int BOOT_NT = 256, BOOT_E = 8, BOOT_CHUNK = BOOT_NT * BOOT_E;
 constexpr size_t BOOT_SLOT_BYTES = 256ull << 20;  // the count slices of the global path together
 constexpr int BOOT_MAX_SLOTS = 512;
 constexpr uint32_t BOOT_EMPTY = 0xFFFFFFFFu, BOOT_TIE = 1u << 31, BOOT_POS = 1u << 30, BOOT_NAN = 1u << 29, BOOT_GID = 0xFFFFFu;
+constexpr ClassCell BOOT_CELL = {20, 24};  // info = group | label << 20 | prediction << 24
 
 // ---- draws -------------------------------------------------------------------------------------------------------------------------------
 // counts of replicate b as uint16 pairs in s_cnt[(G + 1) / 2]; ones: the point estimate.  Ends with a barrier.
@@ -125,33 +124,14 @@ __global__ __launch_bounds__(256) void boot_info_kernel(const float* __restrict_
     const int g = gid ? gid[i] : (int)i;
     int v = -1;
     if (L >= 0 && L < K && g >= 0) {
-        const float* p = probs + i * K;
-        int pred = 0;
-        float best = p[0];
-        for (int k = 1; k < K; ++k)
-            if (p[k] > best) {  // the first largest
-                best = p[k];
-                pred = k;
-            }
-        v = g | (L << 20) | (pred << 24);
+        float best;
+        v = g | BOOT_CELL.pack(L, first_largest(probs + i * K, K, &best));
     }
     info[i] = v;
 }
 
-struct BootGeom {
-    int gx, gy, chunk;  // row blocks, row-j chunks and their length (a multiple of the tile)
-    long Mp;            // positions of an order, padded to whole sweep chunks
-};
-
-static BootGeom boot_geom(long M) {
-    BootGeom g;
-    g.gx = ceil_div(M, RANK_TILE);
-    const long c = std::max(1024L, (long)ceil_div(M, 64));  // at most 64 chunks of >= 1024 rows
-    g.chunk = (int)(((c + RANK_TILE - 1) / RANK_TILE) * RANK_TILE);
-    g.gy = ceil_div(M, g.chunk);
-    g.Mp = (long)ceil_div(M, BOOT_CHUNK) * BOOT_CHUNK;
-    return g;
-}
+// positions of an order, padded to whole sweep chunks
+static long boot_padded(long M) { return (long)ceil_div(M, BOOT_CHUNK) * BOOT_CHUNK; }
 
 // key of row j in order c: column c of probs, or u for c == K; a row that never enters is padding
 __device__ __forceinline__ uint32_t boot_key(const float* __restrict__ probs, const float* __restrict__ u, const int32_t* __restrict__ info,
@@ -162,23 +142,14 @@ __device__ __forceinline__ uint32_t boot_key(const float* __restrict__ probs, co
 
 // grid (gx, gy, orders); rank [orders][M] is zero
 __global__ __launch_bounds__(256) void boot_rank_kernel(const float* __restrict__ probs, const float* __restrict__ u,
-                                                        const int32_t* __restrict__ info, long M, int K, BootGeom g,
+                                                        const int32_t* __restrict__ info, long M, int K, RankGeom g,
                                                         int32_t* __restrict__ rank) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_key[RANK_TILE];
-    const int tid = threadIdx.x, c = blockIdx.z;
-    const long i0 = (long)blockIdx.x * RANK_TILE, i = i0 + tid;
-    const uint32_t ki = i < M ? boot_key(probs, u, info, i, K, c) : RC_KEY_PAD;
-    const bool valid = ki != RC_KEY_PAD;
-    int cnt = 0;
-    const long j0 = (long)blockIdx.y * g.chunk, j1 = min(M, j0 + (long)g.chunk);
-    for (long jt = j0; jt < j1; jt += RANK_TILE) {
-        __syncthreads();
-        const long j = jt + tid;
-        s_key[tid] = j < j1 ? boot_key(probs, u, info, j, K, c) : RC_KEY_PAD;  // the tail of a short tile counts for nobody
-        __syncthreads();
-        if (valid) cnt += rank_count_tile(s_key, ki, jt, i0, tid);
-    }
-    if (valid && cnt) atomicAdd(&rank[(long)c * M + i], cnt);
+    const int c = blockIdx.z;
+    const long i = (long)blockIdx.x * RANK_TILE + threadIdx.x;
+    const auto key = [&](long j) { return boot_key(probs, u, info, j, K, c); };
+    const uint32_t ki = i < M ? key(i) : RC_KEY_PAD;
+    const int cnt = rank_count_chunk(key, ki, M, g.chunk);
+    if (ki != RC_KEY_PAD && cnt) atomicAdd(&rank[(long)c * M + i], cnt);
 }
 
 // grid (gx, orders); og [orders][Mp] is BOOT_EMPTY everywhere
@@ -192,7 +163,7 @@ __global__ __launch_bounds__(256) void boot_scatter_kernel(const float* __restri
     const int v = info[i];
     if (v < 0) return;
     const uint32_t key = boot_key(probs, u, info, i, K, c);
-    const int L = (v >> 20) & 15, P = (v >> 24) & 15;
+    const int L = BOOT_CELL.label(v), P = BOOT_CELL.pred(v);
     const bool pos = c < K ? L == c : L != P;
     const long r = rank[(long)c * M + i];  // < the number of rows that enter <= M
     og[(long)c * Mp + r] = ((uint32_t)v & BOOT_GID) | (pos ? BOOT_POS : 0u) | (c == K && key == RC_KEY_NAN ? BOOT_NAN : 0u);
@@ -223,14 +194,6 @@ struct BootWave {  // a wave's summary of one chunk
     int flag;
 };
 
-__device__ __forceinline__ long long boot_block_sum(long long v, long long* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // One order of one replicate.  Returns (block-wide) sum_{pos} w Nlt - sum_{neg} w Plt; AURC: *risk = the sum of 1 - acc[m] over the
 // expanded rows (negatives are the right predictions), *nan_seen set when a row with weight has the NAN mark.
 template <bool LDSC, bool AURC>
@@ -258,11 +221,7 @@ __device__ __forceinline__ long long boot_sweep(const uint32_t* __restrict__ og,
             }
             tot += (word[e] & BOOT_POS) ? (unsigned long long)w[e] << 32 : (unsigned long long)w[e];
         }
-        unsigned long long inc = tot;  // inclusive scan over the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
+        const unsigned long long inc = wave_scan_incl_u64(tot);
         const unsigned long long ex_w = inc - tot;
         unsigned long long ps = ex_w + rel_snap;  // the latest tie start at or before this thread's last position, relative to the wave
         int pf = hf;
@@ -317,25 +276,25 @@ __device__ __forceinline__ long long boot_sweep(const uint32_t* __restrict__ og,
             run += pos ? (unsigned long long)w[e] << 32 : (unsigned long long)w[e];
         }
     }
-    if (AURC) {
+    if (AURC) {  // the tree of block_sum_fixed, written out: the call costs boot_metrics_kernel<true> five VGPRs (profiles/README.md)
         for (int o = 32; o > 0; o >>= 1) dsum += __shfl_xor(dsum, o);
         __syncthreads();
         if (lane == 0) s_redd[wave] = dsum;
         __syncthreads();
         *risk = (s_redd[0] + s_redd[1]) + (s_redd[2] + s_redd[3]);
     }
-    return boot_block_sum(S, s_red);
+    return block_sum_i64(S, s_red);
 }
 
 template <bool LDSC>
 __global__ __launch_bounds__(BOOT_NT) void boot_metrics_kernel(BootArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ uint32_t boot_lds[];
-    __shared__ uint32_t s_cm[BOOT_MAX_K * BOOT_MAX_K];
+    __shared__ uint32_t s_cm[EVAL_MAX_K * EVAL_MAX_K];
     __shared__ BootWave s_ws[2][4];
     __shared__ long long s_red[4];
     __shared__ double s_redd[4];
-    __shared__ long long s_s[BOOT_MAX_K + 1];
+    __shared__ long long s_s[EVAL_MAX_K + 1];
     __shared__ int s_nan;
     const int tid = threadIdx.x, K = a.K;
     int32_t* cg = LDSC ? nullptr : a.slots + (long)blockIdx.x * a.G;
@@ -350,7 +309,7 @@ __global__ __launch_bounds__(BOOT_NT) void boot_metrics_kernel(BootArgs a) {
             const int v = a.info[i];
             if (v < 0) continue;
             const uint32_t w = LDSC ? boot_count_lds(boot_lds, v & BOOT_GID) : boot_count_global(cg, v & BOOT_GID);
-            if (w) atomicAdd(&s_cm[((v >> 20) & 15) * K + ((v >> 24) & 15)], w);
+            if (w) atomicAdd(&s_cm[BOOT_CELL.label(v) * K + BOOT_CELL.pred(v)], w);
         }
         __syncthreads();
         double risk = 0.0;
@@ -362,13 +321,13 @@ __global__ __launch_bounds__(BOOT_NT) void boot_metrics_kernel(BootArgs a) {
         }
         __syncthreads();
         if (tid != 0) continue;
-        long long W = 0, trace = 0;
+        long long W = 0;
         for (int e = 0; e < K * K; ++e) {
             W += s_cm[e];
             a.cm[(long)b * K * K + e] = s_cm[e];
         }
-        double rsum = 0.0, fsum = 0.0, num = 0.0, den = 0.0;
-        int present = 0;
+        ClassTally tally;
+        double num = 0.0, den = 0.0;
         bool defined = true;
         for (int k = 0; k < K; ++k) {
             long long sup = 0, prd = 0;
@@ -377,12 +336,7 @@ __global__ __launch_bounds__(BOOT_NT) void boot_metrics_kernel(BootArgs a) {
                 prd += s_cm[j * K + k];
             }
             const long long tp = s_cm[k * K + k], nneg = W - sup, u2 = sup * nneg + s_s[k];
-            trace += tp;
-            if (sup > 0) {
-                rsum += (double)tp / (double)sup;
-                ++present;
-            }
-            if (sup + prd > 0) fsum += 2.0 * (double)tp / (double)(sup + prd);
+            tally.add(tp, sup, prd);
             a.u2[(long)b * K + k] = u2;
             a.n_pos[(long)b * K + k] = sup;
             a.n_neg[(long)b * K + k] = nneg;
@@ -395,14 +349,14 @@ __global__ __launch_bounds__(BOOT_NT) void boot_metrics_kernel(BootArgs a) {
         }
         const double nan = __builtin_nan("");
         double* st = a.stats + (long)b * 6;
-        st[0] = W > 0 ? (double)trace / (double)W : 0.0;
-        st[1] = present > 0 ? rsum / (double)present : 0.0;
-        st[2] = fsum / (double)K;
+        st[0] = tally.accuracy(W);
+        st[1] = tally.balanced_accuracy();
+        st[2] = tally.f1_mean(K);
         st[3] = defined ? num / den : nan;
         st[4] = nan;
         st[5] = nan;
         if (a.orders > K) {
-            const long long wrong = W - trace;
+            const long long trace = tally.trace, wrong = W - trace;
             st[4] = W > 0 ? risk / (double)W : nan;
             if (!s_nan && wrong > 0 && trace > 0) st[5] = (double)(wrong * trace + s_s[K]) / (2.0 * (double)wrong * (double)trace);
         }
@@ -422,29 +376,23 @@ static int boot_slots(long G, int B) {
     return (int)std::min({(long)B + 1, (long)BOOT_MAX_SLOTS, fit});
 }
 
-static BootWorkspace boot_workspace(void* ws, long M, long G, int K, int B, const BootGeom& g) {
+static BootWorkspace boot_workspace(void* ws, long M, long G, int K, int B) {
     BootWorkspace w;
-    char* p = static_cast<char*>(ws);
-    const size_t orders = (size_t)K + 1;
-    w.og = reinterpret_cast<uint32_t*>(p);
-    p += orders * g.Mp * sizeof(uint32_t);
-    w.skey = reinterpret_cast<uint32_t*>(p);
-    p += orders * g.Mp * sizeof(uint32_t);
-    w.rank = reinterpret_cast<int32_t*>(p);
-    p += orders * M * sizeof(int32_t);
-    w.gid = reinterpret_cast<int32_t*>(p);
-    p += (size_t)M * sizeof(int32_t);
-    w.info = reinterpret_cast<int32_t*>(p);
-    p += (size_t)M * sizeof(int32_t);
+    Carve c{static_cast<char*>(ws)};
+    const size_t orders = (size_t)K + 1, Mp = (size_t)boot_padded(M);
+    w.og = c.take<uint32_t>(orders * Mp);
+    w.skey = c.take<uint32_t>(orders * Mp);
+    w.rank = c.take<int32_t>(orders * M);
+    w.gid = c.take<int32_t>((size_t)M);
+    w.info = c.take<int32_t>((size_t)M);
     w.nslots = boot_slots(G, B);
-    w.slots = reinterpret_cast<int32_t*>(p);
-    p += (size_t)w.nslots * G * sizeof(int32_t);
-    w.bytes = (size_t)(p - static_cast<char*>(ws));
+    w.slots = c.take<int32_t>((size_t)w.nslots * G);
+    w.bytes = c.used;
     return w;
 }
 
 static bool boot_sizes_ok(long M, long G, int K, int B) {
-    return K >= 2 && K <= BOOT_MAX_K && M >= 1 && M <= BOOT_MAX_M && G >= 1 && G <= M && B >= 1 && B <= BOOT_MAX_B;
+    return K >= 2 && K <= EVAL_MAX_K && M >= 1 && M <= EVAL_MAX_ROWS && G >= 1 && G <= M && B >= 1 && B <= EVAL_MAX_REPLICATES;
 }
 
 }  // namespace pasn
@@ -455,8 +403,8 @@ extern "C" int pasn_bootstrap_lds_max_groups(void) { return BOOT_LDS_MAX_G; }
 
 extern "C" int pasn_bootstrap_counts(int32_t* counts, long G, int B, uint64_t seed, int b0, void* stream) {
     PASN_REQUIRE(counts, "counts is required");
-    PASN_REQUIRE(G >= 1 && G <= BOOT_MAX_M, "G must lie in [1, 2^20]");
-    PASN_REQUIRE(B >= 1 && B <= BOOT_MAX_B, "B must lie in [1, 65536]");
+    PASN_REQUIRE(G >= 1 && G <= EVAL_MAX_ROWS, "G must lie in [1, 2^20]");
+    PASN_REQUIRE(B >= 1 && B <= EVAL_MAX_REPLICATES, "B must lie in [1, 65536]");
     PASN_REQUIRE(b0 >= 0 && (long)b0 + B <= (1L << 31) - 1, "b0 must not be negative, and b0 + B must fit an int32");
     hipStream_t s = (hipStream_t)stream;
     const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
@@ -472,7 +420,7 @@ extern "C" int pasn_bootstrap_counts(int32_t* counts, long G, int B, uint64_t se
 
 extern "C" size_t pasn_bootstrap_workspace_bytes(long M, long G, int K_real, int B) {
     if (!boot_sizes_ok(M, G, K_real, B)) return 0;
-    return boot_workspace(nullptr, M, G, K_real, B, boot_geom(M)).bytes;
+    return boot_workspace(nullptr, M, G, K_real, B).bytes;
 }
 
 extern "C" int pasn_bootstrap_metrics(const float* probs, const int32_t* labels, const float* u, const int64_t* group_offsets,
@@ -482,31 +430,32 @@ extern "C" int pasn_bootstrap_metrics(const float* probs, const int32_t* labels,
     PASN_REQUIRE(stats && cm && u2 && n_pos && n_neg, "every output is required");
     PASN_REQUIRE(workspace, "workspace is required");
     PASN_REQUIRE((group_offsets == nullptr) == (group_rows == nullptr), "group_offsets and group_rows come together");
-    PASN_REQUIRE(K_real >= 2 && K_real <= BOOT_MAX_K, "K_real must lie in [2, 16]");
-    PASN_REQUIRE(M >= 1 && M <= BOOT_MAX_M, "M must lie in [1, 2^20]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(M >= 1 && M <= EVAL_MAX_ROWS, "M must lie in [1, 2^20]");
     PASN_REQUIRE(G >= 1 && G <= M, "G must lie in [1, M]");
     PASN_REQUIRE(group_offsets || G == M, "without groups every row is its own group: G must equal M");
-    PASN_REQUIRE(B >= 1 && B <= BOOT_MAX_B, "B must lie in [1, 65536]");
+    PASN_REQUIRE(B >= 1 && B <= EVAL_MAX_REPLICATES, "B must lie in [1, 65536]");
     PASN_REQUIRE(((uintptr_t)workspace & 15) == 0, "misaligned workspace");
-    const BootGeom g = boot_geom(M);
-    const BootWorkspace w = boot_workspace(workspace, M, G, K_real, B, g);
+    const RankGeom g = rank_geom(M);
+    const long Mp = boot_padded(M);
+    const BootWorkspace w = boot_workspace(workspace, M, G, K_real, B);
     const int orders = u ? K_real + 1 : K_real;
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(w.og, 0xFF, (size_t)orders * g.Mp * sizeof(uint32_t), s) != hipSuccess ||
+    if (hipMemsetAsync(w.og, 0xFF, (size_t)orders * Mp * sizeof(uint32_t), s) != hipSuccess ||
         hipMemsetAsync(w.rank, 0, (size_t)orders * M * sizeof(int32_t), s) != hipSuccess ||
         (group_offsets && hipMemsetAsync(w.gid, 0xFF, (size_t)M * sizeof(int32_t), s) != hipSuccess))
         return check_launch("bootstrap_metrics (zeroing)");
     if (group_offsets) hipLaunchKernelGGL(boot_gid_kernel, dim3(ceil_div(G, 4)), dim3(256), 0, s, group_offsets, group_rows, G, M, w.gid);
     hipLaunchKernelGGL(boot_info_kernel, dim3(g.gx), dim3(256), 0, s, probs, labels, group_offsets ? w.gid : nullptr, M, K_real, w.info);
     hipLaunchKernelGGL(boot_rank_kernel, dim3(g.gx, g.gy, orders), dim3(256), 0, s, probs, u, w.info, M, K_real, g, w.rank);
-    hipLaunchKernelGGL(boot_scatter_kernel, dim3(g.gx, orders), dim3(256), 0, s, probs, u, w.info, M, K_real, g.Mp, w.rank, w.og, w.skey);
-    hipLaunchKernelGGL(boot_ties_kernel, dim3(g.gx, orders), dim3(256), 0, s, M, g.Mp, w.og, w.skey);
+    hipLaunchKernelGGL(boot_scatter_kernel, dim3(g.gx, orders), dim3(256), 0, s, probs, u, w.info, M, K_real, Mp, w.rank, w.og, w.skey);
+    hipLaunchKernelGGL(boot_ties_kernel, dim3(g.gx, orders), dim3(256), 0, s, M, Mp, w.og, w.skey);
     BootArgs a;
     a.info = w.info;
     a.og = w.og;
     a.slots = w.slots;
     a.M = M;
-    a.Mp = g.Mp;
+    a.Mp = Mp;
     a.G = G;
     a.K = K_real;
     a.orders = orders;

@@ -4,7 +4,8 @@
 //
 // pasn_calibration_bins: what all replicates share is computed once (calib_rows_kernel): per row its unit (-1: the row never enters), a
 // 64-bit word (q | bin << 40 | hit << 46 | skipped << 47 | label << 48) for the top label and one (q | bin << 40 | unbinned << 47) per
-// class, and the row's fp64 Brier and NLL terms.  Then a block owns an output row (replicate b < B, or the point estimate B: every weight
+// class, and the row's fp64 Brier and NLL terms; the top label is first_largest of eval_common.h, the rule of the confusion matrix and of
+// the risk-coverage curve.  Then a block owns an output row (replicate b < B, or the point estimate B: every weight
 // 1), the blocks looping when B + 1 exceeds the grid: per row it gathers one count and adds into ONE LDS histogram of (K_real + 1) x n_bins x
 // {n, hit, qsum} with 64-bit integer LDS atomics -- integers, so the histogram does not depend on the order --, the Brier / NLL sums go
 // through block_sum_fixed, and thread 0 writes the statistics.
@@ -15,13 +16,12 @@
 // array.  Launches 0 .. 2 evaluate 1/64, 64 and 1; launches 3 .. 50 take the PASN_TEMPERATURE_STEPS steps; a one-block finish writes `fit`.
 #include <cfloat>
 
-#include "block_reduce.h"
 #include "common.h"
+#include "eval_common.h"
 
 namespace pasn {
 
-constexpr int CAL_MAX_K = 16, CAL_MAX_BINS = 64, CAL_MAX_B = 65536, CAL_NT = 256, CAL_MAX_GRID = 2048;
-constexpr long CAL_MAX_M = 1L << 20;
+constexpr int CAL_MAX_BINS = 64, CAL_NT = 256, CAL_MAX_GRID = 2048;
 constexpr unsigned long long CAL_Q_MASK = (1ull << 40) - 1, CAL_HIT = 1ull << 46, CAL_SKIP = 1ull << 47;
 constexpr int TEMP_MAX_BLOCKS = 256, TEMP_LAUNCHES = 3 + PASN_TEMPERATURE_STEPS;
 constexpr double TEMP_LO = 1.0 / 64.0, TEMP_HI = 64.0;
@@ -44,16 +44,12 @@ struct CalWorkspace {
 
 static CalWorkspace cal_workspace(void* ws, long M, int K) {
     CalWorkspace w;
-    char* p = static_cast<char*>(ws);
-    w.top = reinterpret_cast<unsigned long long*>(p);
-    p += (size_t)M * 8;
-    w.cls = reinterpret_cast<unsigned long long*>(p);
-    p += (size_t)M * K * 8;
-    w.terms = reinterpret_cast<double*>(p);
-    p += (size_t)M * 16;
-    w.unit = reinterpret_cast<int32_t*>(p);
-    p += (((size_t)M * 4 + 15) / 16) * 16;
-    w.bytes = (size_t)(p - static_cast<char*>(ws));
+    Carve c{static_cast<char*>(ws)};
+    w.top = c.take<unsigned long long>((size_t)M);
+    w.cls = c.take<unsigned long long>((size_t)M * K);
+    w.terms = c.take<double>((size_t)M * 2);
+    w.unit = c.take<int32_t>(((size_t)M + 3) / 4 * 4);  // rounded up to 16 bytes
+    w.bytes = c.used;
     return w;
 }
 
@@ -70,15 +66,11 @@ __global__ __launch_bounds__(CAL_NT) void calib_rows_kernel(const float* __restr
         return;
     }
     const float* p = probs + i * K;
-    int pred = 0;
-    float best = p[0];
+    float best;
+    const int pred = first_largest(p, K, &best);
     double brier = 0.0, pl = 0.0;
     for (int k = 0; k < K; ++k) {
         const float v = p[k];
-        if (v > best) {  // the first largest
-            best = v;
-            pred = k;
-        }
         const double d = (double)v - (k == L ? 1.0 : 0.0);
         brier += d * d;
         if (k == L) pl = (double)v;
@@ -102,7 +94,7 @@ struct CalArgs {
 
 __global__ __launch_bounds__(CAL_NT) void calib_bins_kernel(CalArgs a) {
 #pragma clang fp contract(off)
-    __shared__ unsigned long long s_h[(CAL_MAX_K + 1) * CAL_MAX_BINS * 3];  // [K + 1][n_bins][n, hit, qsum]; table K is the top label's
+    __shared__ unsigned long long s_h[(EVAL_MAX_K + 1) * CAL_MAX_BINS * 3];  // [K + 1][n_bins][n, hit, qsum]; table K is the top label's
     __shared__ unsigned long long s_skip;
     __shared__ double s_red[CAL_NT / 64];
     const int tid = threadIdx.x, K = a.K, nb = a.n_bins, cells = (K + 1) * nb * 3;
@@ -183,8 +175,8 @@ __global__ __launch_bounds__(CAL_NT) void calib_bins_kernel(CalArgs a) {
 }
 
 static bool cal_sizes_ok(long M, long G, int K, int n_bins, int B) {
-    return K >= 2 && K <= CAL_MAX_K && M >= 1 && M <= CAL_MAX_M && G >= 1 && G <= M && n_bins >= 1 && n_bins <= CAL_MAX_BINS && B >= 0 &&
-           B <= CAL_MAX_B;
+    return K >= 2 && K <= EVAL_MAX_K && M >= 1 && M <= EVAL_MAX_ROWS && G >= 1 && G <= M && n_bins >= 1 && n_bins <= CAL_MAX_BINS && B >= 0 &&
+           B <= EVAL_MAX_REPLICATES;
 }
 
 // ---- temperature scaling -----------------------------------------------------------------------------------------------------------------
@@ -215,14 +207,14 @@ static int temp_blocks(long M) { return std::min(ceil_div(M, CAL_NT), TEMP_MAX_B
 __device__ __forceinline__ double temp_row(const float* __restrict__ z, int K, int L, double beta, double* e, double* mean, double* var,
                                            double* dl) {
 #pragma clang fp contract(off)
-    double d[CAL_MAX_K];
+    double d[EVAL_MAX_K];
     float zmax = z[0];
 #pragma unroll
-    for (int k = 1; k < CAL_MAX_K; ++k)
+    for (int k = 1; k < EVAL_MAX_K; ++k)
         if (k < K) zmax = fmaxf(zmax, z[k]);
     double S = 0.0, m = 0.0, v = 0.0, lab = 0.0;
 #pragma unroll
-    for (int k = 0; k < CAL_MAX_K; ++k) {
+    for (int k = 0; k < EVAL_MAX_K; ++k) {
         d[k] = k < K ? (double)z[k] - (double)zmax : 0.0;
         e[k] = k < K ? exp(beta * d[k]) : 0.0;
         S += e[k];
@@ -231,7 +223,7 @@ __device__ __forceinline__ double temp_row(const float* __restrict__ z, int K, i
     }
     m = m / S;
 #pragma unroll
-    for (int k = 0; k < CAL_MAX_K; ++k) v += e[k] * ((d[k] - m) * (d[k] - m));
+    for (int k = 0; k < EVAL_MAX_K; ++k) v += e[k] * ((d[k] - m) * (d[k] - m));
     *mean = m;
     *var = v / S;
     *dl = lab;
@@ -304,7 +296,7 @@ __global__ __launch_bounds__(CAL_NT) void temp_step_kernel(const float* __restri
     for (long i = (long)blockIdx.x * CAL_NT + tid; i < M; i += (long)nblocks * CAL_NT) {
         const int L = labels[i];
         if (L < 0 || L >= K_real) continue;
-        double e[CAL_MAX_K], mean, var, dl;
+        double e[EVAL_MAX_K], mean, var, dl;
         const double S = temp_row(logits + i * K, K_real, L, beta, e, &mean, &var, &dl);
         acc.g += log(S) - beta * dl;
         acc.d1 += mean - dl;
@@ -333,11 +325,11 @@ __global__ __launch_bounds__(CAL_NT) void temp_probs_kernel(const float* __restr
 #pragma clang fp contract(off)
     const long i = (long)blockIdx.x * CAL_NT + threadIdx.x;
     if (i >= M) return;
-    double e[CAL_MAX_K], mean, var, dl;
+    double e[EVAL_MAX_K], mean, var, dl;
     const double S = temp_row(logits + i * K, K_real, -1, beta[0], e, &mean, &var, &dl);
     float best = 0.0f;
 #pragma unroll
-    for (int k = 0; k < CAL_MAX_K; ++k)
+    for (int k = 0; k < EVAL_MAX_K; ++k)
         if (k < K_real) {
             const float p = (float)(e[k] / S);
             probs[i * K_real + k] = p;
@@ -346,7 +338,7 @@ __global__ __launch_bounds__(CAL_NT) void temp_probs_kernel(const float* __restr
     if (u) u[i] = 1.0f - best;
 }
 
-static bool temp_sizes_ok(long M, int K, int K_real) { return K_real >= 2 && K_real <= CAL_MAX_K && K >= K_real && K <= 17 && M >= 1 && M <= CAL_MAX_M; }
+static bool temp_sizes_ok(long M, int K, int K_real) { return K_real >= 2 && K_real <= EVAL_MAX_K && K >= K_real && K <= 17 && M >= 1 && M <= EVAL_MAX_ROWS; }
 
 }  // namespace pasn
 
@@ -364,12 +356,12 @@ extern "C" int pasn_calibration_bins(const float* probs, const int32_t* labels, 
     PASN_REQUIRE(probs && labels, "probs and labels are required");
     PASN_REQUIRE(n && hit && qsum && cn && cpos && cq && skipped && stats, "every output is required");
     PASN_REQUIRE(workspace, "workspace is required");
-    PASN_REQUIRE(K_real >= 2 && K_real <= CAL_MAX_K, "K_real must lie in [2, 16]");
-    PASN_REQUIRE(M >= 1 && M <= CAL_MAX_M, "M must lie in [1, 2^20]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(M >= 1 && M <= EVAL_MAX_ROWS, "M must lie in [1, 2^20]");
     PASN_REQUIRE(G >= 1 && G <= M, "G must lie in [1, M]");
     PASN_REQUIRE(row_unit || G == M, "without row_unit every row is its own unit: G must equal M");
     PASN_REQUIRE(n_bins >= 1 && n_bins <= CAL_MAX_BINS, "n_bins must lie in [1, 64]");
-    PASN_REQUIRE(B >= 0 && B <= CAL_MAX_B, "B must lie in [0, 65536]");
+    PASN_REQUIRE(B >= 0 && B <= EVAL_MAX_REPLICATES, "B must lie in [0, 65536]");
     PASN_REQUIRE((counts == nullptr) == (B == 0), "counts is NULL exactly when B == 0");
     PASN_REQUIRE(((uintptr_t)workspace & 15) == 0, "misaligned workspace");
     hipStream_t s = (hipStream_t)stream;
@@ -403,9 +395,9 @@ extern "C" int pasn_temperature_fit(const float* logits, const int32_t* labels, 
                                     void* stream) {
     PASN_REQUIRE(logits && labels && fit, "logits, labels and fit are required");
     PASN_REQUIRE(workspace, "workspace is required");
-    PASN_REQUIRE(K_real >= 2 && K_real <= CAL_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
     PASN_REQUIRE(K >= K_real && K <= 17, "K must lie in [K_real, 17]");
-    PASN_REQUIRE(M >= 1 && M <= CAL_MAX_M, "M must lie in [1, 2^20]");
+    PASN_REQUIRE(M >= 1 && M <= EVAL_MAX_ROWS, "M must lie in [1, 2^20]");
     PASN_REQUIRE(((uintptr_t)workspace & 15) == 0, "misaligned workspace");
     hipStream_t s = (hipStream_t)stream;
     const TempWorkspace w = temp_workspace(workspace);
@@ -418,9 +410,9 @@ extern "C" int pasn_temperature_fit(const float* logits, const int32_t* labels, 
 
 extern "C" int pasn_temperature_probs(const float* logits, long M, int K, int K_real, const double* beta, float* probs, float* u, void* stream) {
     PASN_REQUIRE(logits && beta && probs, "logits, beta and probs are required");
-    PASN_REQUIRE(K_real >= 2 && K_real <= CAL_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
     PASN_REQUIRE(K >= K_real && K <= 17, "K must lie in [K_real, 17]");
-    PASN_REQUIRE(M >= 1 && M <= CAL_MAX_M, "M must lie in [1, 2^20]");
+    PASN_REQUIRE(M >= 1 && M <= EVAL_MAX_ROWS, "M must lie in [1, 2^20]");
     hipLaunchKernelGGL(temp_probs_kernel, dim3(ceil_div(M, CAL_NT)), dim3(CAL_NT), 0, (hipStream_t)stream, logits, M, K, K_real, beta, probs, u);
     return check_launch("temperature_probs");
 }

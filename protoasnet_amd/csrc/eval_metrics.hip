@@ -15,20 +15,12 @@
 // atomics, no zeroing), the y = 0 blocks also count the positives, NaN rows and bad labels of their rows i.  Launch 2 (one block) sums the
 // slots in int64 and writes the per-class and weighted AUC in fp64.
 #include "common.h"
+#include "eval_common.h"  // block_sum_fixed / block_sum_i64, rank_geom, softmax_max_sum_f32
 
 namespace pasn {
 
 constexpr int EV_MAX_P = 4096;  // 3 x P floats of LDS per row block
-constexpr int AUC_MAX_K = 16;
-constexpr int AUC_TILE = 256;
-
-__device__ __forceinline__ double ev_block_sum_f64(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
+constexpr int AUC_TILE = RANK_TILE;
 
 // rank of element p among x[lo, hi) under a stable descending sort
 __device__ __forceinline__ int ev_rank_desc(const float* x, int lo, int hi, int p) {
@@ -62,10 +54,8 @@ __global__ __launch_bounds__(256) void eval_batch_stats_kernel(const float* __re
     const float* lg = logits + (long)n * K;
     if (tid == 0) {
         if (probs) {  // softmax over the real-class logits (Video_XProtoNet_e2e.py:114-117)
-            float m = lg[0];
-            for (int k = 1; k < K_real; ++k) m = fmaxf(m, lg[k]);
-            float s = 0.0f;
-            for (int k = 0; k < K_real; ++k) s += expf(lg[k] - m);
+            float m;
+            const float s = softmax_max_sum_f32(lg, K_real, &m);
             for (int k = 0; k < K_real; ++k) probs[row * K_real + k] = __fdiv_rn(expf(lg[k] - m), s);
         }
         if (labels) labels[row] = (int32_t)target[n];
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(256) void eval_batch_stats_kernel(const float* __re
         part += (double)v[p];
     }
     if (tid == 0) has_nan = 0;
-    const float rs = (float)ev_block_sum_f64(part, red);  // includes a __syncthreads: v and has_nan are visible
+    const float rs = (float)block_sum_fixed(part, red);  // includes a __syncthreads: v and has_nan are visible
     if (div_counts) {  // top-k of each prototype group by similarity, ties to the lower index
         for (int p = tid; p < P; p += 256) {
             const bool cls = p < P_cls;
@@ -122,27 +112,15 @@ __global__ __launch_bounds__(256) void eval_batch_stats_kernel(const float* __re
     }
 }
 
-struct AucGeom {
-    int gx, gy, chunk;
-};
-
-static AucGeom auc_geom(long M) {
-    AucGeom g;
-    g.gx = ceil_div(M, AUC_TILE);
-    // at most 64 row-j chunks of >= 1024 rows; a block's per-class sum stays below 256 * 2 * chunk <= 2^31 (chunk <= 2^22 for M <= 2^24)
-    const long c = std::max(1024L, (long)ceil_div(M, 64));
-    g.chunk = (int)(((c + AUC_TILE - 1) / AUC_TILE) * AUC_TILE);
-    g.gy = ceil_div(M, g.chunk);
-    return g;
-}
-
+// The pairs are tiled by rank_geom (order_key.h).  The AUC takes up to 2^24 rows: a block's per-class sum stays below
+// 256 * 2 * chunk <= 2^31 (chunk <= 2^22 for M <= 2^24).
 // workspace: int32 pair sums [gy][gx][K] | int32 row stats [gx][K + 2] (positives per class, NaN rows, labels >= K)
 __global__ __launch_bounds__(256) void roc_auc_count_kernel(const float* __restrict__ probs, const int32_t* __restrict__ labels, long M,
-                                                            int K, AucGeom g, int32_t* __restrict__ pair, int32_t* __restrict__ rstat) {
-    __shared__ float s_tile[AUC_MAX_K * AUC_TILE];  // [k][t]: a wave reads one t at up to K addresses
+                                                            int K, RankGeom g, int32_t* __restrict__ pair, int32_t* __restrict__ rstat) {
+    __shared__ float s_tile[EVAL_MAX_K * AUC_TILE];  // [k][t]: a wave reads one t at up to K addresses
     __shared__ int32_t l_tile[AUC_TILE];
-    __shared__ int32_t acc[AUC_MAX_K + 2];  // row stats of this block's rows i
-    __shared__ int32_t pk[AUC_MAX_K];       // pair sums per class
+    __shared__ int32_t acc[EVAL_MAX_K + 2];  // row stats of this block's rows i
+    __shared__ int32_t pk[EVAL_MAX_K];       // pair sums per class
     const int tid = threadIdx.x;
     const long i = (long)blockIdx.x * AUC_TILE + tid;
     int L = -1;
@@ -209,10 +187,10 @@ __device__ __forceinline__ double auc_div_rn(double a, double b) {
 }
 
 __global__ __launch_bounds__(256) void roc_auc_finish_kernel(const int32_t* __restrict__ pair, const int32_t* __restrict__ rstat, int K,
-                                                             AucGeom g, double* __restrict__ auc, double* __restrict__ auc_k) {
+                                                             RankGeom g, double* __restrict__ auc, double* __restrict__ auc_k) {
 #pragma clang fp contract(off)  // every product rounded on its own, as numpy computes the weighted mean (the HIP default contracts)
     __shared__ long long red[4];
-    __shared__ long long tot[2 * AUC_MAX_K + 2];  // U2 per class | positives per class | NaN rows | bad labels
+    __shared__ long long tot[2 * EVAL_MAX_K + 2];  // U2 per class | positives per class | NaN rows | bad labels
     const int tid = threadIdx.x;
     const long slots = (long)g.gx * g.gy;
     for (int e = 0; e < 2 * K + 2; ++e) {
@@ -223,11 +201,8 @@ __global__ __launch_bounds__(256) void roc_auc_finish_kernel(const int32_t* __re
             const int c = e - K;  // column of the row stats
             for (long b = tid; b < g.gx; b += 256) s += rstat[b * (K + 2) + c];
         }
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = s;
-        __syncthreads();
-        if (tid == 0) tot[e] = red[0] + red[1] + red[2] + red[3];
+        s = block_sum_i64(s, red);
+        if (tid == 0) tot[e] = s;
     }
     __syncthreads();
     if (tid != 0) return;
@@ -278,17 +253,17 @@ extern "C" int pasn_eval_batch_stats(const float* logits, const float* sim, cons
 
 extern "C" size_t pasn_roc_auc_workspace_bytes(long M, int K_real) {
     if (M <= 0 || K_real <= 0) return 0;
-    const AucGeom g = auc_geom(M);
+    const RankGeom g = rank_geom(M);
     return ((size_t)g.gy * g.gx * K_real + (size_t)g.gx * (K_real + 2)) * sizeof(int32_t);
 }
 
 extern "C" int pasn_roc_auc_ovr(const float* probs, const int32_t* labels, long M, int K_real, double* auc, double* auc_per_class,
                                 void* workspace, void* stream) {
     PASN_REQUIRE(probs && labels && auc && auc_per_class && workspace, "probs, labels, auc, auc_per_class and workspace are required");
-    PASN_REQUIRE(K_real >= 2 && K_real <= AUC_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
     PASN_REQUIRE(M >= 1 && M <= (1L << 24), "M must lie in [1, 2^24]");
     PASN_REQUIRE(((uintptr_t)workspace & 3) == 0, "misaligned workspace");
-    const AucGeom g = auc_geom(M);
+    const RankGeom g = rank_geom(M);
     int32_t* pair = static_cast<int32_t*>(workspace);
     int32_t* rstat = pair + (size_t)g.gy * g.gx * K_real;
     hipStream_t s = (hipStream_t)stream;

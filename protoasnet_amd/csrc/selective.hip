@@ -2,8 +2,8 @@
 // curve (accuracy, balanced accuracy and mean F1 of the rows kept when the most uncertain ones are set aside).  The reference trains the
 // abstention class (src/loss/loss.py:323-371) and has no code that evaluates it; include/protoasnet_amd.h holds the definitions.
 //
-// pasn_uncertainty_scores: one thread per row, the expf / __fdiv_rn sequence of eval_batch_stats_kernel (eval_metrics.hip), so mode 0 is
-// bitwise 1.0f - the largest entry of the probs row that kernel stores.
+// pasn_uncertainty_scores: one thread per row, through softmax_max_sum_f32 (eval_common.h) as eval_batch_stats_kernel (eval_metrics.hip),
+// so mode 0 is bitwise 1.0f - the largest entry of the probs row that kernel stores.
 //
 // pasn_group_predictions: groups as CSR.  One launch, four groups per block.  A group of up to GP_WAVE_ROWS rows belongs to one wave:
 // lane k < K_real carries column k's two fp64 sums, every lane the two sums over u, and the wave walks the rows in the listed order.
@@ -12,26 +12,24 @@
 //
 // pasn_risk_coverage: five launches.
 //   1. rank: the position of valid row i under (u ascending, NaN last, lower index first) is the number of valid rows j before it,
-//      counted out of LDS tiles of 256 keys (the rank-by-counting of roc_auc_count_kernel).  u maps to a uint32 key that orders as the
-//      floats do (-0 = +0, NaN above +inf, padding above NaN); tiles are aligned to the 256 rows of a block, so every tile but the
-//      block's own lies wholly before or behind its rows and needs ONE comparison per pair (<= or <).  Integer atomics add the chunks'
-//      counts to rank[i]; the y = 0 blocks count the valid and the NaN rows.
+//      counted out of LDS tiles of 256 keys (rank_count_chunk of order_key.h, which bootstrap.hip calls too).  u maps to a uint32 key
+//      that orders as the floats do (-0 = +0, NaN above +inf, padding above NaN).  Integer atomics add the chunks' counts to rank[i];
+//      the y = 0 blocks count the valid and the NaN rows.
 //   2. scatter: order[rank] = i, threshold[rank] = u_i, cell[rank] = (label, first largest probability).
 //   3. histogram: per scan block of 1024 positions, the count of tp_k, support_k and predicted_k for every class.
 //   4. curve: a block's base is the sum of the histograms before it; a packed 3 x 20 bit scan per class gives every position its prefix
 //      counts, from which the three metrics follow in fp64 (confusion_to_metrics of trainer.py on a prefix).  All counts are integers:
-//      the order of arrival cannot matter.  The block also adds its (1 - acc) terms in a fixed tree.
-//   5. aurc: the blocks' partial sums in a fixed tree, over Mv.
+//      the order of arrival cannot matter.  The block also adds its (1 - acc) terms in a fixed tree (block_sum_fixed).
+//   5. aurc: the blocks' partial sums in the same tree, over Mv.
 #include "common.h"
-#include "order_key.h"  // rc_key, rank_count_tile (shared with bootstrap.hip)
+#include "eval_common.h"
 
 namespace pasn {
 
-constexpr int SEL_MAX_K = 16;
 constexpr int SEL_TILE = RANK_TILE;
-constexpr int GP_WAVE_ROWS = 64;   // larger groups get the block
-constexpr int RC_SCAN = 1024;      // positions per scan block: 4 per thread
-constexpr long RC_MAX_M = 1L << 20;
+constexpr int GP_WAVE_ROWS = 64;  // larger groups get the block
+constexpr int RC_SCAN = 1024;     // positions per scan block: 4 per thread
+constexpr ClassCell RC_CELL = {4, 0};  // cell = label * 16 + prediction
 
 // ---- uncertainty scores ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void uncertainty_scores_kernel(const float* __restrict__ logits, long M, int K, int K_real, int mode,
@@ -46,10 +44,8 @@ __global__ __launch_bounds__(256) void uncertainty_scores_kernel(const float* __
         return;
     }
     const int n = mode == 0 ? K_real : K;
-    float m = lg[0];
-    for (int k = 1; k < n; ++k) m = fmaxf(m, lg[k]);
-    float s = 0.0f;
-    for (int k = 0; k < n; ++k) s += expf(lg[k] - m);
+    float m;
+    const float s = softmax_max_sum_f32(lg, n, &m);
     if (mode == 1) {  // the abstention column of the joined softmax (loss.py:356)
         u[i] = __fdiv_rn(expf(lg[K - 1] - m), s);
         return;
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(256) void group_predictions_kernel(const float* __r
                                                                 double* __restrict__ p_conf, double* __restrict__ u_mean,
                                                                 int32_t* __restrict__ g_label, int32_t* __restrict__ g_count,
                                                                 int32_t* __restrict__ status) {
-    __shared__ float s_p[SEL_TILE * SEL_MAX_K];
+    __shared__ float s_p[SEL_TILE * EVAL_MAX_K];
     __shared__ float s_u[SEL_TILE];
     __shared__ int32_t s_lab[SEL_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -140,42 +136,29 @@ __global__ __launch_bounds__(256) void group_predictions_kernel(const float* __r
                 const long i = rows[lo + t0 + tid];
                 s_u[tid] = u[i];
                 s_lab[tid] = labels[i];
-                for (int k = 0; k < K; ++k) s_p[tid * SEL_MAX_K + k] = probs[i * K + k];
+                for (int k = 0; k < K; ++k) s_p[tid * EVAL_MAX_K + k] = probs[i * K + k];
             }
             __syncthreads();
             if (wave == 0)
-                for (int r = 0; r < nt; ++r) gp_add(a, s_u[r], s_p[r * SEL_MAX_K + kk], col, s_lab[r], lab0);
+                for (int r = 0; r < nt; ++r) gp_add(a, s_u[r], s_p[r * EVAL_MAX_K + kk], col, s_lab[r], lab0);
         }
         if (wave == 0) gp_store(a, g, n, lab0, K, lane, p_mean, p_conf, u_mean, g_label, g_count, status);
     }
 }
 
 // ---- risk-coverage -----------------------------------------------------------------------------------------------------------------------
-struct RcGeom {
-    int gx, gy, chunk, nb;  // row blocks, row-j chunks and their length (a multiple of the tile), scan blocks
-};
-
-static RcGeom rc_geom(long M) {
-    RcGeom g;
-    g.gx = ceil_div(M, SEL_TILE);
-    const long c = std::max(1024L, (long)ceil_div(M, 64));  // at most 64 chunks of >= 1024 rows
-    g.chunk = (int)(((c + SEL_TILE - 1) / SEL_TILE) * SEL_TILE);
-    g.gy = ceil_div(M, g.chunk);
-    g.nb = ceil_div(M, RC_SCAN);
-    return g;
-}
+static int rc_scan_blocks(long M) { return ceil_div(M, RC_SCAN); }
 
 __global__ __launch_bounds__(256) void rc_rank_kernel(const float* __restrict__ u, const int32_t* __restrict__ labels, long M, int K,
-                                                      RcGeom g, int32_t* __restrict__ rank, unsigned long long* __restrict__ counts) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_key[SEL_TILE];
+                                                      RankGeom g, int32_t* __restrict__ rank, unsigned long long* __restrict__ counts) {
     __shared__ int s_cnt[2];
     const int tid = threadIdx.x;
-    const long i0 = (long)blockIdx.x * SEL_TILE, i = i0 + tid;
-    uint32_t ki = RC_KEY_PAD;
-    if (i < M) {
-        const int L = labels[i];
-        if (L >= 0 && L < K) ki = rc_key(u[i]);
-    }
+    const long i = (long)blockIdx.x * RANK_TILE + tid;
+    const auto key = [&](long j) {  // a row with a label outside [0, K) never enters
+        const int L = labels[j];
+        return L >= 0 && L < K ? rc_key(u[j]) : RC_KEY_PAD;
+    };
+    const uint32_t ki = i < M ? key(i) : RC_KEY_PAD;
     const bool valid = ki != RC_KEY_PAD;
     if (blockIdx.y == 0) {
         if (tid < 2) s_cnt[tid] = 0;
@@ -188,23 +171,7 @@ __global__ __launch_bounds__(256) void rc_rank_kernel(const float* __restrict__ 
         __syncthreads();
         if (tid < 2 && s_cnt[tid]) atomicAdd(&counts[tid], (unsigned long long)s_cnt[tid]);
     }
-    int cnt = 0;
-    const long j0 = (long)blockIdx.y * g.chunk, j1 = min(M, j0 + (long)g.chunk);
-    for (long jt = j0; jt < j1; jt += SEL_TILE) {
-        __syncthreads();
-        {
-            const long j = jt + tid;
-            uint32_t kj = RC_KEY_PAD;
-            if (j < j1) {
-                const int L = labels[j];
-                if (L >= 0 && L < K) kj = rc_key(u[j]);
-            }
-            s_key[tid] = kj;  // the tail of a short tile is padding: it counts for nobody
-        }
-        __syncthreads();
-        if (!valid) continue;
-        cnt += rank_count_tile(s_key, ki, jt, i0, tid);
-    }
+    const int cnt = rank_count_chunk(key, ki, M, g.chunk);
     if (valid && cnt) atomicAdd(&rank[i], cnt);
 }
 
@@ -216,24 +183,18 @@ __global__ __launch_bounds__(256) void rc_scatter_kernel(const float* __restrict
     if (i >= M) return;
     const int L = labels[i];
     if (L < 0 || L >= K) return;
-    const float* p = probs + i * K;
-    int pred = 0;
-    float best = p[0];
-    for (int k = 1; k < K; ++k)
-        if (p[k] > best) {  // the first largest
-            best = p[k];
-            pred = k;
-        }
+    float best;
+    const int pred = first_largest(probs + i * K, K, &best);
     const int r = rank[i];  // < Mv <= M: the number of valid rows before this one
     order[r] = (int32_t)i;
     threshold[r] = u[i];
-    cell[r] = L * SEL_MAX_K + pred;
+    cell[r] = RC_CELL.pack(L, pred);
 }
 
 // hist [nb][3][K] int32: per scan block, tp_k | support_k | predicted_k
 __global__ __launch_bounds__(256) void rc_hist_kernel(const int32_t* __restrict__ cell, const unsigned long long* __restrict__ counts, int K,
                                                       int32_t* __restrict__ hist) {
-    __shared__ int32_t h[3 * SEL_MAX_K];
+    __shared__ int32_t h[3 * EVAL_MAX_K];
     const int tid = threadIdx.x;
     const long Mv = (long)counts[0];
     if (tid < 3 * K) h[tid] = 0;
@@ -241,7 +202,7 @@ __global__ __launch_bounds__(256) void rc_hist_kernel(const int32_t* __restrict_
     for (int q = 0; q < RC_SCAN / 256; ++q) {
         const long pos = (long)blockIdx.x * RC_SCAN + q * 256 + tid;
         if (pos < Mv) {
-            const int c = cell[pos], L = c / SEL_MAX_K, P = c % SEL_MAX_K;
+            const int c = cell[pos], L = RC_CELL.label(c), P = RC_CELL.pred(c);
             if (L == P) atomicAdd(&h[L], 1);
             atomicAdd(&h[K + L], 1);
             atomicAdd(&h[2 * K + P], 1);
@@ -256,7 +217,7 @@ __global__ __launch_bounds__(256) void rc_curve_kernel(const int32_t* __restrict
                                                        double* __restrict__ bal_acc, double* __restrict__ f1_mean,
                                                        double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    __shared__ int32_t base[3 * SEL_MAX_K];
+    __shared__ int32_t base[3 * EVAL_MAX_K];
     __shared__ unsigned long long wsum[4];
     __shared__ double red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -275,12 +236,10 @@ __global__ __launch_bounds__(256) void rc_curve_kernel(const int32_t* __restrict
     for (int q = 0; q < 4; ++q) {
         const bool in = p0 + q < Mv;
         const int c = in ? cell[p0 + q] : 0;
-        L[q] = in ? c / SEL_MAX_K : -1;
-        P[q] = in ? c % SEL_MAX_K : -1;
+        L[q] = in ? RC_CELL.label(c) : -1;
+        P[q] = in ? RC_CELL.pred(c) : -1;
     }
-    long trace[4] = {0, 0, 0, 0};
-    int present[4] = {0, 0, 0, 0};
-    double rsum[4] = {0.0, 0.0, 0.0, 0.0}, fsum[4] = {0.0, 0.0, 0.0, 0.0};
+    ClassTally tally[4];
     for (int k = 0; k < K; ++k) {
         // inclusive prefix of (tp_k, support_k, predicted_k) packed 20 bits each: a block holds 1024 positions
         unsigned long long loc[4], run = 0ull;
@@ -288,11 +247,7 @@ __global__ __launch_bounds__(256) void rc_curve_kernel(const int32_t* __restrict
             run += (unsigned long long)(L[q] == k && P[q] == k) | ((unsigned long long)(L[q] == k) << 20) | ((unsigned long long)(P[q] == k) << 40);
             loc[q] = run;
         }
-        unsigned long long inc = run;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
+        const unsigned long long inc = wave_scan_incl_u64(run);
         __syncthreads();  // wsum of the class before has been read; base is visible (k = 0)
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
@@ -302,28 +257,21 @@ __global__ __launch_bounds__(256) void rc_curve_kernel(const int32_t* __restrict
             const unsigned long long v = ex + loc[q];
             const long tp = base[k] + (long)(v & 0xFFFFFull), sup = base[K + k] + (long)((v >> 20) & 0xFFFFFull),
                        prd = base[2 * K + k] + (long)((v >> 40) & 0xFFFFFull);
-            trace[q] += tp;
-            if (sup > 0) {
-                rsum[q] += (double)tp / (double)sup;
-                ++present[q];
-            }
-            if (sup + prd > 0) fsum[q] += 2.0 * (double)tp / (double)(sup + prd);
+            tally[q].add(tp, sup, prd);
         }
     }
     double e = 0.0;
     for (int q = 0; q < 4; ++q) {
-        const long m = p0 + q + 1;
+        const long m = p0 + q + 1;  // the rows kept: >= 1
         if (m > Mv) break;
-        const double a = (double)trace[q] / (double)m;
+        const double a = tally[q].accuracy(m);
         acc[m - 1] = a;
-        bal_acc[m - 1] = present[q] > 0 ? rsum[q] / (double)present[q] : 0.0;
-        f1_mean[m - 1] = fsum[q] / (double)K;
+        bal_acc[m - 1] = tally[q].balanced_accuracy();
+        f1_mean[m - 1] = tally[q].f1_mean(K);
         e += 1.0 - a;
     }
-    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
-    if (lane == 0) red[wave] = e;
-    __syncthreads();
-    if (tid == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    e = block_sum_fixed(e, red);
+    if (tid == 0) partial[blockIdx.x] = e;
 }
 
 __global__ __launch_bounds__(256) void rc_aurc_kernel(const double* __restrict__ partial, int nb,
@@ -333,12 +281,10 @@ __global__ __launch_bounds__(256) void rc_aurc_kernel(const double* __restrict__
     const int tid = threadIdx.x;
     double s = 0.0;
     for (int b = tid; b < nb; b += 256) s += partial[b];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
+    s = block_sum_fixed(s, red);
     if (tid == 0) {
         const long Mv = (long)counts[0];
-        aurc[0] = Mv > 0 ? ((red[0] + red[1]) + (red[2] + red[3])) / (double)Mv : __builtin_nan("");
+        aurc[0] = Mv > 0 ? s / (double)Mv : __builtin_nan("");
     }
 }
 
@@ -348,18 +294,15 @@ struct RcWorkspace {
     size_t bytes;
 };
 
-static RcWorkspace rc_workspace(void* ws, long M, int K, const RcGeom& g) {
+static RcWorkspace rc_workspace(void* ws, long M, int K) {
     RcWorkspace w;
-    char* p = static_cast<char*>(ws);
-    w.partial = reinterpret_cast<double*>(p);
-    p += (size_t)g.nb * sizeof(double);
-    w.rank = reinterpret_cast<int32_t*>(p);
-    p += (size_t)M * sizeof(int32_t);
-    w.cell = reinterpret_cast<int32_t*>(p);
-    p += (size_t)M * sizeof(int32_t);
-    w.hist = reinterpret_cast<int32_t*>(p);
-    p += (size_t)g.nb * 3 * K * sizeof(int32_t);
-    w.bytes = (size_t)(p - static_cast<char*>(ws));
+    Carve c{static_cast<char*>(ws)};
+    const size_t nb = (size_t)rc_scan_blocks(M);
+    w.partial = c.take<double>(nb);
+    w.rank = c.take<int32_t>((size_t)M);
+    w.cell = c.take<int32_t>((size_t)M);
+    w.hist = c.take<int32_t>(nb * 3 * K);
+    w.bytes = c.used;
     return w;
 }
 
@@ -370,8 +313,8 @@ using namespace pasn;
 extern "C" int pasn_uncertainty_scores(const float* logits, long M, int K, int K_real, int mode, float* u, void* stream) {
     PASN_REQUIRE(logits && u, "logits and u are required");
     PASN_REQUIRE(M >= 1, "M must be positive");
-    PASN_REQUIRE(K_real >= 2 && K_real <= SEL_MAX_K, "K_real must lie in [2, 16]");
-    PASN_REQUIRE(K >= K_real && K <= SEL_MAX_K + 1, "K must lie in [K_real, 17]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(K >= K_real && K <= EVAL_MAX_K + 1, "K must lie in [K_real, 17]");
     PASN_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (maxprob), 1 (alpha, joined) or 2 (alpha, separate)");
     PASN_REQUIRE(mode != 1 || K == K_real + 1, "mode 1 (alpha, joined) needs K == K_real + 1");
     PASN_REQUIRE(mode != 2 || K > K_real, "mode 2 (alpha, separate) needs an abstention column: K > K_real");
@@ -385,7 +328,7 @@ extern "C" int pasn_group_predictions(const float* probs, const float* u, const 
     PASN_REQUIRE(probs && u && labels && group_offsets && group_rows, "probs, u, labels, group_offsets and group_rows are required");
     PASN_REQUIRE(p_mean && p_conf && u_mean && g_label && g_count && status, "every output is required");
     PASN_REQUIRE(G >= 1, "G must be positive");
-    PASN_REQUIRE(K_real >= 2 && K_real <= SEL_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(status, 0, 2 * sizeof(int32_t), s) != hipSuccess) return check_launch("group_predictions (status)");
     hipLaunchKernelGGL(group_predictions_kernel, dim3(ceil_div(G, 4)), dim3(256), 0, s, probs, u, labels, group_offsets, group_rows, G, K_real,
@@ -394,8 +337,8 @@ extern "C" int pasn_group_predictions(const float* probs, const float* u, const 
 }
 
 extern "C" size_t pasn_risk_coverage_workspace_bytes(long M, int K_real) {
-    if (M <= 0 || M > RC_MAX_M || K_real < 2 || K_real > SEL_MAX_K) return 0;
-    return rc_workspace(nullptr, M, K_real, rc_geom(M)).bytes;
+    if (M <= 0 || M > EVAL_MAX_ROWS || K_real < 2 || K_real > EVAL_MAX_K) return 0;
+    return rc_workspace(nullptr, M, K_real).bytes;
 }
 
 extern "C" int pasn_risk_coverage(const float* probs, const int32_t* labels, const float* u, long M, int K_real, int32_t* order, double* acc,
@@ -404,19 +347,20 @@ extern "C" int pasn_risk_coverage(const float* probs, const int32_t* labels, con
     PASN_REQUIRE(probs && labels && u, "probs, labels and u are required");
     PASN_REQUIRE(order && acc && bal_acc && f1_mean && threshold && aurc && counts, "every output is required");
     PASN_REQUIRE(workspace, "workspace is required");
-    PASN_REQUIRE(K_real >= 2 && K_real <= SEL_MAX_K, "K_real must lie in [2, 16]");
-    PASN_REQUIRE(M >= 1 && M <= RC_MAX_M, "M must lie in [1, 2^20]");
+    PASN_REQUIRE(K_real >= 2 && K_real <= EVAL_MAX_K, "K_real must lie in [2, 16]");
+    PASN_REQUIRE(M >= 1 && M <= EVAL_MAX_ROWS, "M must lie in [1, 2^20]");
     PASN_REQUIRE(((uintptr_t)workspace & 7) == 0, "misaligned workspace");
-    const RcGeom g = rc_geom(M);
-    const RcWorkspace w = rc_workspace(workspace, M, K_real, g);
+    const RankGeom g = rank_geom(M);
+    const int nb = rc_scan_blocks(M);
+    const RcWorkspace w = rc_workspace(workspace, M, K_real);
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
     if (hipMemsetAsync(w.rank, 0, (size_t)M * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s) != hipSuccess)
         return check_launch("risk_coverage (zeroing)");
     hipLaunchKernelGGL(rc_rank_kernel, dim3(g.gx, g.gy), dim3(256), 0, s, u, labels, M, K_real, g, w.rank, cnt);
     hipLaunchKernelGGL(rc_scatter_kernel, dim3(g.gx), dim3(256), 0, s, probs, labels, u, M, K_real, w.rank, order, threshold, w.cell);
-    hipLaunchKernelGGL(rc_hist_kernel, dim3(g.nb), dim3(256), 0, s, w.cell, cnt, K_real, w.hist);
-    hipLaunchKernelGGL(rc_curve_kernel, dim3(g.nb), dim3(256), 0, s, w.cell, cnt, K_real, w.hist, acc, bal_acc, f1_mean, w.partial);
-    hipLaunchKernelGGL(rc_aurc_kernel, dim3(1), dim3(256), 0, s, w.partial, g.nb, cnt, aurc);
+    hipLaunchKernelGGL(rc_hist_kernel, dim3(nb), dim3(256), 0, s, w.cell, cnt, K_real, w.hist);
+    hipLaunchKernelGGL(rc_curve_kernel, dim3(nb), dim3(256), 0, s, w.cell, cnt, K_real, w.hist, acc, bal_acc, f1_mean, w.partial);
+    hipLaunchKernelGGL(rc_aurc_kernel, dim3(1), dim3(256), 0, s, w.partial, nb, cnt, aurc);
     return check_launch("risk_coverage");
 }

@@ -31,6 +31,8 @@ from . import _lib
 CLASS_LABELS = ["No AS", "Early AS", "Significant AS"]  # src/data/as_dataloader.py: class_labels
 OPTIONAL_LOG_KEYS = ("interval_idx", "window_start", "window_end", "original_length")  # base.py:203-206
 MAX_PROTOTYPES = 4096  # pasn_eval_batch_stats: larger P is PASN_ERR_UNSUPPORTED
+# csrc/eval_common.h: the limits selective.py, bootstrap.py and calibration.py share (a rank by counting; 4-bit class fields)
+MAX_ROWS, MAX_K, MAX_REPLICATES = 1 << 20, 16, 65536
 
 
 def _require_cuda(*ts) -> None:
@@ -119,7 +121,7 @@ def roc_auc_ovr_weighted(probs: torch.Tensor, labels: torch.Tensor, num_classes:
     auc = torch.zeros(1, dtype=torch.float64, device=probs.device)
     auc_k = torch.full((num_classes,), float("nan"), dtype=torch.float64, device=probs.device)
     if M > 0:
-        ws = torch.empty(int(_lib.lib().pasn_roc_auc_workspace_bytes(M, num_classes)) // 4 + 1, dtype=torch.int32, device=probs.device)
+        ws = _lib.workspace(_lib.lib().pasn_roc_auc_workspace_bytes(M, num_classes), probs.device)
         _lib.check(_lib.lib().pasn_roc_auc_ovr(_lib.ptr(_f32(probs)), _lib.ptr(labels.to(torch.int32).contiguous()), M, num_classes,
                                                _lib.ptr(auc), _lib.ptr(auc_k), _lib.ptr(ws), _lib.current_stream()))
     return (auc[0], auc_k) if per_class else auc[0]

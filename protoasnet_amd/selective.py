@@ -27,10 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .metrics import EpochEvaluator, _f32, _require_cuda, roc_auc_ovr_weighted
+from .metrics import MAX_ROWS, EpochEvaluator, _f32, _require_cuda, roc_auc_ovr_weighted
 
 MAXPROB, ALPHA_JOINED, ALPHA_SEPARATE = 0, 1, 2  # the modes of pasn_uncertainty_scores
-MAX_ROWS = 1 << 20  # pasn_risk_coverage: a rank by counting
 DEFAULT_COVERAGES = (1.0, 0.9, 0.8, 0.7, 0.5)
 
 
@@ -80,6 +79,26 @@ def build_groups(keys: Sequence) -> Tuple[np.ndarray, np.ndarray, list]:
     return offsets, rows, list(index)
 
 
+def check_groups(groups, M: int, exclusive: bool = False) -> Tuple[np.ndarray, np.ndarray, int]:
+    """``build_groups``' tuple (or its first two arrays) checked on the host against ``M`` rows -- the kernels do not check, and these
+    indices address device memory.  Returns the contiguous ``(offsets int64, rows int32, G)``.  ``exclusive=True``: the groups are
+    resampling units (``bootstrap.py``, ``calibration.py``), so no more groups than rows and a row in one group only."""
+    offsets = np.ascontiguousarray(groups[0], dtype=np.int64)
+    rows = np.ascontiguousarray(groups[1], dtype=np.int32)
+    G = offsets.size - 1
+    if G < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
+        raise ValueError("group offsets must start at 0, not decrease and end at the number of listed rows")
+    if exclusive and G > M:
+        raise ValueError(f"{G} groups for {M} rows")
+    if rows.size and (rows.min() < 0 or rows.max() >= M):
+        raise ValueError(f"group rows must lie in [0, {M})")
+    if exclusive and rows.size and np.bincount(rows, minlength=M).max() > 1:
+        raise ValueError("a row may be listed in one group only")
+    if exclusive and G * int(np.diff(offsets).max()) >= 1 << 31:  # the expanded rows of a replicate are counted in 32 bits
+        raise ValueError("G times the largest group must stay below 2^31")
+    return offsets, rows, G
+
+
 class GroupPredictions:
     """Device results of ``group_predictions``: ``p_mean`` / ``p_conf`` (G, K_real) fp64, ``u_mean`` (G,) fp64, ``labels`` / ``counts``
     (G,) int32, ``status`` (2,) int32 = {groups whose rows disagree on the label, rows holding a NaN}."""
@@ -105,13 +124,7 @@ def group_predictions(probs: torch.Tensor, u: torch.Tensor, labels: torch.Tensor
     if probs.dim() != 2 or u.shape != probs.shape[:1] or labels.shape != probs.shape[:1]:
         raise ValueError("probs must be (M, K_real), u and labels (M,)")
     M, K_real = probs.shape
-    offsets = np.ascontiguousarray(groups[0], dtype=np.int64)
-    rows = np.ascontiguousarray(groups[1], dtype=np.int32)
-    G = offsets.size - 1
-    if G < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
-        raise ValueError("group offsets must start at 0, not decrease and end at the number of listed rows")
-    if rows.size and (rows.min() < 0 or rows.max() >= M):  # the kernel does not check: these indices address device memory
-        raise ValueError(f"group rows must lie in [0, {M})")
+    offsets, rows, G = check_groups(groups, M)
     dev = probs.device
     d_off, d_rows = torch.from_numpy(offsets).to(dev), torch.from_numpy(rows).to(dev)
     p_mean, p_conf = torch.empty(G, K_real, dtype=torch.float64, device=dev), torch.empty(G, K_real, dtype=torch.float64, device=dev)
@@ -199,7 +212,7 @@ def risk_coverage(probs: torch.Tensor, labels: torch.Tensor, u: torch.Tensor) ->
     threshold = torch.empty(M, dtype=torch.float32, device=dev)
     aurc = torch.empty(1, dtype=torch.float64, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    ws = torch.empty(int(_lib.lib().pasn_risk_coverage_workspace_bytes(M, K_real)) // 8 + 1, dtype=torch.float64, device=dev)
+    ws = _lib.workspace(_lib.lib().pasn_risk_coverage_workspace_bytes(M, K_real), dev)
     _lib.check(_lib.lib().pasn_risk_coverage(_lib.ptr(probs), _lib.ptr(labels), _lib.ptr(u), M, K_real, _lib.ptr(order), _lib.ptr(curves[0]),
                                              _lib.ptr(curves[1]), _lib.ptr(curves[2]), _lib.ptr(threshold), _lib.ptr(aurc), _lib.ptr(counts),
                                              _lib.ptr(ws), _lib.current_stream()))
