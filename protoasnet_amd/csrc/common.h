@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <string>
+#include <type_traits>
 
 #include "../../include/protoasnet_amd.h"
 #include "tuning.h"
@@ -27,15 +28,31 @@ namespace pasn {
 // ---- host-side error plumbing -------------------------------------------------------------------
 void set_error(const std::string& msg);
 int check_launch(const char* what);
-#define PASN_REQUIRE(cond, msg)                                        \
-    do {                                                               \
-        if (!(cond)) {                                                 \
-            ::pasn::set_error(std::string(__func__) + ": " + (msg));   \
-            return PASN_ERR_ARG;                                       \
-        }                                                              \
+// (fn: the entry point the message names -- a helper that checks on behalf of its caller passes the caller's __func__ on)
+#define PASN_REQUIRE_AS(fn, cond, msg)                           \
+    do {                                                         \
+        if (!(cond)) {                                           \
+            ::pasn::set_error(std::string(fn) + ": " + (msg));   \
+            return PASN_ERR_ARG;                                 \
+        }                                                        \
     } while (0)
+#define PASN_REQUIRE(cond, msg) PASN_REQUIRE_AS(__func__, cond, msg)
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// f((T*)nullptr) with T the element type of `dtype`; in f: `using T = elem_t<decltype(tag)>`
+template <typename F>
+static void with_dtype(int dtype, F f) {
+    if (dtype == PASN_BF16) f((__bf16*)nullptr);
+    else f((float*)nullptr);
+}
+template <typename P>
+using elem_t = std::remove_pointer_t<P>;
+// one launch of 256-thread blocks
+template <typename K, typename... A>
+static void launch256(K kernel, dim3 grid, size_t lds, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, args...);
+}
 
 // Raise a kernel instance's dynamic-LDS limit once per (call site, DEVICE).  hipFuncAttributeMaxDynamicSharedMemorySize is a per-device
 // attribute: a process-wide "done" flag left every launch needing > 64 KB failing on a second GPU driven by the same process.  The

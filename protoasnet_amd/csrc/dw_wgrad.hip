@@ -191,20 +191,6 @@ __global__ __launch_bounds__(256) void dw_dgrad_s2_kernel(const T* __restrict__ 
     }
 }
 
-// f((T*)nullptr) with T the element type of `dtype`; in f: `using T = elem_t<decltype(tag)>`
-template <typename F>
-static void with_dtype(int dtype, F f) {
-    if (dtype == PASN_BF16) f((__bf16*)nullptr);
-    else f((float*)nullptr);
-}
-template <typename P>
-using elem_t = std::remove_pointer_t<P>;
-// one launch of 256-thread blocks
-template <typename K, typename... A>
-static void launch256(K kernel, dim3 grid, size_t lds, hipStream_t s, A... args) {
-    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, args...);
-}
-
 extern "C" int pasn_dwconv3d_dgrad(const void* dy, const float* w, void* dx, const pasn_conv_desc* d, int dtype, void* stream) {
     PASN_REQUIRE(dy && w && dx && d, "null pointer");
     PASN_REQUIRE(d->Cin_p == d->Cout_p && d->Cin_p % 8 == 0, "depthwise conv keeps the channel stride");

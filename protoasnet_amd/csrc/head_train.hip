@@ -223,12 +223,10 @@ extern "C" int pasn_xproto_tail_fwd(const void* z, const void* r, const float* p
     PASN_REQUIRE(d->Dp % 8 == 0 && d->Pp % 8 == 0 && d->P <= 256 && d->P <= d->Pp && d->D <= d->Dp, "bad head extents (P <= 256)");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(d->N, d->Pp / 8);
-    if (dtype == PASN_BF16)
-        hipLaunchKernelGGL(xproto_pool_fwd_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)z, (const __bf16*)r, occ, feat, d->S, d->D, d->Dp,
-                           d->P, d->Pp);
-    else
-        hipLaunchKernelGGL(xproto_pool_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)z, (const float*)r, occ, feat, d->S, d->D, d->Dp, d->P,
-                           d->Pp);
+    with_dtype(dtype, [&](auto tag) {
+        using T = elem_t<decltype(tag)>;
+        launch256(xproto_pool_fwd_kernel<T>, grid, 0, s, (const T*)z, (const T*)r, occ, feat, d->S, d->D, d->Dp, d->P, d->Pp);
+    });
     if (z) hipLaunchKernelGGL(xproto_tail_fwd_kernel, dim3(d->N), dim3(256), 0, s, feat, protos, fc_w, sim, logits, d->D, d->P, d->K);
     return check_launch("xproto_tail_fwd");
 }
@@ -272,12 +270,10 @@ extern "C" int pasn_xproto_tail_bwd(const void* z, const void* r, const float* p
         hipLaunchKernelGGL(xproto_tail_bwd_kernel, dim3(d->P), dim3(256), 0, s, feat, protos, fc_w, sim, dlogits, dsim, dfeat, dprotos, dfc_w, d->N, d->D,
                        d->P, d->K);
     const dim3 grid(d->N, ceil_div(d->S, PB_ROWS));
-    if (dtype == PASN_BF16)
-        hipLaunchKernelGGL(xproto_pool_bwd_kernel<__bf16>, grid, dim3(256), lds, s, (const __bf16*)z, (const __bf16*)r, dfeat, docc, (__bf16*)dz,
-                           (__bf16*)dr, d->S, d->D, d->Dp, d->P, d->Pp);
-    else
-        hipLaunchKernelGGL(xproto_pool_bwd_kernel<float>, grid, dim3(256), lds, s, (const float*)z, (const float*)r, dfeat, docc, (float*)dz,
-                           (float*)dr, d->S, d->D, d->Dp, d->P, d->Pp);
+    with_dtype(dtype, [&](auto tag) {
+        using T = elem_t<decltype(tag)>;
+        launch256(xproto_pool_bwd_kernel<T>, grid, lds, s, (const T*)z, (const T*)r, dfeat, docc, (T*)dz, (T*)dr, d->S, d->D, d->Dp, d->P, d->Pp);
+    });
     return check_launch("xproto_tail_bwd");
 }
 
@@ -349,16 +345,11 @@ extern "C" int pasn_l2_head_bwd(const void* z, const float* protos, const float*
     PASN_REQUIRE(N > 0 && S > 0 && D > 0 && P > 0 && K > 0 && Dp >= D && Dp % 8 == 0, "bad head extents");
     PASN_REQUIRE(activation == 0 || activation == 1, "activation must be 0 (log) or 1 (linear)");
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PASN_BF16) {
-        hipLaunchKernelGGL(l2_head_bwd_z_kernel<__bf16>, dim3(N), dim3(256), 0, s, (const __bf16*)z, protos, fc_w, min_dist, argmin, dlogits, dmin,
-                           (__bf16*)dz, coef, S, D, Dp, P, K, activation, eps);
-        hipLaunchKernelGGL(l2_head_bwd_p_kernel<__bf16>, dim3(P), dim3(256), 0, s, (const __bf16*)z, protos, min_dist, argmin, dlogits, coef, dprotos,
-                           dfc_w, N, S, D, Dp, P, K, activation, eps);
-    } else {
-        hipLaunchKernelGGL(l2_head_bwd_z_kernel<float>, dim3(N), dim3(256), 0, s, (const float*)z, protos, fc_w, min_dist, argmin, dlogits, dmin,
-                           (float*)dz, coef, S, D, Dp, P, K, activation, eps);
-        hipLaunchKernelGGL(l2_head_bwd_p_kernel<float>, dim3(P), dim3(256), 0, s, (const float*)z, protos, min_dist, argmin, dlogits, coef, dprotos, dfc_w,
-                           N, S, D, Dp, P, K, activation, eps);
-    }
+    with_dtype(dtype, [&](auto tag) {
+        using T = elem_t<decltype(tag)>;
+        launch256(l2_head_bwd_z_kernel<T>, dim3(N), 0, s, (const T*)z, protos, fc_w, min_dist, argmin, dlogits, dmin, (T*)dz, coef, S, D, Dp, P, K, activation, eps);
+        launch256(l2_head_bwd_p_kernel<T>, dim3(P), 0, s, (const T*)z, protos, min_dist, argmin, dlogits, coef, dprotos, dfc_w, N, S, D, Dp, P, K,
+                  activation, eps);
+    });
     return check_launch("l2_head_bwd");
 }

@@ -92,8 +92,10 @@ extern "C" int pasn_affine_warp_fwd(const void* x, void* y, long planes, int H, 
     const int blocks = (int)std::min<long>((total + 255) / 256, 1 << 20);
     const WarpGeom g = warp_geom(angle_deg, scale);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PASN_BF16) hipLaunchKernelGGL(affine_warp_fwd_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)x, (__bf16*)y, planes, H, W, g);
-    else hipLaunchKernelGGL(affine_warp_fwd_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)x, (float*)y, planes, H, W, g);
+    with_dtype(dtype, [&](auto tag) {
+        using T = elem_t<decltype(tag)>;
+        launch256(affine_warp_fwd_kernel<T>, dim3(blocks), 0, s, (const T*)x, (T*)y, planes, H, W, g);
+    });
     return check_launch("affine_warp_fwd");
 }
 

@@ -66,7 +66,7 @@ def _variants(cases, ids):
             for case, cid in zip(cases, ids) for dtype, dname in ((FP32, "fp32"), (BF, "bf16")) for contig, lname in ((False, "default"), (True, "rows-contig"))]
 
 
-UNIT_IDS = ["54-shape0-0.0", "24-shape1-300.0", "432-shape2--5.0", "432-2x3x7x7", "54-3x3x21x19", "24-2x3x31x31"]
+UNIT_IDS = ["54-shape0-0.0", "24-shape1-300.0", "432-shape2--5.0", "24-2x1x5x5", "432-2x3x7x7", "54-3x3x21x19", "24-2x3x31x31"]
 GROUP_IDS = ["54-shape0-2", "24-shape1-3", "216-shape2-2", "54-4x3x21x19-2"]
 SE_IDS = ["54-8-2x5x6", "432-32-3x7x7", "54-8-3x21x19"]
 

@@ -43,10 +43,11 @@ def row_geom(n, s, cp, contig=False, blocks=1024):
     return dict(CG=cg, LPR=lpr, RL=rl, chunks=chunks, rows_per_chunk=rpc, live_threads=rl * lpr)
 
 
-# (c, (n, t, h, w), offset): the first three are the single-chunk cases the suite has always had
-UNIT_CASES = [(54, (3, 4, 9, 7), 0.0), (24, (2, 3, 16, 16), 300.0), (432, (2, 2, 3, 3), -5.0),
+# (c, (n, t, h, w), offset): the first three are the single-chunk cases the suite has always had; the fourth has fewer rows in a clip
+# (S = 25) than a block has row lanes (64, or 85 with PASN_TRAIN_ROWS_CONTIG): most threads never load a row and still join the block reduce
+UNIT_CASES = [(54, (3, 4, 9, 7), 0.0), (24, (2, 3, 16, 16), 300.0), (432, (2, 2, 3, 3), -5.0), (24, (2, 1, 5, 5), 0.0),
               (432, (2, 3, 7, 7), 0.0), (54, (3, 3, 21, 19), 0.0), (24, (2, 3, 31, 31), 0.0)]
-UNIT_MULTI_CHUNK = UNIT_CASES[3:]
+UNIT_MULTI_CHUNK = UNIT_CASES[4:]
 # (c, (n, t, h, w), groups)
 GROUP_CASES = [(54, (4, 3, 9, 7), 2), (24, (6, 2, 8, 8), 3), (216, (2, 2, 5, 4), 2), (54, (4, 3, 21, 19), 2)]
 GROUP_MULTI_CHUNK = GROUP_CASES[3:]
