@@ -821,6 +821,54 @@ size_t pasn_temperature_workspace_bytes(long M, int K_real);
 int pasn_temperature_fit(const float* logits, const int32_t* labels, long M, int K, int K_real, double* fit, void* workspace, void* stream);
 int pasn_temperature_probs(const float* logits, long M, int K, int K_real, const double* beta, float* probs, float* u, void* stream);
 
+/* Explanation faithfulness (faithfulness.py): deletion and insertion curves.  Do the voxels an occurrence map marks carry the prototype
+ * similarity and the class probability?  The clip's voxels are removed (deletion) or inserted into a baseline (insertion) in the order of
+ * the map, a step at a time, and the model is run on every perturbed copy.  The reference has no code for it; these definitions are the
+ * specification.  Every call is stream-ordered: no host synchronisation, no global atomics, no block waiting on another.
+ *
+ * pasn_perturb_steps: when does a voxel change sides?  maps [M][V] uint8 (M = N k maps of V = To Ho Wo voxels, pasn_explain_maps' uint8
+ * output), counts [S1] int32 in DEVICE memory, non-decreasing, 0 <= counts[s] <= V (anything else: unspecified steps, no out-of-bounds
+ * access).  The voxels of one map are ordered by (level DESCENDING, flat index ASCENDING); pos(v) in [0, V) is a voxel's position.
+ *   steps [M][V] uint8: steps[v] = the number of s with counts[s] <= pos(v): the first step whose top set {pos < counts[s]} holds the
+ *   voxel, S1 when none does.  For every s exactly counts[s] voxels have steps <= s.
+ * Integers only: the output is exact and does not depend on the launch geometry.  Three launches: 256-bin histograms of 4096-voxel tiles
+ * (in LDS, then in the workspace); per map the level totals, the step of every level whose voxels share one, the at most S1 levels that
+ * straddle a count and their exclusive prefixes across the tiles; the write pass, in which a straddling level's voxels get their rank
+ * inside the tile from a block scan.  Rows are not 16-byte aligned when V is odd: the tiles are laid on the 16-byte grid of the row's
+ * address, whole 16-byte words are loaded and stored, a row's head and tail go byte by byte.  maps and steps 16-byte aligned;
+ * `workspace`: pasn_perturb_steps_workspace_bytes(M, V, S1) bytes, 16-byte aligned, no initialisation.
+ * 1 <= M <= 65 535, 1 <= V < 2^31, 1 <= S1 <= 64; anything else, or a NULL pointer, returns PASN_ERR_ARG before any launch (the size
+ * query returns 0).
+ *
+ * pasn_perturb_apply: the perturbed clips of a chunk of steps.  x [N][C][V] (dtype PASN_F32 / PASN_BF16), steps [N][k][V] as above,
+ * step_ids [Sc] int32 in DEVICE memory (any subset of the steps, any order), baseline [N][C][V] of the same dtype or NULL (then every
+ * baseline element is `fill`, rounded to the dtype once, to nearest even).  mode 0 (deletion): out = steps[v] <= s ? baseline : x;
+ * mode 1 (insertion): out = steps[v] <= s ? x : baseline, s = step_ids[.].
+ *   out [N][k][Sc][C][V]: a bitwise copy of the element selected.  Deletion at a step with counts[s] = 0 is x, at counts[s] = V the baseline.
+ * One launch; a block owns 4096 voxels of one (n, j, s), reads their steps once into an LDS mask and walks the C channels.  16-byte
+ * stores wherever the output address allows (a row's head and tail element by element), 16-byte loads where the input addresses allow.
+ * 1 <= N k Sc <= 2^31 - 1 blocks along two grid axes (N k <= 65 535, Sc <= 65 535), 1 <= C <= 64, 1 <= V < 2^31.
+ *
+ * pasn_perturb_curves: one launch, one block, after the model has run on the perturbed batch in [n][j][s] order with ALL S1 steps,
+ * B = N k S1 rows: sim [B][P] fp32 (1 - proto_dist), logits [B][K] fp32; sel [N][k] int32 (the prototype of map j), cls [N] int32 (the
+ * class whose probability is followed, normally the prediction on the clean clip), counts [S1] int32 as above.
+ *   curve_sim  [N][k][S1] fp32: sim[b][sel[n][j]], a copy
+ *   curve_prob [N][k][S1] fp32: softmax(logits[b][0 .. K_real))[cls[n]]: the largest logit subtracted, expf, the sum in column order,
+ *                               one IEEE division, all fp32
+ *   auc [N][k][2] fp64 (similarity, probability): sum_{s >= 1} (x_s - x_{s-1}) (y_s + y_{s-1}) / 2 with x_s = (double)counts[s] / V and
+ *                               y the fp32 curve value widened, s ascending, every operation rounded on its own
+ *   acc [2 k S1 + 2 k + 1] fp64 or NULL, the caller's running sums over the clips of a sweep (zeroed by the caller):
+ *                               += sum_n curve_sim [k][S1], += sum_n curve_prob [k][S1], += sum_n auc [k][2], += N; n ascending
+ * An entry of sel outside [0, P) or of cls outside [0, K_real) gives NaN curves for that clip, nothing is read out of bounds.
+ * 1 <= N k S1 <= 2^20, 1 <= S1 <= 64, 1 <= K_real <= 16, K_real <= K <= 17, P >= 1, 1 <= V < 2^31. */
+size_t pasn_perturb_steps_workspace_bytes(long M, long V, int S1);
+int pasn_perturb_steps(const uint8_t* maps, const int32_t* counts, long M, long V, int S1, uint8_t* steps, void* workspace, void* stream);
+int pasn_perturb_apply(const void* x, const uint8_t* steps, const int32_t* step_ids, const void* baseline, float fill, int N, int C, int k,
+                       long V, int Sc, int mode, int dtype, void* out, void* stream);
+int pasn_perturb_curves(const float* sim, const float* logits, const int32_t* sel, const int32_t* cls, const int32_t* counts, int N, int k,
+                        int S1, int P, int K, int K_real, long V, float* curve_sim, float* curve_prob, double* auc, double* acc,
+                        void* stream);
+
 /* Global explanations: the k nearest clips of a split per prototype, kept on the device while a loader is swept (global_explain.py).
  * The reference ships only the raw material, the whole (clips, P) similarity matrix "for ranking prototypes"
  * (XProtoNet_Base.py:613-656 get_sim_scores / load_sim_scores; explain_global is a stub); the selection rule per batch is the push's

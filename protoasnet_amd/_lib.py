@@ -176,6 +176,11 @@ SIGNATURES = {
     "pasn_temperature_workspace_bytes": (c_size_t, [c_long, c_int]),
     "pasn_temperature_fit": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "pasn_temperature_probs": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ---- explanation faithfulness: deletion / insertion curves (faithfulness.py)
+    "pasn_perturb_steps_workspace_bytes": (c_size_t, [c_long, c_long, c_int]),
+    "pasn_perturb_steps": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),
+    "pasn_perturb_apply": (c_int, [c_void_p] * 4 + [c_float, c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "pasn_perturb_curves": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_long] + [c_void_p] * 5),
     # ---- the training loss recipe (losses.FusedCriterion)
     "pasn_proto_loss_fwd": (c_int, [c_void_p] * 13 + [POINTER(ProtoLossDesc), c_void_p]),
     "pasn_proto_loss_bwd": (c_int, [c_void_p] * 14 + [POINTER(ProtoLossDesc), c_void_p]),

@@ -471,6 +471,12 @@ class _XProtoHeadMixin:
 
         return explain_batch(self, x, **kw)
 
+    def faithfulness(self, x: torch.Tensor, **kw):
+        """Deletion / insertion curves of the clips ``x`` under their own occurrence maps (faithfulness.perturbation_curves)."""
+        from .faithfulness import perturbation_curves
+
+        return perturbation_curves(self, x, **kw)
+
 
 class XProtoNet(_XProtoHeadMixin, PPNet):
     """Image ProtoASNet / XProtoNet (reference src/models/XProtoNet.py:8-106) -- head B on a 2-D trunk."""

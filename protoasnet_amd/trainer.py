@@ -537,6 +537,47 @@ class DPTrainer:
                  f"NLL {res['nll_before']:.4f} -> {res['nll_after']:.4f}")
         return res
 
+    def evaluate_faithfulness(self, mode: str = "val", steps: int = 10, select: int = 1, max_clips: Optional[int] = None,
+                              max_batch: int = 64, seed: int = 0) -> Dict[str, object]:
+        """Are the occurrence maps faithful on ``data_loaders[mode]``?  (``protoasnet_amd.faithfulness``)  An eval-mode sweep: per batch
+        (through ``prepare_input``) the deletion and insertion curves of the ``select`` best prototypes of the predicted class under the
+        model's maps and under a random map, summed in fp64 on the device and read once.  Returns
+        ``FaithfulnessAccumulator.result()``: the mean curves, the mean areas, the random control's and their differences.  ``max_clips``
+        ends the sweep after that many clips.  Each rank sweeps its own loader; no collectives, no training or epoch state; the model is
+        left in the mode it was in."""
+        from . import faithfulness
+        from .explain import _is_xproto
+
+        if not _is_xproto(self.model):
+            raise NotImplementedError("faithfulness curves cover XProtoNet and Video_XProtoNet")
+        if self.device.type != "cuda":
+            raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
+        if max_clips is not None and max_clips < 1:
+            raise ValueError(f"max_clips must be positive, got {max_clips}")
+        acc = faithfulness.FaithfulnessAccumulator(self.model, select=select, steps=steps, max_batch=max_batch,
+                                                   abstain_class=bool(self.config.get("abstain_class")), seed=seed)
+        was_training = self.model.training
+        self.model.eval()
+        seen = 0
+        try:
+            with torch.no_grad():
+                for sample in self.staged(self.data_loaders[mode]):
+                    x = self.prepare_input(sample["cine"])
+                    if max_clips is not None:
+                        x = x[: max_clips - seen]
+                    acc.update(x)
+                    seen += int(x.shape[0])
+                    if max_clips is not None and seen >= max_clips:
+                        break
+        finally:
+            self.model.train(was_training)
+        res = acc.result()
+        self.log(f"Epoch: {self.current_epoch} | {mode} | faithfulness ({res['clips']} clips) | deletion AUC (prob) "
+                 f"{float(res['deletion']['auc_prob'].mean()):.4f} vs random {float(res['random']['deletion']['auc_prob'].mean()):.4f} | "
+                 f"insertion AUC (prob) {float(res['insertion']['auc_prob'].mean()):.4f} vs random "
+                 f"{float(res['random']['insertion']['auc_prob'].mean()):.4f}")
+        return res
+
     def push(self, replace_prototypes: bool = True):
         abstain = bool(self.config.get("abstain_class"))
         self.sync_norm_buffers()  # every shard of the sweep must see the same eval-mode statistics
