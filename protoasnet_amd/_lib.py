@@ -259,9 +259,8 @@ _TUNING_EPOCH = [0]
 
 def tuning_reload() -> None:
     """Take a new snapshot of the PASN_* environment (after ``os.environ`` / ``monkeypatch.setenv`` changed it: tests, A/B tools).
-    Bumps ``tuning_epoch()``: compiled plans, training runners and captured graphs are keyed on it, because their workspaces were sized
-    under the geometry switches of the snapshot they were built with (PASN_TRAIN_BLOCKS, PASN_DWWG_BLOCKS ...) while the launchers
-    recompute the geometry per launch -- a plan from an older snapshot is rebuilt instead of replayed."""
+    Bumps ``tuning_epoch()``, which ``plan.PlanCache`` stamps into every compiled plan, runner and captured graph (their workspaces
+    were sized under the snapshot's geometry switches): an entry from an older snapshot is dropped and rebuilt, never replayed."""
     lib().pasn_tuning_reload()
     _TUNING_EPOCH[0] += 1
 

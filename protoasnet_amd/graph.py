@@ -26,19 +26,17 @@ What a captured graph depends on, and how each dependency is tracked:
 The returned tensors are the graph's static outputs: every replay overwrites them (clone what must survive the next call).
 """
 import warnings
-from collections import OrderedDict
-from typing import Tuple
 
 import torch
 
-from . import _lib
+from .plan import PlanCache, tensor_signature
 
 
 class _Entry:
-    __slots__ = ("graph", "out", "sig", "keep", "x_static")
+    __slots__ = ("graph", "out", "keep", "x_static")
 
-    def __init__(self, graph, out, sig, keep, x_static):
-        self.graph, self.out, self.sig, self.keep, self.x_static = graph, out, sig, keep, x_static
+    def __init__(self, graph, out, keep, x_static):
+        self.graph, self.out, self.keep, self.x_static = graph, out, keep, x_static
 
 
 class GraphedForward:
@@ -47,28 +45,29 @@ class GraphedForward:
             raise RuntimeError("GraphedForward replays the eval-mode forward: call model.eval() first")
         self.model, self.warmup = model, max(1, int(warmup))
         self.static_input, self.max_graphs = bool(static_input), max(1, int(max_graphs))
-        self._graphs: "OrderedDict[Tuple, _Entry]" = OrderedDict()
+        self._graphs = PlanCache(self._signature, max_entries=self.max_graphs, on_evict=self._warn_evicted)
         self.captures = 0  # how many times a forward was captured (tests; a steadily growing count means the key keeps changing)
 
     # ------------------------------------------------------------------------------------------ what the graph was captured against
     def _signature(self) -> tuple:
-        return tuple((t.data_ptr(), t._version) for t in list(self.model.parameters()) + list(self.model.buffers()))
+        return tensor_signature(list(self.model.parameters()) + list(self.model.buffers()))
 
     def _keepalive(self) -> list:
-        """The objects whose device memory the captured kernels address but the graph's private pool does not own."""
-        keep = []
-        for m in self.model.modules():
-            plans = getattr(m, "_plans", None)  # plan.HipTrunk: {key: (signature, Plan)}
-            if isinstance(plans, dict):
-                keep.append(dict(plans))
-            cache = getattr(m, "_cache", None)  # nets.PointwiseChain: packed weights / row plans
-            if isinstance(cache, dict):
-                keep.append(dict(cache))
-        return keep
+        """The objects whose device memory the captured kernels address but the graph's private pool does not own: what every
+        ``PlanCache`` on the model's modules (trunk plans, the head chains' packed weights / row plans) holds right now."""
+        return [c.values() for m in self.model.modules() for c in vars(m).values() if isinstance(c, PlanCache)]
 
-    def _capture(self, x: torch.Tensor, sig: tuple, x_static) -> _Entry:
+    def _warn_evicted(self, old: tuple) -> None:
+        warnings.warn(
+            f"GraphedForward: more than {self.max_graphs} live captures -- evicting the one for input {old[:3]}.  A new input address "
+            "per call re-captures per call; pass static_input=True (or reuse one input tensor and copy_ into it)", RuntimeWarning)
+
+    def _capture(self, x: torch.Tensor) -> _Entry:
         if self.model.training:
             raise RuntimeError("GraphedForward replays the eval-mode forward: the model was switched to train() since construction")
+        x_static = None
+        if self.static_input:
+            x = x_static = torch.empty_like(x, memory_format=torch.contiguous_format).copy_(x)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
@@ -81,36 +80,17 @@ class GraphedForward:
         with torch.no_grad(), torch.cuda.graph(g, capture_error_mode="thread_local"):
             out = self.model(x)
         self.captures += 1
-        return _Entry(g, out, sig, self._keepalive(), x_static)
+        return _Entry(g, out, self._keepalive(), x_static)
 
     def __call__(self, x: torch.Tensor):
         if not x.is_cuda:
             raise RuntimeError("GraphedForward runs on the GPU only; there is no CPU fallback")
-        if self.static_input:
-            key = ("static", tuple(x.shape), x.dtype, x.device, _lib.tuning_epoch())
-        else:
-            key = (x.data_ptr(), tuple(x.shape), x.dtype, tuple(x.stride()), x.device, _lib.tuning_epoch())
-        sig = self._signature()
-        ent = self._graphs.get(key)
-        if ent is not None and ent.sig != sig:  # a weight / buffer changed since the capture: never replay the stale graph
-            del self._graphs[key]
-            ent = None
-        if ent is None:
-            x_static = None
-            if self.static_input:
-                x_static = torch.empty_like(x, memory_format=torch.contiguous_format)
-                x_static.copy_(x)
-            ent = self._capture(x_static if self.static_input else x, sig, x_static)
-            self._graphs[key] = ent
-            while len(self._graphs) > self.max_graphs:
-                old, _ = self._graphs.popitem(last=False)
-                warnings.warn(
-                    f"GraphedForward: more than {self.max_graphs} live captures -- evicting the one for input {old[:3]}.  A new input address "
-                    "per call re-captures per call; pass static_input=True (or reuse one input tensor and copy_ into it)", RuntimeWarning)
-        else:
-            self._graphs.move_to_end(key)
-            if ent.x_static is not None:
-                ent.x_static.copy_(x)
+        key = (("static", tuple(x.shape), x.dtype, x.device) if self.static_input
+               else (x.data_ptr(), tuple(x.shape), x.dtype, tuple(x.stride()), x.device))
+        seen = self.captures
+        ent = self._graphs.lookup(key, lambda: self._capture(x))  # a weight / buffer changed since: stale stamp, dropped, never replayed
+        if ent.x_static is not None and self.captures == seen:  # a hit: a fresh capture has just copied the clip in
+            ent.x_static.copy_(x)
         ent.graph.replay()
         return ent.out
 

@@ -20,7 +20,7 @@ from . import _lib
 from ._lib import XProtoDesc
 from .backbones import base_architecture_to_features
 from .data import GreyInputError
-from .plan import Act, HipTrunk, PlanBuilder, channels_last_rows, logical_view, pack_conv_weight, round_up
+from .plan import Act, HipTrunk, PlanBuilder, PlanCache, channels_last_rows, logical_view, pack_conv_weight, round_up, tensor_signature
 from .receptive_field import compute_proto_layer_rf_info_v2
 
 
@@ -35,7 +35,7 @@ class PointwiseChain(nn.Sequential):
 
     def __init__(self, *mods):
         super().__init__(*mods)
-        self._cache = {}
+        self._cache = PlanCache(self._sig)
 
     def convs(self):
         return [m for m in self if isinstance(m, (nn.Conv2d, nn.Conv3d))]
@@ -51,43 +51,40 @@ class PointwiseChain(nn.Sequential):
         return out
 
     def _sig(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+        return tensor_signature(self.parameters())
 
     def packed(self, cin_p: int, dtype: torch.dtype, frag: bool = False):
         """[(weight [rows][1][kc] in dtype, bias fp32 [rows] or None)] per conv, cached until a parameter changes.
         ``frag``: weights fragment-major, [rows / 32][kc / 16][64 lanes][8] (bf16; what ``pasn_xproto_chain_fwd`` reads)."""
-        key, sig = ("packed", cin_p, dtype, frag), self._sig()
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        out, cp = [], cin_p
-        for conv in self.convs():
-            w, kc, rows = pack_conv_weight(conv.weight, cp, dtype)
-            if frag:
-                w = w.view(rows // 32, 32, kc // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
-            b = None
-            if conv.bias is not None:
-                b = torch.zeros(rows, dtype=torch.float32, device=w.device)
-                b[: conv.out_channels] = conv.bias.detach().float()
-            out.append((w, b))
-            cp = round_up(conv.out_channels, 8)
-        self._cache[key] = (sig, out)
-        return out
+        def make():
+            out, cp = [], cin_p
+            for conv in self.convs():
+                w, kc, rows = pack_conv_weight(conv.weight, cp, dtype)
+                if frag:
+                    w = w.view(rows // 32, 32, kc // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
+                b = None
+                if conv.bias is not None:
+                    b = torch.zeros(rows, dtype=torch.float32, device=w.device)
+                    b[: conv.out_channels] = conv.bias.detach().float()
+                out.append((w, b))
+                cp = round_up(conv.out_channels, 8)
+            return out
+
+        return self._cache.lookup(("packed", cin_p, dtype, frag), make)
 
     def run_rows(self, rows: torch.Tensor, shape5, c: int, dtype: torch.dtype) -> torch.Tensor:
         """rows: channels-last [N][S][Cp] storage of a (N,c,T,H,W) map -> channels-last storage [N][T][H][W][Dp]."""
         n, t, h, w = shape5
-        key, sig = ("plan", tuple(rows.shape), tuple(shape5), c, dtype, rows.device, _lib.tuning_epoch()), self._sig()
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != sig:
+
+        def make():
             pb = PlanBuilder(rows.device, dtype, dtype)
             x_in = Act(n, t, h, w, c, rows.shape[2], pb._new_buf(rows.numel() * rows.element_size(), external=True))
             a = x_in
             for conv, act in self._steps():
                 a = pb.conv(a, conv, None, act)
-            hit = (sig, pb.finish(x_in, a))
-            self._cache[key] = hit
-        return hit[1].run(rows)
+            return pb.finish(x_in, a)
+
+        return self._cache.lookup(("plan", tuple(rows.shape), tuple(shape5), c, dtype, rows.device), make).run(rows)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
@@ -292,24 +289,30 @@ class PPNet(nn.Module):
             x = x.float()
         return x.contiguous()
 
-    def _train_pass_a(self, x: torch.Tensor):
-        """Train-mode forward of the ProtoPNet model (differentiable; ``train.TrainRunner`` with head A)."""
+    def _train_signature(self) -> tuple:
+        # the launch lists hold the parameters' device addresses: a model moved / cast / pruned since gets a fresh compilation
+        return tuple((p.data_ptr(), p.requires_grad) for p in self.parameters()), tuple(self.prototype_shape)
+
+    def _train_runner(self, x: torch.Tensor, mode: int, head: str):
+        """Train-mode pass (batch-statistics norm, differentiable): one compiled forward + backward launch list per input
+        shape (``train.TrainRunner``), driven by autograd -- the path ``loss.backward()`` of the reference's agents takes
+        (Video_XProtoNet_e2e.py:118-141; ``compute_occurence_map`` is called with gradients by loss.py:302)."""
         from .train import TrainRunner
 
         x = self._train_input(x)
-        runners = self.__dict__.setdefault("_train_runners", {})
-        key = (tuple(x.shape), x.dtype, self._dtype(), "A", hash(tuple((p.data_ptr(), p.requires_grad) for p in self.parameters())),
-               tuple(self.prototype_shape), _lib.tuning_epoch())
-        runner = runners.get(key)
-        if runner is None:
-            for stale in [k for k in runners if k[:4] == key[:4]]:
-                del runners[stale]
-            runner = runners[key] = TrainRunner(self, x, 0, head="A")
-        return runner(x)
+        if "_train_runners" not in self.__dict__:
+            self._train_runners = PlanCache(self._train_signature)
+
+        def make():
+            if head == "B" and (len(self.add_on_layers.convs()) != 2 or len(self.occurrence_module.convs()) != 3):
+                raise NotImplementedError("the training path supports the 2-conv add-on and 3-conv occurrence module of the shipped configs")
+            return TrainRunner(self, x, mode, head=head)
+
+        return self._train_runners.lookup((tuple(x.shape), x.dtype, self._dtype(), mode if head == "B" else "A"), make)(x)
 
     def forward(self, x: torch.Tensor):
         if self.training:
-            return self._train_pass_a(x)
+            return self._train_runner(x, 0, "A")
         z, (n, h, w) = self._conv_rows(x)
         logits, min_d, _ = self._head(z, n, h * w, want_dist=False)
         return logits, min_d
@@ -351,29 +354,9 @@ def _occurrence_module(conv, cin: int, depth: int, num_prototypes: int) -> Point
 class _XProtoHeadMixin:
     """Head B shared by the image and video models: one ``pasn_xproto_head_fwd`` call after the trunk."""
 
-    def _train_pass(self, x: torch.Tensor, mode: int):
-        """Train-mode pass (batch-statistics norm, differentiable): one compiled forward + backward launch list per input
-        shape (``train.TrainRunner``), driven by autograd -- the path ``loss.backward()`` of the reference's agents takes
-        (Video_XProtoNet_e2e.py:118-141; ``compute_occurence_map`` is called with gradients by loss.py:302)."""
-        from .train import TrainRunner
-
-        x = self._train_input(x)
-        runners = self.__dict__.setdefault("_train_runners", {})
-        # the launch lists hold the parameters' device addresses: a model moved / cast / pruned since gets a fresh compilation
-        key = (tuple(x.shape), x.dtype, self._dtype(), mode, hash(tuple((p.data_ptr(), p.requires_grad) for p in self.parameters())),
-               tuple(self.prototype_shape), _lib.tuning_epoch())
-        runner = runners.get(key)
-        if runner is None:
-            for stale in [k for k in runners if k[:4] == key[:4]]:
-                del runners[stale]
-            if len(self.add_on_layers.convs()) != 2 or len(self.occurrence_module.convs()) != 3:
-                raise NotImplementedError("the training path supports the 2-conv add-on and 3-conv occurrence module of the shipped configs")
-            runner = runners[key] = TrainRunner(self, x, mode)
-        return runner(x)
-
     def _xproto(self, x: torch.Tensor, mode: int):
         if self.training:
-            out = self._train_pass(x, mode)
+            out = self._train_runner(x, mode, "B")
             return (out[0], out[1], out[2], None) if mode == 0 else (None, None, out[0], None)
         self._guard(x)
         feat = self.cnn_backbone(x)
@@ -454,7 +437,7 @@ class _XProtoHeadMixin:
         nb = x.shape[0]
         both = torch.cat([x, x_transformed])
         if self.training:
-            logits, sim, occ = self._train_pass(both, 2)
+            logits, sim, occ = self._train_runner(both, 2, "B")
         else:
             logits, sim, occ, _ = self._xproto(both, 0)
         return (logits[:nb], sim[:nb], occ[:nb]), occ[nb:]

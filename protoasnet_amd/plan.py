@@ -909,6 +909,48 @@ class Plan:
         return y
 
 
+def tensor_signature(tensors) -> tuple:
+    """(storage address, autograd version counter) of every tensor: moves on ``load_state_dict``, ``.to()``, an optimizer step and any
+    other in-place op -- but NOT on a write through ``.data`` or a raw pointer, which bumps no counter."""
+    return tuple((t.data_ptr(), t._version) for t in tensors)
+
+
+class PlanCache:
+    """Compiled device state (plans, packed weights, training runners, captured graphs) by key.  An entry is stamped with
+    (``signature()``, tuning epoch) when it is built and is good only while that stamp is the current one; a miss first drops EVERY
+    entry with another stamp (none can hit again, and two generations of arenas are never held at once), then builds.  With
+    ``max_entries`` the least recently used entries beyond it are evicted, each reported through ``on_evict(key)``."""
+
+    def __init__(self, signature: Callable[[], tuple], max_entries: Optional[int] = None, on_evict: Optional[Callable] = None):
+        self.signature, self.max_entries, self.on_evict = signature, max_entries, on_evict
+        self._entries: Dict[tuple, tuple] = {}  # key -> (stamp, value), least recently used first
+
+    def lookup(self, key, make: Callable):
+        stamp = (self.signature(), _lib.tuning_epoch())
+        hit = self._entries.get(key)
+        if hit is not None and hit[0] == stamp:
+            self._entries[key] = self._entries.pop(key)  # most recently used last
+            return hit[1]
+        self._entries = {k: v for k, v in self._entries.items() if v[0] == stamp}
+        value = make()
+        self._entries[key] = (stamp, value)
+        while self.max_entries is not None and len(self._entries) > self.max_entries:
+            old = next(iter(self._entries))
+            del self._entries[old]
+            if self.on_evict is not None:
+                self.on_evict(old)
+        return value
+
+    def values(self) -> list:
+        return [v for _, v in self._entries.values()]
+
+    def clear(self) -> None:
+        self._entries = {}
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+
 def logical_view(y: torch.Tensor, channels: int, video: bool) -> torch.Tensor:
     """Channels-last storage [N][T][H][W][Cp] -> the reference's logical (N,C,[T,]H,W) tensor (a strided view)."""
     v = y[..., :channels].permute(0, 4, 1, 2, 3)
@@ -947,7 +989,7 @@ class HipTrunk(nn.Module):
 
     def __init__(self):
         super().__init__()
-        self._plans: Dict[tuple, Tuple[tuple, Plan]] = {}
+        self._plans = PlanCache(self._signature)
         self.compute_dtype: Optional[torch.dtype] = None  # None: follow the parameter dtype
         self.input_affine: Tuple[float, float] = (1.0, 0.0)  # x' = x * a + b applied to a GREY (1-channel) input while loading
 
@@ -967,32 +1009,27 @@ class HipTrunk(nn.Module):
         )
 
     def _signature(self) -> tuple:
-        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        return tensor_signature(list(self.parameters()) + list(self.buffers()))
 
     def invalidate_plans(self) -> None:
-        """Drop every cached launch list (and its packed weights).  The cache key is (storage address, autograd version counter) of
+        """Drop every cached launch list (and its packed weights).  The cache stamp is (storage address, autograd version counter) of
         every parameter / buffer, which sees optimizer steps, ``load_state_dict``, ``.to()`` and any in-place op on the parameter --
         but NOT a write through ``param.data`` or a raw pointer, which bumps no counter.  Code that does that to a trunk calls this
         afterwards.  (The reference writes through ``.data`` only to ``prototype_vectors`` and ``last_layer.weight``
         (push_abs_revision.py:346, ProtoPNet.py:308-311); neither is packed or cached here.)"""
-        self._plans = {}
+        self._plans.clear()
 
     def plan_for(self, x: torch.Tensor) -> Plan:
-        p0 = next(self.parameters())
-        dtype = self.compute_dtype or p0.dtype
-        key = (tuple(x.shape), x.dtype, dtype, x.device, self.input_affine if x.shape[1] == 1 else None, _lib.tuning_epoch())
-        sig = self._signature()
-        hit = self._plans.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        pb = PlanBuilder(x.device, dtype, x.dtype, self.input_affine)
-        x_in = pb.input(tuple(x.shape))
-        with torch.no_grad():
-            y_out = self.build_plan(pb, x_in)
-        plan = pb.finish(x_in, y_out)
-        self._plans = {k: v for k, v in self._plans.items() if v[0] == sig}  # drop plans packed from stale weights
-        self._plans[key] = (sig, plan)
-        return plan
+        dtype = self.compute_dtype or next(self.parameters()).dtype
+
+        def make() -> Plan:
+            pb = PlanBuilder(x.device, dtype, x.dtype, self.input_affine)
+            x_in = pb.input(tuple(x.shape))
+            with torch.no_grad():
+                y_out = self.build_plan(pb, x_in)
+            return pb.finish(x_in, y_out)
+
+        return self._plans.lookup((tuple(x.shape), x.dtype, dtype, x.device, self.input_affine if x.shape[1] == 1 else None), make)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.training:
