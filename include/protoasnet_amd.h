@@ -116,7 +116,8 @@ int pasn_x3d_stem_mfma_fwd(const void* x, const void* wq, const float* scale, co
 /*
  * The same first layer on the matrix cores, bf16 activations out: (1,kh,kw <= 7) windows, stride (1,2,2) -- the 7x7 stems of
  * R(2+1)D-18 and ResNet-18 (resnet_features.py:203-205, :316-320); d->Cin = 3 (the reference's clip) or 1 (grey clip, taps summed,
- * as for pasn_first_conv_gray_fwd).  pasn_first_conv_mfma_slot returns -1 when the layer is not covered (use pasn_first_conv_fwd), else
+ * as for pasn_first_conv_gray_fwd).  Instances exist for ceil(Cin*kh/2) in {11, 5, 4, 2} (the 7x7 and 3x3 windows), kh >= 2.
+ * pasn_first_conv_mfma_slot returns -1 when the layer is not covered (use pasn_first_conv_fwd / pasn_first_conv_gray_fwd), else
  * the slot o of tap 0 in the 8-wide window the weights must be laid out for:
  *   wq : bf16 [2*ceil(Cin*kh/2)][32*ceil(Cout_p/32)][8],  wq[ci*kh + r][co][o + s] = w[co][ci][r][s], zero elsewhere
  *   x' = x * in_a + in_b is applied while the clip is staged (1, 0 = none); zero padding pads the normalised tensor.

@@ -12,7 +12,8 @@
 
 Each operand format the kernels define is packed by ONE module-level function: ``pack_conv_weight`` (dense [rows][taps][kc]),
 ``fragment_major`` / ``fragment_view`` (its MFMA fragment order, ``frag_steps`` per dtype; the training pass refreshes through the same
-view), ``se_operands`` (squeeze-excite fc pair), ``pack_dw_taps`` (depthwise [taps][Cp]), ``stencil_operands`` (matrix-core stencil).
+view), ``se_operands`` (squeeze-excite fc pair), ``pack_dw_taps`` (depthwise [taps][Cp]), ``stencil_operands`` (matrix-core stencil), ``pack_first_valu`` /
+``pack_first_mfma`` / ``pack_stem_mfma`` (the first layer's taps: VALU rows, matrix-core K order, the stem's combined map).
 A ``PlanBuilder`` method that may answer "not covered" probes first and allocates after: it asks the library with ``_geom`` (output
 extents, no buffer) and ``_probe_desc`` (a descriptor nobody keeps), and only a launch that will be recorded reserves buffers
 (``_alloc``) and appends to ``keep`` -- a declined launch leaves no trace in the arena plan.  ``conv_kernel_name`` /
@@ -168,6 +169,19 @@ def pack_first_mfma(w: torch.Tensor, slot: int, cp: int, device, out: Optional[t
     wq = out if out is not None else torch.zeros(nq, bn, 8, dtype=torch.float32, device=device)
     wq[:rows, :c, slot:slot + kw] = w.permute(1, 2, 0, 3).reshape(rows, c, kw)
     return wq
+
+
+def pack_stem_mfma(wxy: torch.Tensor, wt: torch.Tensor, device) -> torch.Tensor:
+    """X3D stem weights in the matrix-core stem's K order: both convs as one map, the fp32 product W'[co][kt][ci][r][s] = wt[co][kt] *
+    wxy[co][ci][r][s] (``wxy`` (C, Ci, 3, 3), ``wt`` (C, 5)) as fp32 [2 * ksteps][32][8] -- K rows R = (kt, ci, r) in pairs, 4-wide window
+    slots with tap s in slot 1 + s, 32 channels.  The kernel reads the bf16 cast."""
+    c, ci = wxy.shape[0], wxy.shape[1]
+    rows = 5 * ci * 3
+    ksteps = (rows + 3) // 4
+    comb = wt[:, :, None, None, None] * wxy[:, None]                         # [co][kt][ci][r][s]
+    wr = torch.zeros(4 * ksteps, 32, 4, dtype=torch.float32, device=device)
+    wr[:rows, :c, 1:4] = comb.permute(1, 2, 3, 0, 4).reshape(rows, c, 3)
+    return wr.view(2 * ksteps, 2, 32, 4).permute(0, 2, 1, 3).reshape(2 * ksteps, 32, 8)
 
 
 def pack_first_valu(w: torch.Tensor, cp: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -367,6 +381,10 @@ class PlanBuilder:
         d = self._probe_desc(x, y, k, s, p, "relu")
         fusable = (x.planar and x.C in (1, 3) and kt == (5, 1, 1) and st_ == (1, 1, 1) and pt_ == (2, 0, 0) and conv_t.groups == c
                    and conv_xy.bias is None and conv_t.bias is None and bool(self.lib.pasn_x3d_stem_supported(ctypes.byref(d))))
+        code_in, code_out = _lib.dtype_code(self.in_dtype), self.code
+        mfma = fusable and bool(self.lib.pasn_x3d_stem_mfma_supported(ctypes.byref(d), code_in, code_out))
+        if fusable and not mfma and self.in_dtype == torch.uint8 and x.C != 1:
+            fusable = False  # x3d_stem_kernel reads uint8 from a grey clip only (stem.hip, stem_dispatch): the two launches have the instance
         if not fusable:
             e = self.first_conv(x, conv_xy, None, act="none")
             return self.dwconv(e, conv_t, norm, act="relu")
@@ -374,17 +392,9 @@ class PlanBuilder:
         wsrc = conv_xy.weight.detach().float()[:, :, 0]
         if x.C == 1:  # grey clip: taps summed over the three identical input channels (9 instead of 27)
             wsrc = wsrc.sum(dim=1, keepdim=True)
-        code_in, code_out = _lib.dtype_code(self.in_dtype), self.code
-        if int(self.lib.pasn_x3d_stem_mfma_supported(ctypes.byref(d), code_in, code_out)):
+        if mfma:
             # matrix-core stem: both convs as one map, K rows R = (kt, ci, r), 4-wide window slots with tap s in slot 1 + s; rows in pairs
-            rows = 5 * x.C * 3
-            ksteps = (rows + 3) // 4
-            wtc = conv_t.weight.detach().float().reshape(c, 5)                       # [co][kt]
-            comb = wtc[:, :, None, None, None] * wsrc[:, None]                       # [co][kt][ci][r][s]
-            wr = torch.zeros(4 * ksteps, 32, 4, dtype=torch.float32, device=self.device)
-            wr[:rows, :c, 1:4] = comb.permute(1, 2, 3, 0, 4).reshape(rows, c, 3)
-            wq = wr.view(2 * ksteps, 2, 32, 4).permute(0, 2, 1, 3).reshape(2 * ksteps, 32, 8)
-            wq = wq.to(torch.bfloat16).contiguous()
+            wq = pack_stem_mfma(wsrc, conv_t.weight.detach().float().reshape(c, 5), self.device).to(torch.bfloat16).contiguous()
             scale, bias = fold_norm(norm, None, c, y.Cp, self.device)
             self.keep += [wq, scale, bias, d]
             a = (wq.data_ptr(), scale.data_ptr(), bias.data_ptr())
