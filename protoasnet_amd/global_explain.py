@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from . import push as push_mod
 from .data import ECHO_MEAN, ECHO_STD
+from .sweep import WinnerStore, filenames_at, gather_ranks, sweep_batches
 
 K_MAX = 64      # one row entry per lane of a wave
 _I64_MAX = torch.iinfo(torch.int64).max
@@ -77,7 +78,11 @@ class TopKState:
         self.dist = torch.full((P, k), float("inf"), dtype=torch.float32, device=device)
         self.index = torch.full((P, k), -1, dtype=torch.int64, device=device)
         self.slot = torch.arange(k, dtype=torch.int32, device=device).repeat(P, 1).contiguous()
-        self.stores: dict = {}
+        self.store = WinnerStore(P, k, device)
+
+    @property
+    def stores(self) -> dict:
+        return self.store.stores
 
     def update(self, proto_dist, labels, proto_class, class_mask, index_base: int) -> None:
         B, P = (int(v) for v in proto_dist.shape)
@@ -87,25 +92,11 @@ class TopKState:
 
     def gather(self, name: str, payload: torch.Tensor, per_proto: bool, index_base: int, fill=0) -> None:
         """``payload`` (B, P, ...) with ``per_proto`` else (B, ...): its rows follow this batch's winners into ``stores[name]``."""
-        payload = payload.contiguous()
-        B = int(payload.shape[0])
-        row_shape = tuple(payload.shape[2 if per_proto else 1:])
-        store = self.stores.get(name)
-        if store is None:
-            store = self.stores[name] = torch.full((self.P, self.k) + row_shape, fill, dtype=payload.dtype, device=self.device)
-        elif tuple(store.shape[2:]) != row_shape or store.dtype != payload.dtype:
-            raise ValueError(f"payload {name!r}: rows {row_shape} {payload.dtype} do not match the store {tuple(store.shape[2:])} {store.dtype}")
-        _lib.check(_lib.lib().pasn_topk_gather(
-            self.index.data_ptr(), self.slot.data_ptr(), payload.data_ptr(), store.data_ptr(), B, self.P, self.k,
-            int(np.prod(row_shape, dtype=np.int64)), payload.element_size(), int(per_proto), int(index_base), _lib.current_stream()))
+        self.store.gather(name, payload, per_proto, self.index, self.slot, index_base, fill)
 
     def resolved(self, name: str) -> torch.Tensor:
         """``stores[name]`` in row order (slot indirection resolved); empty entries keep the store's fill value."""
-        store = self.stores[name]
-        rows = store[torch.arange(self.P, device=store.device)[:, None], self.slot.long()]
-        fill = store.new_full((), -1 if store.dtype in _SIGNED else 0)
-        valid = (self.index >= 0).view((self.P, self.k) + (1,) * (store.dim() - 2))
-        return torch.where(valid, rows, fill)
+        return self.store.resolved(name, self.index, self.slot)
 
 
 # ------------------------------------------------------------------------------------------------- pure host-side pieces
@@ -163,27 +154,7 @@ def ranking_stats(class_sim_sum: torch.Tensor, class_count: torch.Tensor, proto_
     return mean, purity, margin, ranking
 
 
-def _filenames(names: dict, index: torch.Tensor) -> List[List[Optional[str]]]:
-    bases = np.array(sorted(names), dtype=np.int64)
-    out = []
-    for row in index.detach().cpu().numpy().astype(np.int64):
-        files = []
-        for g in row:
-            at = int(np.searchsorted(bases, g, side="right")) - 1 if g >= 0 and bases.size else -1
-            batch = names[int(bases[at])] if at >= 0 else []
-            off = int(g - bases[at]) if at >= 0 else 0
-            files.append(batch[off] if at >= 0 and off < len(batch) else None)
-        out.append(files)
-    return out
-
-
-def _all_gather(t: torch.Tensor, device) -> List[torch.Tensor]:
-    import torch.distributed as dist
-
-    t = push_mod._for_collective(t.contiguous())
-    buf = [torch.empty_like(t) for _ in range(dist.get_world_size())]
-    dist.all_gather(buf, t)
-    return [b.to(device) for b in buf]
+_filenames = filenames_at
 
 
 # ------------------------------------------------------------------------------------------------- the sweep
@@ -209,15 +180,10 @@ def nearest_clips(dataloader, model, k: int = 10, class_specific: bool = False, 
     class_sum = torch.zeros((P, K), dtype=torch.float64, device=device)
     class_count = torch.zeros((K,), dtype=torch.int64, device=device)
     lib = _lib.lib()
-    names, sims, targets, pinned = {}, [], [], []
-    rows_shape = None
-    for _, base, sample in push_mod._iter_shard(dataloader, rank, world_size):
-        x = sample["cine"]
-        if preprocess_input_function is not None:
-            x = preprocess_input_function(x)
-        labels = push_mod._labels_to_device(sample["target_AS"], device, pinned)
+    names, sims, targets = {}, [], []
+    for _, base, sample, xdev, labels in sweep_batches(dataloader, device, rank, world_size, preprocess_input_function):
         with torch.no_grad():
-            _, proto_dist, occ, logits = model.push_forward(x.to(device))
+            _, proto_dist, occ, logits = model.push_forward(xdev)
         proto_dist = proto_dist.contiguous()
         B = int(proto_dist.shape[0])
         state.update(proto_dist, labels, proto_class, mask, base)
@@ -226,30 +192,20 @@ def nearest_clips(dataloader, model, k: int = 10, class_specific: bool = False, 
         state.gather("labels", labels, False, base, fill=-1)
         _lib.check(lib.pasn_proto_class_stats(proto_dist.data_ptr(), labels.data_ptr(), B, P, K, class_sum.data_ptr(),
                                               class_count.data_ptr(), _lib.current_stream()))
-        rows_shape = (tuple(occ.shape[2:]), occ.dtype, logits.dtype)
         files = sample.get("filename")
-        names[int(base)] = [None] * B if files is None else list(files)
+        names[base] = [None] * B if files is None else list(files)
         if keep_sim_scores:
             sims.append(1 - proto_dist)
             targets.append(labels)
-    if world_size > 1:
-        import torch.distributed as dist
-
-        shapes = [None] * world_size
-        dist.all_gather_object(shapes, rows_shape)
-        rows_shape = next((s for s in shapes if s is not None), None)
-    if rows_shape is None:
+    if not state.store.agree(world_size):
         raise ValueError("nearest_clips: the loader holds no batch")
-    if "occ" not in state.stores:  # a rank with an empty shard: empty stores of the agreed shapes
-        state.stores = {"occ": torch.zeros((P, k) + rows_shape[0], dtype=rows_shape[1], device=device),
-                        "logits": torch.zeros((P, k, K), dtype=rows_shape[2], device=device),
-                        "labels": torch.full((P, k), -1, dtype=torch.int64, device=device)}
     rows = (state.dist, state.index, state.resolved("labels"), state.resolved("logits"), state.resolved("occ"))
     sim_scores = torch.cat(sims) if sims else None
     tgt = torch.cat(targets) if targets else None
     if world_size > 1:
-        gathered = [_all_gather(t, device) for t in rows]
-        rows = merge_topk([tuple(g[r] for g in gathered) for r in range(world_size)])
+        import torch.distributed as dist
+
+        rows = merge_topk(gather_ranks(rows, device))
         for t in (class_sum, class_count):
             buf = push_mod._for_collective(t)
             dist.all_reduce(buf)

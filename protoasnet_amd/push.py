@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .sweep import P_MAX, WinnerStore, filenames_at, first_across_ranks, gather_ranks, sweep_batches
 
 
 # ------------------------------------------------------------------------------------------------- state
@@ -94,16 +95,9 @@ def _all_gather_states(state: PushState, merge):
 
     if not (dist.is_available() and dist.is_initialized()):
         raise RuntimeError("_all_gather_states needs an initialised process group")
-    world = dist.get_world_size()
-    if world == 1:
+    if dist.get_world_size() == 1:
         return state.tensors()
-    gathered = []
-    for t in state.tensors():
-        t = _for_collective(t.contiguous())
-        buf = [torch.empty_like(t) for _ in range(world)]
-        dist.all_gather(buf, t)
-        gathered.append([b.to(state.dist.device) for b in buf])
-    return merge([(gathered[0][r], gathered[1][r], gathered[2][r]) for r in range(world)])
+    return merge(gather_ranks(state.tensors(), state.dist.device))
 
 
 def _for_collective(t: torch.Tensor) -> torch.Tensor:
@@ -201,55 +195,72 @@ def push_prototypes(dataloader, model, class_specific=True, abstain_class=True, 
     mask = xproto_class_mask(P, model.num_classes, class_specific, abstain_class).to(device)
     state = PushState(P, D, device)
     lib = _lib.lib()
-    save = root_dir_for_saving_prototypes is not None
-    rec, names, ar = None, {}, torch.arange(P, device=device)
-    pinned = []
-    for i, base, sample in _iter_shard(dataloader, rank, world_size):
-        x = sample["cine"]
-        if preprocess_input_function is not None:
-            x = preprocess_input_function(x)
-        labels = _labels_to_device(sample["target_AS"], device, pinned)
-        xdev = x.to(device)
+    records = _Records(P, device) if root_dir_for_saving_prototypes is not None else None
+    names = {}
+    for _, base, sample, xdev, labels in sweep_batches(dataloader, device, rank, world_size, preprocess_input_function):
         with torch.no_grad():
             feats, proto_dist, occ, logits = model.push_forward(xdev)
-        B = int(x.shape[0])
+        B = int(xdev.shape[0])
         feats, proto_dist = feats.contiguous(), proto_dist.contiguous()
         _lib.check(lib.pasn_push_xproto_update(
             proto_dist.data_ptr(), feats.data_ptr(), labels.data_ptr(), proto_class.data_ptr(), mask.data_ptr(),
-            state.dist.data_ptr(), state.index.data_ptr(), state.vec.data_ptr(), B, P, D, int(base), _lib.current_stream()))
-        if save:
+            state.dist.data_ptr(), state.index.data_ptr(), state.vec.data_ptr(), B, P, D, base, _lib.current_stream()))
+        if records is not None:
             # the records the reference keeps per prototype (push_abs_revision.py:300-307) stay ON THE DEVICE: a prototype
             # whose current winner lies in this batch takes the batch's occurrence map / logits / clip / label; no host sync
-            names[int(base)] = list(sample.get("filename", [""] * B))
-            here = (state.index >= base) & (state.index < base + B)
-            b = (state.index - base).clamp(0, B - 1)
-            new = (occ[b, ar], logits[b], xdev[b].float(), labels[b])
-            if rec is None:
-                rec = [torch.zeros_like(t) for t in new]
-            rec = [torch.where(here.view((P,) + (1,) * (t.dim() - 1)), t, r) for t, r in zip(new, rec)]
+            names[base] = list(sample.get("filename", [""] * B))
+            records.follow(state.index.view(P, 1), base, ("occ", occ, True), ("logits", logits, False), ("labels", labels, False))
+            records.follow_wide("clips", xdev, state.index, base)
     local_index = state.index.clone()
     merged = _all_gather_states(state, merge_xproto) if world_size > 1 else state.tensors()
-    if save:
-        if world_size > 1:
-            rec, names = _reduce_records(rec, names, local_index, merged[1], device)
-        if rank == 0 and rec is not None:
-            _save_xproto_artefacts(root_dir_for_saving_prototypes, epoch_number, merged, rec, names, log)
+    if records is not None:
+        rec = records.records(local_index.view(P, 1), world_size)
+        if rec is not None:
+            rec[3] = rec[3].float()  # the winners' clips travelled in the batch's dtype: widened once, P clips
+            if world_size > 1:
+                rec, names = _reduce_records(rec, names, local_index, merged[1], device)
+            if rank == 0:
+                _save_xproto_artefacts(root_dir_for_saving_prototypes, epoch_number, merged, rec, names, log)
     return _finish(model, merged, model.prototype_shape, replace_prototypes, log, start)
+
+
+class _Records(WinnerStore):
+    """What a saving push keeps per prototype beside (distance, index, vector): the k = 1 store.  Records of a prototype that never
+    won stay zero."""
+
+    def __init__(self, P: int, device):
+        if P > P_MAX:
+            raise ValueError(f"a push that saves its artefacts takes at most {P_MAX} prototypes (the winners' records follow them "
+                             f"through pasn_topk_gather), got {P}; without a saving directory there is no limit")
+        super().__init__(P, 1, device)
+        self.slot = torch.zeros((P, 1), dtype=torch.int32, device=device)
+
+    def follow(self, index, base: int, *payloads) -> None:
+        """``index`` (P, 1): the winners' global indices after this batch's update; payloads as ``(name, tensor, per_proto)``."""
+        for name, payload, per_proto in payloads:
+            self.gather(name, payload, per_proto, index, self.slot, base)
+
+    def follow_wide(self, name: str, payload, index, base: int) -> None:
+        """The same for a per-clip payload (B, ...) whose rows are megabytes (the input clips), ``index`` (P,): pasn_topk_gather copies a
+        row with ONE wave -- about 1.5 ms for a 4.8 MB clip, in every batch that holds a winner (profiles/README.md, "Sweep refactor") --
+        so these rows take the masked select instead, which moves the P rows at memory bandwidth; in the payload's dtype."""
+        if name not in self.stores:
+            self._create(name, tuple(payload.shape[1:]), payload.dtype, 0)
+        B = int(payload.shape[0])
+        here = ((index >= base) & (index < base + B)).view((self.P, 1) + (1,) * (payload.dim() - 1))
+        self.stores[name] = torch.where(here, payload[(index - base).clamp(0, B - 1)].unsqueeze(1), self.stores[name])
+
+    def records(self, index, world_size: int):
+        """The (P, ...) records in the order they were first followed; None when no rank saw a batch."""
+        return [self.resolved(name, index, self.slot)[:, 0] for name in self.stores] if self.agree(world_size) else None
 
 
 def _reduce_records(rec, names, local_index, merged_index, device):
     """Sharded push: the records of a prototype live on the rank whose shard holds its final winner.  Every rank zeroes the
     records it does not own, ONE sum-reduce per record tensor brings them to rank 0 (exact: all other addends are zeros), the
-    file names travel as objects.  Shapes are agreed on first (a rank with an empty shard has no records yet)."""
+    file names travel as objects.  Every rank hands in records of the same shapes (``WinnerStore.agree``)."""
     import torch.distributed as dist
 
-    shapes = [None] * dist.get_world_size()
-    dist.all_gather_object(shapes, None if rec is None else [(tuple(t.shape), str(t.dtype)) for t in rec])
-    proto = next((sh for sh in shapes if sh is not None), None)
-    if proto is None:
-        return None, names
-    if rec is None:
-        rec = [torch.zeros(sh, dtype=getattr(torch, dt.split(".")[1]), device=device) for sh, dt in proto]
     own = (local_index >= 0) & (local_index == merged_index)
     out = []
     for t in rec:
@@ -259,10 +270,7 @@ def _reduce_records(rec, names, local_index, merged_index, device):
         out.append(t.to(device))
     all_names = [None] * dist.get_world_size()
     dist.all_gather_object(all_names, names)
-    merged_names = {}
-    for d in all_names:
-        merged_names.update(d)
-    return out, merged_names
+    return out, {base: files for part in all_names for base, files in part.items()}
 
 
 def _save_xproto_artefacts(root: str, epoch_number, merged, rec, names, log) -> str:
@@ -275,17 +283,11 @@ def _save_xproto_artefacts(root: str, epoch_number, merged, rec, names, log) -> 
     proto_epoch_dir = os.path.join(root, "epoch-" + str(epoch_number)) if epoch_number is not None else root
     os.makedirs(proto_epoch_dir, exist_ok=True)
     dist, index, _ = merged
-    occ, logits, imgs, gts = (t.detach().cpu().numpy() for t in rec)
+    occ, logits, gts, imgs = (t.detach().cpu().numpy() for t in rec)
     if imgs.shape[1] == 1:  # winners from single-channel clips: the artefact keeps the reference's (P, 3, ...) layout
         imgs = np.repeat(imgs, 3, axis=1)
-    idx = index.detach().cpu().numpy().astype(np.int64)
-    bases = sorted(names)
-    files = []
-    for g in idx:
-        base = max([b for b in bases if b <= g], default=None) if g >= 0 else None
-        files.append(names[base][g - base] if base is not None and g - base < len(names[base]) else None)
     data = {
-        "prototypes_filenames": np.array(files),
+        "prototypes_filenames": np.array(filenames_at(names, index)),
         "prototypes_src_imgs": imgs,                       # (P, 3, (To), Ho, Wo)
         "prototypes_gts": gts,                             # (P)
         "prototypes_preds": logits,                        # (P, K)
@@ -319,8 +321,8 @@ def push_prototypes_ppnet(dataloader, model, class_specific=True, preprocess_inp
     With a saving directory, the box files of the reference are written (push_ProtoPNet.py:121-135):
     ``<prefix>-receptive_field<epoch>.npy`` and ``<prefix><epoch>.npy`` (rows ``[dataset image index, y0, y1, x0, x1, label x K]``,
     -1 where a prototype was never updated) and, with ``prototype_self_act_filename_prefix``, the winners' activation maps
-    ``<prefix><j>.npy``.  The winner's distance map and label stay on the device during the sweep (one ``torch.where`` per
-    batch, no per-batch copy to the host); the boxes are derived once at the end.  The PNG renderings are out of scope."""
+    ``<prefix><j>.npy``.  The winner's distance map and label follow it on the device during the sweep (``sweep.WinnerStore``,
+    no per-batch copy to the host); the boxes are derived once at the end.  The PNG renderings are out of scope."""
     if prototype_layer_stride != 1:
         raise NotImplementedError("prototype_layer_stride != 1 is never used by the reference configs")
     _require_group(world_size)
@@ -333,45 +335,32 @@ def push_prototypes_ppnet(dataloader, model, class_specific=True, preprocess_inp
     state = PushState(P, D, device, ppnet=True)
     lib = _lib.lib()
     search_batch_size = dataloader.batch_size
-    save = root_dir_for_saving_prototypes is not None
-    rec, hw, img_side = None, None, None
-    pinned = []
-    for i, _, sample in _iter_shard(dataloader, rank, world_size):
-        x = sample["cine"]
-        if preprocess_input_function is not None:
-            x = preprocess_input_function(x)
-        labels = _labels_to_device(sample["target_AS"], device, pinned)
+    records = _Records(P, device) if root_dir_for_saving_prototypes is not None else None
+    meta = None
+    for i, _, sample, xdev, labels in sweep_batches(dataloader, device, rank, world_size, preprocess_input_function):
         with torch.no_grad():
-            z, (n, h, w) = model._conv_rows(x.to(device))
+            z, (n, h, w) = model._conv_rows(xdev)
             _, _, dist = model._head(z, n, h * w, want_dist=True)
         base = int(i * search_batch_size)  # push_ProtoPNet.py:92
         _lib.check(lib.pasn_push_ppnet_update(
             dist.data_ptr(), z.data_ptr(), labels.data_ptr(), proto_class.data_ptr(), int(bool(class_specific)),
             state.dist.data_ptr(), state.index.data_ptr(), state.vec.data_ptr(), n, P, h * w, D, z.shape[-1],
             _lib.dtype_code(z.dtype), base, _lib.current_stream()))
-        if save:
-            hw, img_side = (h, w), int(x.shape[2])
-            img = state.index[:, 0]
-            here = (img >= base) & (img < base + n)
-            b = (img - base).clamp(0, n - 1)
-            new = (dist[b, torch.arange(P, device=device)], labels[b])  # (P, h*w) distance map of the winner image, (P,) its label
-            if rec is None:
-                rec = [torch.zeros_like(t) for t in new]
-            rec = [torch.where(here.view((P,) + (1,) * (t.dim() - 1)), t, r) for t, r in zip(new, rec)]
+        if records is not None:
+            meta = ((h, w), int(xdev.shape[2]))
+            # the winner image's (h*w) distance map and its label; the image column of the two-column index, copied once per batch
+            records.follow(state.index[:, :1].contiguous(), base, ("dmap", dist, True), ("labels", labels, False))
     local_index = state.index.clone()
     merged = _all_gather_states(state, merge_ppnet) if world_size > 1 else state.tensors()
-    if save:
-        if world_size > 1:
-            import torch.distributed as dist_
-
-            meta = [None] * world_size
-            dist_.all_gather_object(meta, (hw, img_side))
-            hw, img_side = next((m for m in meta if m[0] is not None), (None, None))
+    if records is not None:
+        rec = records.records(local_index[:, :1], world_size)
+        if world_size > 1 and rec is not None:
+            meta = first_across_ranks(meta)
             own_index, merged_img = local_index[:, 0], merged[1][:, 0]
             rec, _ = _reduce_records(rec, {}, torch.where((local_index == merged[1]).all(1), own_index, torch.full_like(own_index, -1)),
                                      merged_img, device)
         if rank == 0 and rec is not None:
-            _save_ppnet_artefacts(model, root_dir_for_saving_prototypes, epoch_number, merged, rec, hw, img_side, search_batch_size,
+            _save_ppnet_artefacts(model, root_dir_for_saving_prototypes, epoch_number, merged, rec, meta[0], meta[1], search_batch_size,
                                   save_prototype_class_identity, proto_bound_boxes_filename_prefix,
                                   prototype_self_act_filename_prefix, prototype_activation_function_in_numpy, log)
     return _finish(model, merged, model.prototype_shape, replace_prototypes, log, start)

@@ -47,6 +47,7 @@ Out of scope: wandb, plots, the ``classification_report`` t
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 from copy import deepcopy
@@ -71,6 +72,11 @@ def confusion_to_metrics(cm: torch.Tensor) -> Dict[str, object]:
     denom = support + predicted
     f1 = torch.where(denom > 0, 2 * tp / denom.clamp(min=1), torch.zeros_like(tp))
     return {"accuracy": accu, "f1": f1.tolist(), "f1_mean": float(f1.mean())}
+
+
+def _loader_capacity(loader) -> int:
+    """``len(loader) * batch_size`` when the loader knows both, else 0: the rows a per-clip device buffer is sized for."""
+    return len(loader) * int(getattr(loader, "batch_size", 0) or 0) if hasattr(loader, "__len__") else 0
 
 
 class DPTrainer:
@@ -418,9 +424,8 @@ class DPTrainer:
         batch_size`` when the loader knows both."""
         if self.device.type != "cuda":
             return None
-        cap = len(loader) * int(getattr(loader, "batch_size", 0) or 0) if hasattr(loader, "__len__") else 0
         return metrics_mod.EpochEvaluator(self.model, level=0.8, keep_logits=keep_logits, abstain_class=bool(self.config.get("abstain_class")),
-                                          capacity=cap)
+                                          capacity=_loader_capacity(loader))
 
     def write_prediction_log(self, epoch: int, mode: str, f1_mean: float, metas, ev) -> Optional[str]:
         """The reference's per-clip CSV (base.py:195-211; file name Video_XProtoNet_e2e.py:314-318).  With several ranks every rank's rows
@@ -499,27 +504,51 @@ class DPTrainer:
         ``SelectiveEvaluator`` holding every row's logits, probabilities, label and file name.  The model is left in the mode it was in;
         no collectives, no training or epoch state."""
         from . import selective
-        from .explain import _is_xproto
 
-        if not _is_xproto(self.model):
-            raise NotImplementedError("selective evaluation covers XProtoNet and Video_XProtoNet")
-        if self.device.type != "cuda":
-            raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
         abstain = bool(self.config.get("abstain_class"))
-        loader = self.data_loaders[mode]
-        cap = len(loader) * int(getattr(loader, "batch_size", 0) or 0) if hasattr(loader, "__len__") else 0
         path = self.CeLoss.ab_logitpath if abstain else "joined"
-        sel = selective.SelectiveEvaluator(self.model, abstain, score=score, ab_logitpath=path, capacity=cap)
+        with self._forward_only(mode, head_b="selective evaluation covers") as batches:
+            sel = selective.SelectiveEvaluator(self.model, abstain, score=score, ab_logitpath=path,
+                                               capacity=_loader_capacity(self.data_loaders[mode]))
+            for sample, x in batches:
+                logit, similarities, _ = self.model(x)
+                sel.update(logit, similarities, sample["target_AS"].to(self.device, non_blocking=True), list(sample["filename"]))
+        return sel
+
+    @contextlib.contextmanager
+    def _forward_only(self, mode: str, head_b: Optional[str] = None, max_clips: Optional[int] = None):
+        """A forward-only pass over ``data_loaders[mode]``: for the length of the ``with`` block the model is in eval mode under
+        ``torch.no_grad()``, and the mode it was in comes back however the block ends.  The block receives the generator of
+        ``(sample, x)``: the ``staged`` samples and their ``prepare_input`` clips, ending after ``max_clips`` clips.  ``head_b``
+        ("<feature> covers"): the pass is for XProtoNet / Video_XProtoNet on the GPU and refuses anything else."""
+        if head_b is not None:
+            from .explain import _is_xproto
+
+            if not _is_xproto(self.model):
+                raise NotImplementedError(f"{head_b} XProtoNet and Video_XProtoNet")
+            if self.device.type != "cuda":
+                raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
+        if max_clips is not None and max_clips < 1:
+            raise ValueError(f"max_clips must be positive, got {max_clips}")
+
+        def batches():
+            seen = 0
+            for sample in self.staged(self.data_loaders[mode]):
+                x = self.prepare_input(sample["cine"])
+                if max_clips is not None:
+                    x = x[: max_clips - seen]
+                yield sample, x
+                seen += int(x.shape[0])
+                if max_clips is not None and seen >= max_clips:
+                    break
+
         was_training = self.model.training
         self.model.eval()
         try:
             with torch.no_grad():
-                for sample in self.staged(loader):
-                    logit, similarities, _ = self.model(self.prepare_input(sample["cine"]))
-                    sel.update(logit, similarities, sample["target_AS"].to(self.device, non_blocking=True), list(sample["filename"]))
+                yield batches()
         finally:
             self.model.train(was_training)
-        return sel
 
     def fit_temperature(self, mode: str = "val") -> Dict[str, object]:
         """Temperature scaling fitted on the clips of ``data_loaders[mode]`` (``calibration.fit_temperature``; the sweep of
@@ -546,31 +575,12 @@ class DPTrainer:
         ends the sweep after that many clips.  Each rank sweeps its own loader; no collectives, no training or epoch state; the model is
         left in the mode it was in."""
         from . import faithfulness
-        from .explain import _is_xproto
 
-        if not _is_xproto(self.model):
-            raise NotImplementedError("faithfulness curves cover XProtoNet and Video_XProtoNet")
-        if self.device.type != "cuda":
-            raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
-        if max_clips is not None and max_clips < 1:
-            raise ValueError(f"max_clips must be positive, got {max_clips}")
-        acc = faithfulness.FaithfulnessAccumulator(self.model, select=select, steps=steps, max_batch=max_batch,
-                                                   abstain_class=bool(self.config.get("abstain_class")), seed=seed)
-        was_training = self.model.training
-        self.model.eval()
-        seen = 0
-        try:
-            with torch.no_grad():
-                for sample in self.staged(self.data_loaders[mode]):
-                    x = self.prepare_input(sample["cine"])
-                    if max_clips is not None:
-                        x = x[: max_clips - seen]
-                    acc.update(x)
-                    seen += int(x.shape[0])
-                    if max_clips is not None and seen >= max_clips:
-                        break
-        finally:
-            self.model.train(was_training)
+        with self._forward_only(mode, head_b="faithfulness curves cover", max_clips=max_clips) as batches:
+            acc = faithfulness.FaithfulnessAccumulator(self.model, select=select, steps=steps, max_batch=max_batch,
+                                                       abstain_class=bool(self.config.get("abstain_class")), seed=seed)
+            for _, x in batches:
+                acc.update(x)
         res = acc.result()
         self.log(f"Epoch: {self.current_epoch} | {mode} | faithfulness ({res['clips']} clips) | deletion AUC (prob) "
                  f"{float(res['deletion']['auc_prob'].mean()):.4f} vs random {float(res['random']['deletion']['auc_prob'].mean()):.4f} | "
@@ -599,20 +609,17 @@ class DPTrainer:
         The model is left in the mode it was in; no training state is touched."""
         epoch = self.current_epoch
         self.log(f"Epoch: {epoch} generating the sim scores for dataset:{mode}")
-        was_training = self.model.training
         if self.world_size > 1:
             self.sync_norm_buffers()
-        self.model.eval()
         sims, targets = [], []
-        with torch.no_grad():
-            for sample in self.staged(self.data_loaders[mode]):
-                _, similarities, _ = self.model(self.prepare_input(sample["cine"]))
+        with self._forward_only(mode) as batches:
+            for sample, x in batches:
+                _, similarities, _ = self.model(x)
                 sims.append(similarities.float())
                 targets.append(torch.as_tensor(sample["target_AS"]).detach().cpu().to(torch.float32))
         P = self.model.num_prototypes
         sim_scores = torch.cat(sims).cpu() if sims else torch.empty((0, P), dtype=torch.float32)
         y_true_all = torch.cat(targets) if targets else torch.empty((0,), dtype=torch.float32)
-        self.model.train(was_training)
         if self.world_size > 1:
             every = [None] * self.world_size
             dist.all_gather_object(every, (sim_scores, y_true_all))

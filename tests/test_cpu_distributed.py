@@ -87,6 +87,33 @@ def test_sharded_push_without_a_process_group_is_refused():
     _require_group(1)
 
 
+def test_saving_push_names_its_prototype_limit_before_the_sweep(tmp_path):
+    """The winners' records follow them through pasn_topk_gather (P <= 4096): a saving push with more prototypes says so before it
+    touches the loader, for both model kinds."""
+    from protoasnet_amd import push
+
+    class Model(torch.nn.Module):
+        num_prototypes, num_classes, prototype_shape = 4100, 4, (4100, 8, 1, 1)
+        prototype_class_identity = torch.zeros(4100, 4)
+
+        def __init__(self):
+            super().__init__()
+            self.prototype_vectors = torch.nn.Parameter(torch.zeros(self.prototype_shape))
+
+    class Untouched:
+        batch_size = 4
+
+        def __len__(self):
+            return 3
+
+        def __iter__(self):
+            raise AssertionError("the sweep started")
+
+    for fn in (push.push_prototypes, push.push_prototypes_ppnet):
+        with pytest.raises(ValueError, match="at most 4096 prototypes"):
+            fn(Untouched(), Model(), root_dir_for_saving_prototypes=str(tmp_path), log=lambda *_: None)
+
+
 def test_shard_iteration_offsets_come_from_the_sampler_not_the_rank():
     """A torch DataLoader is re-instantiated over the rank's slice of its batch_sampler: foreign batches are never loaded and the
     global clip offsets are the sampler's prefix sums (ragged batches included), identical on every rank."""

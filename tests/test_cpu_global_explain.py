@@ -167,6 +167,52 @@ def test_filenames_follow_the_global_index():
     assert global_explain._filenames(names, index) == [["c0", "a0", "b0"], ["c1", "a2", None]]
 
 
+def _filenames_by_base_scan(names, index):
+    """The push's former spelling: per index the largest batch base at or below it."""
+    bases = sorted(names)
+    files = []
+    for g in index.tolist():
+        base = max([b for b in bases if b <= g], default=None) if g >= 0 else None
+        files.append(names[base][g - base] if base is not None and g - base < len(names[base]) else None)
+    return files
+
+
+def _filenames_by_searchsorted(names, index):
+    """The global explanation's former spelling, row by row."""
+    import numpy as np
+
+    bases = np.array(sorted(names), dtype=np.int64)
+    out = []
+    for row in index.numpy().astype(np.int64):
+        files = []
+        for g in row:
+            at = int(np.searchsorted(bases, g, side="right")) - 1 if g >= 0 and bases.size else -1
+            batch = names[int(bases[at])] if at >= 0 else []
+            off = int(g - bases[at]) if at >= 0 else 0
+            files.append(batch[off] if at >= 0 and off < len(batch) else None)
+        out.append(files)
+    return out
+
+
+def test_filenames_at_equals_both_former_spellings():
+    from protoasnet_amd.sweep import filenames_at
+
+    assert global_explain._filenames is filenames_at
+    hand = {0: ["a0", "a1", "a2"], 3: ["b0"], 4: ["c0", "c1"]}
+    cases = [(hand, torch.tensor([[4, 0, 3], [5, 2, -1]])),
+             # the push's cases: never won, an index equal to a base, an index past the last batch's names, "" defaults, no names at all
+             ({0: ["", ""], 2: ["x", "y"], 4: ["z"]}, torch.tensor([[-1, 0, 2, 4], [5, 9, 3, 1]])),
+             ({}, torch.tensor([[-1, 0, 7]]))]
+    for names, index in cases:
+        want = _filenames_by_searchsorted(names, index)
+        assert filenames_at(names, index) == want
+        assert [_filenames_by_base_scan(names, row) for row in index] == want
+        assert filenames_at(names, index.flatten()) == [f for row in want for f in row]  # the push's (P,) index: a flat list
+    assert filenames_at(hand, torch.tensor([[4, 0, 3], [5, 2, -1]])) == [["c0", "a0", "b0"], ["c1", "a2", None]]
+    assert filenames_at({0: ["", ""], 2: ["x", "y"], 4: ["z"]}, torch.tensor([-1, 2, 5, 4])) == [None, "x", None, "z"]
+    assert filenames_at({}, torch.tensor([-1, 0])) == [None, None]
+
+
 # ------------------------------------------------------------------------------------------------- the reference's file names
 class _Agent:
     """The two methods under test need ``config`` only."""

@@ -180,6 +180,32 @@ def test_sharded_push_refuses_a_shuffling_loader():
     assert next(push._iter_shard(torch.utils.data.DataLoader(ds, batch_size=2, shuffle=False), 1, 2))[0] == 2
 
 
+def test_get_sim_scores_restores_the_mode_when_the_loader_raises(tmp_path):
+    """An exception inside the sweep used to leave the model in eval mode; a clean sweep still writes the reference's two files."""
+    from protoasnet_amd.trainer import DPTrainer
+
+    b = _batches(5, 3)
+
+    def breaking():
+        yield b[0]
+        raise OSError("the second batch cannot be read")
+
+    cfg = {"abstain_class": True, "save_dir": str(tmp_path), "train": dict(TRAIN_CFG)}
+    t = DPTrainer(Toy(), cfg, {"train": b, "val": b[:2], "broken": breaking()}, log=lambda *_: None)
+    for training in (True, False):
+        t.data_loaders["broken"] = breaking()
+        t.model.train(training)
+        with pytest.raises(OSError, match="second batch"):
+            t.get_sim_scores("broken")
+        assert t.model.training is training and torch.is_grad_enabled()
+    t.model.train()
+    t.get_sim_scores("val")
+    assert t.model.training
+    sims, targets = t.load_sim_scores(0, "val")
+    assert sims.shape == (4, 8) and sims.dtype == torch.float32
+    assert torch.equal(targets, torch.cat([s["target_AS"] for s in b[:2]]).float())
+
+
 def test_optimizer_groups_scheduler_and_checkpoint_follow_the_reference(tmp_path):
     from protoasnet_amd.trainer import DPTrainer, confusion_to_metrics
 

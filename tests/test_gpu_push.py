@@ -101,6 +101,90 @@ def test_ppnet_push_kernel_bit_exact(class_specific):
     assert np.array_equal(vec, ref_p[:, :, 0, 0].astype(np.float32))
 
 
+def _chain(index, base, B, new, rec):
+    """The formulation the store replaces: a prototype whose current winner ``index`` (P,) lies in this batch takes the batch's row."""
+    here = (index >= base) & (index < base + B)
+    rec = rec if rec is not None else [torch.zeros_like(t) for t in new(torch.zeros_like(index))]
+    return [torch.where(here.view((-1,) + (1,) * (t.dim() - 1)), t, r) for t, r in zip(new((index - base).clamp(0, B - 1)), rec)]
+
+
+def test_winner_store_at_k1_equals_the_record_chain_xproto():
+    """The records of a saving push (occurrence map, logits, clip, label of each prototype's winner) through ``WinnerStore`` with k = 1
+    against the ``here`` / ``clamp`` / ``torch.where`` chain it replaces, applied after every ``pasn_push_xproto_update``: bitwise equal,
+    the clip kept in bf16 and widened once at the end; ties inside and across batches (distances in quarters); class 2 has no clip, so
+    its prototypes never win and keep all-zero records.  (The push itself sends its megabyte clip rows through
+    ``push._Records.follow_wide``; ``test_push_prototypes_writes_reference_pickle`` checks those.)"""
+    from protoasnet_amd import _lib
+    from protoasnet_amd.push import PushState, xproto_class_mask
+    from protoasnet_amd.sweep import WinnerStore
+
+    rng = np.random.default_rng(3)
+    P, D, K = 40, 16, 4
+    cls = torch.argmax(oracle.heads.prototype_class_identity(P, K), dim=1).to(torch.int32).to(DEV)
+    mask = xproto_class_mask(P, K, True, True).to(DEV)
+    state, store = PushState(P, D, DEV), WinnerStore(P, 1, DEV)
+    slot, ar = torch.zeros((P, 1), dtype=torch.int32, device=DEV), torch.arange(P, device=DEV)
+    rec, base = None, 0
+    for B in (8, 8, 8, 8, 8, 5):
+        dist = torch.from_numpy((np.round(rng.random((B, P)) * 4) / 4).astype(np.float32)).to(DEV)
+        feats = torch.from_numpy(rng.standard_normal((B, P, D)).astype(np.float32)).to(DEV)
+        labels = torch.from_numpy(rng.choice([0, 1], B).astype(np.int64)).to(DEV)
+        occ = torch.from_numpy(rng.standard_normal((B, P, 1, 2, 3, 3)).astype(np.float32)).to(DEV)
+        logits = torch.from_numpy(rng.standard_normal((B, 4)).astype(np.float32)).to(DEV)
+        clips = torch.from_numpy(rng.standard_normal((B, 3, 2, 4, 4)).astype(np.float32)).to(DEV).to(torch.bfloat16)
+        _lib.check(_lib.lib().pasn_push_xproto_update(dist.data_ptr(), feats.data_ptr(), labels.data_ptr(), cls.data_ptr(), mask.data_ptr(),
+                                                      state.dist.data_ptr(), state.index.data_ptr(), state.vec.data_ptr(), B, P, D, base,
+                                                      _lib.current_stream()))
+        rec = _chain(state.index, base, B, lambda b: (occ[b, ar], logits[b], clips[b].float(), labels[b]), rec)
+        for name, payload, per_proto in (("occ", occ, True), ("logits", logits, False), ("clips", clips, False), ("labels", labels, False)):
+            store.gather(name, payload, per_proto, state.index.view(P, 1), slot, base, fill=0)
+        base += B
+    index = state.index.view(P, 1)
+    got = [store.resolved(name, index, slot)[:, 0] for name in ("occ", "logits", "clips", "labels")]
+    assert got[2].dtype == torch.bfloat16 and got[3].dtype == torch.int64
+    got[2] = got[2].float()
+    never = state.index < 0
+    assert never.tolist() == (cls == 2).tolist() and int(never.sum()) == 10  # the abstention block compares with every clip
+    assert len(set((state.index[~never] // 8).tolist())) > 1  # the winners come from more than one batch
+    for g, w in zip(got, rec):
+        assert g.shape == w.shape and g.dtype == w.dtype and torch.equal(g, w)
+        assert not bool(g[never].any()) and bool(g[~never].any())
+
+
+def test_winner_store_at_k1_equals_the_record_chain_ppnet():
+    """The same for the PPNet push: the image column of the two-column index ``pasn_push_ppnet_update`` keeps, the (n, P, h*w) distance map
+    as a per-prototype payload and the labels per image; batches of 4, 4, 3 images at bases i * 4 (push_ProtoPNet.py:92)."""
+    from protoasnet_amd import _lib
+    from protoasnet_amd.push import PushState
+    from protoasnet_amd.sweep import WinnerStore
+
+    rng = np.random.default_rng(4)
+    P, D, K, S, bs = 12, 8, 3, 9, 4
+    cls = torch.argmax(oracle.heads.prototype_class_identity(P, K), dim=1).to(torch.int32).to(DEV)
+    state, store = PushState(P, D, DEV, ppnet=True), WinnerStore(P, 1, DEV)
+    slot, ar = torch.zeros((P, 1), dtype=torch.int32, device=DEV), torch.arange(P, device=DEV)
+    rec = None
+    for i, n in enumerate((4, 4, 3)):
+        dist = torch.from_numpy((np.round(rng.random((n, P, S)) * 4) / 4).astype(np.float32)).to(DEV)
+        z = torch.from_numpy(rng.standard_normal((n, S, D)).astype(np.float32)).to(DEV)
+        labels = torch.from_numpy(rng.choice([0, 1], n).astype(np.int64)).to(DEV)
+        _lib.check(_lib.lib().pasn_push_ppnet_update(dist.data_ptr(), z.data_ptr(), labels.data_ptr(), cls.data_ptr(), 1,
+                                                     state.dist.data_ptr(), state.index.data_ptr(), state.vec.data_ptr(), n, P, S, D, D,
+                                                     _lib.dtype_code(z.dtype), i * bs, _lib.current_stream()))
+        rec = _chain(state.index[:, 0], i * bs, n, lambda b: (dist[b, ar], labels[b]), rec)
+        image = state.index[:, :1].contiguous()
+        store.gather("dmap", dist, True, image, slot, i * bs, fill=0)
+        store.gather("labels", labels, False, image, slot, i * bs, fill=0)
+    image = state.index[:, :1]
+    got = [store.resolved(name, image, slot)[:, 0] for name in ("dmap", "labels")]
+    never = image[:, 0] < 0
+    assert never.tolist() == (cls == 2).tolist()
+    assert len(set(image[:, 0][~never].tolist())) > 1  # the first image wins a full tie: more than one winner image all the same
+    for g, w in zip(got, rec):
+        assert g.shape == w.shape and g.dtype == w.dtype and torch.equal(g, w)
+        assert not bool(g[never].any())
+
+
 class _Loader(list):
     batch_size = 4
 
