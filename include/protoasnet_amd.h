@@ -870,6 +870,77 @@ int pasn_perturb_curves(const float* sim, const float* logits, const int32_t* se
                         int S1, int P, int K, int K_real, long V, float* curve_sim, float* curve_prob, double* auc, double* acc,
                         void* stream);
 
+/* Robustness (robustness.py): echo-style corruptions of a clip, and the stability of the prediction and of its explanation under them.
+ * Does the prototype explanation survive the perturbations the class prediction survives?  The reference has no code for it; these
+ * definitions are the specification.  Every call is stream-ordered: no host synchronisation, no allocation, no global atomics, no block
+ * waiting on another.
+ *
+ * pasn_clip_corrupt: one launch, normalised clip in, corrupted normalised clip out.  x, y [N][C][T][H][W] (planar, the model's input;
+ * T = 1 for images), C = 1 or 3, dtype PASN_F32 / PASN_BF16 on both sides.  The descriptor holds the optional stages; a stage that is
+ * NULL or zero is off:
+ *   src_t [N][T] int32 in DEVICE memory or NULL   frame hold: output frame t is computed from input frame src_t[n][t], clamped to [0, T)
+ *   taps [2R+1] fp32 in DEVICE memory, 0 <= R <= 8  separable blur over H and W with edge replication (R = 0: off, taps may be NULL)
+ *   row_a, row_b [H] fp32 in DEVICE memory or NULL  photometric stage per image row (row = depth): gain, contrast, depth attenuation;
+ *                                                 it is on when either is given, a NULL row_a then counts as ones, a NULL row_b as zeros
+ *   sigma_add, sigma_mul fp32                     additive noise, multiplicative speckle
+ *   seed uint64; mean, stdv fp32                  the noise stream; the clip's normalisation
+ * Per output element (n, c, t, h, w), every fp32 operation rounded on its own (no contraction):
+ *   1. ts = src_t ? clamp(src_t[n][t], 0, T - 1) : t
+ *   2. blur, photometric stage and both sigmas all off: y is a bitwise copy of x[n][c][ts][h][w]; steps 3 - 8 are skipped
+ *   3. pixel domain: v(h', w') = widen(x[n][c][ts][h'][w']) * stdv + mean
+ *   4. blur (R > 0): row pass g(h', w) = sum_{i = -R .. R} taps[i + R] * v(h', clamp(w + i, 0, W - 1)), accumulated from 0.0f with i
+ *      ascending as acc = acc + (tap * v); column pass: the same over h on g.  H or W smaller than R is legal.
+ *   5. photometric: v = row_a[h] * v + row_b[h]
+ *   6. noise: z is shared by the C channels of a voxel (a grey clip stays grey): Philox4x32-10 with key (seed lo, seed hi) and counter
+ *      (q lo, q hi, n, 0), q = (t H + h) W + w of the OUTPUT voxel, gives r0 .. r3;
+ *        z = (float)(int32)((r0 >> 8) + (r1 >> 8) + (r2 >> 8) + (r3 >> 8) - 33554430) * c,  c = the fp32 nearest sqrt(3) * 2^-24.
+ *      z is an Irwin-Hall(4) variate of unit variance bounded at +-3.47: it is NOT a Gaussian (no tails).  Only integers and one
+ *      conversion go into it, so numpy reproduces it bit for bit.  Then v = v + sigma_add * z (when sigma_add != 0), and after that
+ *      v = v + (sigma_mul * z) * v (when sigma_mul != 0).
+ *   7. v = fminf(fmaxf(v, 0), 1); NaN gives 0
+ *   8. y = (v - mean) / stdv, IEEE division, rounded once to the dtype (to nearest even)
+ * A block owns a 32 x 64 tile of one (n, t) with its R-wide halo in LDS, the row pass goes into LDS, the column pass reads it; the block
+ * walks the C channels.  16-byte stores where the output address allows, element by element at a row's head and tail.  Instances: blur
+ * on / off x dtype.  NULL x, y or descriptor, R outside [0, 8], R > 0 without taps, C not 1 or 3, a size <= 0, another dtype or
+ * more than 2^31 - 1 tiles return PASN_ERR_ARG before any launch.
+ *
+ * pasn_stability_stats: compare the clean (a) and the corrupted (b) forward of the same clips.  logits_a, logits_b [N][K], sim_a, sim_b
+ * [N][P], occ_a, occ_b [N][P][S] fp32 (push_forward's occurrence maps on the feature grid (Ti, Hi, Wi), S = Ti Hi Wi), labels [N] int32
+ * or NULL.  P % K == 0, G = P / K, 1 <= k <= G, 1 <= m <= S.  pred_a, pred_b: the argmax over [0, K_real) with pasn_explain_rank's rule
+ * (lowest index on ties, NaN largest).  sel_a: the first k of pred_a's class block by sim_a in pasn_explain_rank's order (descending,
+ * the higher index first on ties); sel_b: the first k of THE SAME block by sim_b.
+ *   clip [N][4] fp64:    flip (pred_b != pred_a as 0 / 1); tv = 0.5 sum_c |p_a - p_b| with the softmax over K_real in fp64 (largest logit
+ *                        subtracted, sums in class order); p_a[pred_a] - p_b[pred_a]; |sel_a and sel_b| / k
+ *   correct [N][2] int32 (pred_a == label, pred_b == label), written when labels is given (then required)
+ *   sel [N][k] int32:    sel_a
+ *   pair [N][k][4] fp64, for p = sel_a[n][j]:
+ *     dsim   (double)sim_b[n][p] - (double)sim_a[n][p]
+ *     corr   Pearson correlation of the two maps over S: mean = (sum in index order) / S; saa = sum (a - mean_a)^2, sbb, sab likewise,
+ *            fp64 in index order; corr = sab / sqrt(saa * sbb); 1 when saa and sbb are both exactly 0, 0 when exactly one is
+ *     iou    of the two top-m sets, a map's top set being its m voxels first in (value DESCENDING, index ASCENDING):
+ *            (double)inter / (double)(2 m - inter), integers in, so exact
+ *     shift  sqrt(dt^2 + dh^2 + dw^2) / sqrt((Ti-1)^2 + (Hi-1)^2 + (Wi-1)^2) between the two argmax positions (lowest index on ties) in
+ *            (t, h, w) grid units; 0 when S = 1
+ *   acc [6 + 4 k + 1] fp64 or NULL, the caller's running sums (zeroed by the caller), added with n ascending: the 4 clip statistics, the
+ *                        2 correct counts (0 without labels), pair [k][4], N
+ * Two calls are bitwise equal.  Maps holding NaN give unspecified statistics (nothing is read out of bounds).  At most three launches:
+ * one wave per clip; one block per (n, j) that holds both maps in LDS and ranks them by counting; one block for acc.
+ * S > 4096 returns PASN_ERR_UNSUPPORTED (no slow path); 1 <= N <= 65 535, 1 <= K_real <= K, P <= 16 384, k <= 4096; anything else, or a NULL
+ * pointer among the required ones, returns PASN_ERR_ARG before any launch. */
+typedef struct pasn_corrupt_desc {
+    const int32_t* src_t;
+    const float* taps;
+    const float* row_a;
+    const float* row_b;
+    uint64_t seed;
+    int32_t R;
+    float sigma_add, sigma_mul, mean, stdv;
+} pasn_corrupt_desc;
+int pasn_clip_corrupt(const void* x, void* y, int N, int C, int T, int H, int W, int dtype, const pasn_corrupt_desc* desc, void* stream);
+int pasn_stability_stats(const float* logits_a, const float* logits_b, const float* sim_a, const float* sim_b, const float* occ_a,
+                         const float* occ_b, const int32_t* labels, int N, int K, int K_real, int P, int Ti, int Hi, int Wi, int k, int m,
+                         double* clip, int32_t* correct, int32_t* sel, double* pair, double* acc, void* stream);
+
 /* Global explanations: the k nearest clips of a split per prototype, kept on the device while a loader is swept (global_explain.py).
  * The reference ships only the raw material, the whole (clips, P) similarity matrix "for ranking prototypes"
  * (XProtoNet_Base.py:613-656 get_sim_scores / load_sim_scores; explain_global is a stub); the selection rule per batch is the push's

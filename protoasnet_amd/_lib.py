@@ -34,6 +34,11 @@ class ProtoLossDesc(ctypes.Structure):
                 + [(n, c_float) for n in ("w_ce", "ab_weight", "w_cluster", "w_sep", "w_ortho", "w_map", "w_fc")])
 
 
+class CorruptDesc(ctypes.Structure):
+    _fields_ = ([(n, c_void_p) for n in ("src_t", "taps", "row_a", "row_b")] + [("seed", c_uint64), ("R", c_int32)]
+                + [(n, c_float) for n in ("sigma_add", "sigma_mul", "mean", "stdv")])
+
+
 OPTIM_MAX_GROUPS = 8  # PASN_OPTIM_MAX_GROUPS
 
 
@@ -181,6 +186,9 @@ SIGNATURES = {
     "pasn_perturb_steps": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),
     "pasn_perturb_apply": (c_int, [c_void_p] * 4 + [c_float, c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
     "pasn_perturb_curves": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_long] + [c_void_p] * 5),
+    # ---- robustness: clip corruptions and explanation stability (robustness.py)
+    "pasn_clip_corrupt": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [POINTER(CorruptDesc), c_void_p]),
+    "pasn_stability_stats": (c_int, [c_void_p] * 7 + [c_int] * 9 + [c_void_p] * 6),
     # ---- the training loss recipe (losses.FusedCriterion)
     "pasn_proto_loss_fwd": (c_int, [c_void_p] * 13 + [POINTER(ProtoLossDesc), c_void_p]),
     "pasn_proto_loss_bwd": (c_int, [c_void_p] * 14 + [POINTER(ProtoLossDesc), c_void_p]),

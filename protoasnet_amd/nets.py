@@ -460,6 +460,12 @@ class _XProtoHeadMixin:
 
         return perturbation_curves(self, x, **kw)
 
+    def robustness(self, x: torch.Tensor, corruption, severity=None, **kw):
+        """Stability of the prediction and of its occurrence maps on the clips ``x`` under one corruption (robustness.robustness)."""
+        from .robustness import robustness
+
+        return robustness(self, x, corruption, severity, **kw)
+
 
 class XProtoNet(_XProtoHeadMixin, PPNet):
     """Image ProtoASNet / XProtoNet (reference src/models/XProtoNet.py:8-106) -- head B on a 2-D trunk."""

@@ -51,7 +51,7 @@ import contextlib
 import logging
 import os
 from copy import deepcopy
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import torch
 import torch.distributed as dist
@@ -586,6 +586,31 @@ class DPTrainer:
                  f"{float(res['deletion']['auc_prob'].mean()):.4f} vs random {float(res['random']['deletion']['auc_prob'].mean()):.4f} | "
                  f"insertion AUC (prob) {float(res['insertion']['auc_prob'].mean()):.4f} vs random "
                  f"{float(res['random']['insertion']['auc_prob'].mean()):.4f}")
+        return res
+
+    def evaluate_robustness(self, mode: str = "val", corruptions: Optional[Sequence[str]] = None, severities: Sequence[int] = (1, 3, 5),
+                            select: int = 1, top_fraction: float = 0.1, max_clips: Optional[int] = None, seed: int = 0) -> Dict[str, object]:
+        """Do the prediction and its explanation survive echo-style corruptions of ``data_loaders[mode]``?
+        (``protoasnet_amd.robustness``)  An eval-mode sweep: per batch (through ``prepare_input``) one clean ``push_forward`` and one
+        corrupted one per (corruption, severity) cell (``corruptions=None``: all of ``robustness.CORRUPTIONS``), compared on the device
+        and summed in fp64 there, read once.  Returns ``RobustnessAccumulator.result()``: per cell the accuracy clean and corrupted, the
+        flip rate, the mean total variation and probability drop, the top-``select`` prototype overlap and per prototype rank the mean
+        similarity change, map correlation, top-set IoU and argmax shift.  ``max_clips`` ends the sweep after that many clips.  Each
+        rank sweeps its own loader; no collectives, no training or epoch state; the model is left in the mode it was in."""
+        from . import robustness
+
+        with self._forward_only(mode, head_b="robustness evaluation covers", max_clips=max_clips) as batches:
+            acc = robustness.RobustnessAccumulator(self.model, corruptions=corruptions, severities=severities, select=select,
+                                                   top_fraction=top_fraction, seed=seed, abstain_class=bool(self.config.get("abstain_class")))
+            for sample, x in batches:
+                acc.update(x, torch.as_tensor(sample["target_AS"])[: int(x.shape[0])])
+        res = acc.result()
+        for name, by_severity in res["cells"].items():
+            for sev, c in by_severity.items():
+                self.log(f"Epoch: {self.current_epoch} | {mode} | robustness ({res['clips']} clips) | {name} severity {sev} | accuracy "
+                         f"{c['acc_clean']:.4f} -> {c['acc_corrupted']:.4f} | flip rate {c['flip_rate']:.4f} | tv {c['tv']:.4f} | "
+                         f"prob drop {c['prob_drop']:.4f} | top-{select} overlap {c['overlap']:.4f} | map corr {float(c['corr'][0]):.4f} | "
+                         f"IoU {float(c['iou'][0]):.4f} | shift {float(c['shift'][0]):.4f}")
         return res
 
     def push(self, replace_prototypes: bool = True):
