@@ -221,7 +221,7 @@ __device__ __forceinline__ long long boot_sweep(const uint32_t* __restrict__ og,
             }
             tot += (word[e] & BOOT_POS) ? (unsigned long long)w[e] << 32 : (unsigned long long)w[e];
         }
-        const unsigned long long inc = wave_scan_incl_u64(tot);
+        const unsigned long long inc = wave_scan_incl(tot);
         const unsigned long long ex_w = inc - tot;
         unsigned long long ps = ex_w + rel_snap;  // the latest tie start at or before this thread's last position, relative to the wave
         int pf = hf;

@@ -14,6 +14,7 @@
 // block per (n, j): both maps in LDS, fp64 moments in index order by one lane each, ranks by counting), then one block adds onto acc.
 #include "common.h"
 #include "eval_common.h"
+#include "explain_common.h"
 #include "philox.h"
 
 #pragma clang fp contract(off)
@@ -35,16 +36,6 @@ struct CorruptArgs {
     int copy, photo, noise;
 };
 
-__device__ __forceinline__ float cr_widen(uint32_t u) { return __uint_as_float(u); }
-__device__ __forceinline__ float cr_widen(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-// one rounding to the dtype, to nearest even (a NaN cannot arrive: the clamp removed it)
-template <typename U>
-__device__ __forceinline__ U cr_narrow(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if constexpr (sizeof(U) == 4) return u;
-    else return (U)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 // The Irwin-Hall(4) variate of output voxel q of clip n: integers and one conversion, then one product.  NOT a Gaussian.
 __device__ __forceinline__ float cr_z(uint32_t k0, uint32_t k1, long q, int n) {
     uint32_t r[4];
@@ -53,7 +44,8 @@ __device__ __forceinline__ float cr_z(uint32_t k0, uint32_t k1, long q, int n) {
     return (float)s * CR_ZC;
 }
 
-// steps 5 - 8 of the definition on a pixel-domain value; returns the normalised value before its rounding to the dtype
+// steps 5 - 8 of the definition on a pixel-domain value; returns the normalised value before its rounding to the dtype (raw_narrow: no
+// NaN can arrive there, the clamp removed it)
 __device__ __forceinline__ float cr_finish(const CorruptArgs& a, float v, float ra, float rb, float z) {
     if (a.photo) v = ra * v + rb;
     if (a.sigma_add != 0.0f) v = v + a.sigma_add * z;
@@ -98,7 +90,7 @@ __global__ __launch_bounds__(CR_NT) void clip_corrupt_kernel(CorruptArgs a) {
             for (int i = tid; i < vh * vw; i += CR_NT) {
                 const int hh = i / vw, ww = i % vw;
                 const int gh = min(max(h0 - R + hh, 0), H - 1), gw = min(max(w0 - R + ww, 0), W - 1);
-                s_v[hh * CR_VW + ww] = cr_widen(xp[(long)gh * W + gw]) * a.stdv + a.mean;
+                s_v[hh * CR_VW + ww] = raw_widen(xp[(long)gh * W + gw]) * a.stdv + a.mean;
             }
             __syncthreads();
             for (int i = tid; i < vh * CR_TW; i += CR_NT) {
@@ -123,14 +115,13 @@ __global__ __launch_bounds__(CR_NT) void clip_corrupt_kernel(CorruptArgs a) {
             const int r = s / NSLOT, j = s % NSLOT;
             U* orow = yp + (long)(h0 + r) * W + w0;
             const U* xrow = xp + (long)(h0 + r) * W + w0;
-            const int lead = (int)(((16 - ((uintptr_t)orow & 15)) & 15) / sizeof(U));
-            const int e0 = lead + (j - 1) * EPV, lo = max(e0, 0), hi = min(e0 + EPV, cols);
+            const int e0 = lead_to_16(orow) + (j - 1) * EPV, lo = max(e0, 0), hi = min(e0 + EPV, cols);
             if (lo >= hi) continue;
             const bool full = hi - lo == EPV;
             U o[EPV];
             if constexpr (BLUR) {
 #pragma unroll
-                for (int e = 0; e < EPV; ++e) o[e] = cr_narrow<U>(s_v[r * CR_TW + min(max(e0 + e, 0), CR_TW - 1)]);
+                for (int e = 0; e < EPV; ++e) o[e] = raw_narrow<U>(s_v[r * CR_TW + min(max(e0 + e, 0), CR_TW - 1)]);
             } else {
                 if (full && (((uintptr_t)(xrow + e0)) & 15) == 0) {
                     const uint4 q = *reinterpret_cast<const uint4*>(xrow + e0);
@@ -144,7 +135,7 @@ __global__ __launch_bounds__(CR_NT) void clip_corrupt_kernel(CorruptArgs a) {
 #pragma unroll
                     for (int e = 0; e < EPV; ++e) {
                         const float z = a.noise ? s_z[r * CR_TW + min(max(e0 + e, 0), CR_TW - 1)] : 0.0f;
-                        o[e] = cr_narrow<U>(cr_finish(a, cr_widen(o[e]) * a.stdv + a.mean, ra, rb, z));
+                        o[e] = raw_narrow<U>(cr_finish(a, raw_widen(o[e]) * a.stdv + a.mean, ra, rb, z));
                     }
                 }
             }
@@ -172,29 +163,10 @@ struct StabArgs {
     double *pair, *acc;
 };
 
-// pasn_explain_rank's prediction: the first maximum of l[0 .. K_real), NaN counts as the largest value
-__device__ __forceinline__ int st_pred(const float* l, int K_real) {
-    int best = 0;
-    float bv = l[0];
-    for (int c = 1; c < K_real; ++c) {
-        const float v = l[c];
-        if (!(bv != bv) && (v > bv || v != v)) {
-            bv = v;
-            best = c;
-        }
-    }
-    return best;
-}
-
-// the first k of class block `base .. base + G` by similarity in pasn_explain_rank's order (descending, the HIGHER index first on ties)
+// the first k of class block `base .. base + G` in the order of explain_block_rank, which is pasn_explain_rank's
 __device__ __forceinline__ void st_select(const float* sim, int base, int G, int k, int32_t* out) {
     for (int p = base + (int)threadIdx.x; p < base + G; p += 64) {
-        const float v = sim[p];
-        int r = 0;
-        for (int q = base; q < base + G; ++q) {
-            const float o = sim[q];
-            r += (o > v || (o == v && q > p)) ? 1 : 0;
-        }
+        const int r = explain_block_rank(sim, base, G, p);
         if (r < k) out[r] = p;
     }
 }
@@ -204,7 +176,7 @@ __global__ __launch_bounds__(64) void stability_clip_kernel(StabArgs a) {
     __shared__ int s_hits;
     const int n = blockIdx.x, tid = threadIdx.x, K_real = a.K_real, k = a.k;
     const float *la = a.logits_a + (long)n * a.K, *lb = a.logits_b + (long)n * a.K;
-    const int pa = st_pred(la, K_real), pb = st_pred(lb, K_real);
+    const int pa = explain_pred(la, K_real), pb = explain_pred(lb, K_real);  // (pasn_explain_rank's prediction)
     const int G = a.P / a.K;
     if (tid == 0) s_hits = 0;
     for (int r = tid; r < 2 * k; r += 64) s_sel[r] = pa * G;  // a rank that NaN similarities leave out stays inside the block
@@ -335,22 +307,13 @@ __global__ __launch_bounds__(ST_NT) void stability_pair_kernel(StabArgs a) {
     out[3] = diag > 0 ? sqrt((double)(dt * dt + dh * dh + dw * dw)) / sqrt((double)diag) : 0.0;
 }
 
-// acc += the sums over the clips, n ascending: one thread per entry
+// acc = [clip statistics (4), correct counts (2), pair statistics (k, 4), N]
 __global__ __launch_bounds__(ST_NT) void stability_acc_kernel(StabArgs a) {
-    const int total = 6 + 4 * a.k + 1;
-    for (int e = threadIdx.x; e < total; e += ST_NT) {
-        double t = a.acc[e];
-        if (e == total - 1) {
-            t += (double)a.N;
-        } else {
-            for (long n = 0; n < a.N; ++n) {
-                if (e < 4) t += a.clip[n * 4 + e];
-                else if (e < 6) t += (a.labels && a.correct) ? (double)a.correct[n * 2 + (e - 4)] : 0.0;
-                else t += a.pair[n * 4 * a.k + (e - 6)];
-            }
-        }
-        a.acc[e] = t;
-    }
+    sweep_acc_add<ST_NT>(a.acc, 6 + 4 * a.k + 1, a.N, [&](long n, int e) {
+        if (e < 4) return a.clip[n * 4 + e];
+        if (e < 6) return (a.labels && a.correct) ? (double)a.correct[n * 2 + (e - 4)] : 0.0;
+        return a.pair[n * 4 * a.k + (e - 6)];
+    });
 }
 
 }  // namespace pasn
@@ -367,25 +330,10 @@ extern "C" int pasn_clip_corrupt(const void* x, void* y, int N, int C, int T, in
     PASN_REQUIRE(desc->R == 0 || desc->taps, "a blur (R > 0) needs its taps");
     const uintptr_t esz = dtype == PASN_BF16 ? 2 : 4;
     PASN_REQUIRE((((uintptr_t)x | (uintptr_t)y) & (esz - 1)) == 0, "x and y must be aligned to their element");
-    CorruptArgs a;
-    a.x = x;
-    a.y = y;
-    a.src_t = desc->src_t;
-    a.taps = desc->taps;
-    a.row_a = desc->row_a;
-    a.row_b = desc->row_b;
-    a.N = N, a.C = C, a.T = T, a.H = H, a.W = W, a.R = desc->R;
-    a.tilesH = (H + CR_TH - 1) / CR_TH;
-    a.tilesW = (W + CR_TW - 1) / CR_TW;
-    a.sigma_add = desc->sigma_add;
-    a.sigma_mul = desc->sigma_mul;
-    a.mean = desc->mean;
-    a.stdv = desc->stdv;
-    a.k0 = (uint32_t)desc->seed;
-    a.k1 = (uint32_t)(desc->seed >> 32);
-    a.photo = desc->row_a || desc->row_b;
-    a.noise = desc->sigma_add != 0.0f || desc->sigma_mul != 0.0f;
-    a.copy = desc->R == 0 && !a.photo && !a.noise;
+    const bool photo = desc->row_a || desc->row_b, noise = desc->sigma_add != 0.0f || desc->sigma_mul != 0.0f;
+    const CorruptArgs a{x, y, desc->src_t, desc->taps, desc->row_a, desc->row_b, N, C, T, H, W, desc->R, (H + CR_TH - 1) / CR_TH,
+                        (W + CR_TW - 1) / CR_TW, desc->sigma_add, desc->sigma_mul, desc->mean, desc->stdv, (uint32_t)desc->seed,
+                        (uint32_t)(desc->seed >> 32), desc->R == 0 && !photo && !noise, photo, noise};  // (the struct's field order)
     const long blocks = (long)N * T * a.tilesH * a.tilesW;
     PASN_REQUIRE(blocks <= 0x7fffffffL, "more than 2^31 - 1 tiles");
     const dim3 grid((unsigned)blocks);
@@ -419,11 +367,7 @@ extern "C" int pasn_stability_stats(const float* logits_a, const float* logits_b
     }
     PASN_REQUIRE(m >= 1 && m <= S, "m must lie in [1, S]");
     PASN_REQUIRE((long)N * k <= 0x7fffffffL, "more than 2^31 - 1 maps");
-    StabArgs a;
-    a.logits_a = logits_a, a.logits_b = logits_b, a.sim_a = sim_a, a.sim_b = sim_b, a.occ_a = occ_a, a.occ_b = occ_b;
-    a.labels = labels;
-    a.N = N, a.K = K, a.K_real = K_real, a.P = P, a.Ti = Ti, a.Hi = Hi, a.Wi = Wi, a.k = k, a.m = m;
-    a.clip = clip, a.correct = correct, a.sel = sel, a.pair = pair, a.acc = acc;
+    const StabArgs a{logits_a, logits_b, sim_a, sim_b, occ_a, occ_b, labels, N, K, K_real, P, Ti, Hi, Wi, k, m, clip, correct, sel, pair, acc};
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(stability_clip_kernel, dim3((unsigned)N), dim3(64), 2 * (size_t)k * sizeof(int32_t), s, a);
     hipLaunchKernelGGL(stability_pair_kernel, dim3((unsigned)((long)N * k)), dim3(ST_NT), 0, s, a);

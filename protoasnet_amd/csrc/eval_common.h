@@ -67,11 +67,12 @@ struct ClassTally {
     __device__ __forceinline__ double f1_mean(int K) const { return fsum / (double)K; }
 };
 
-// inclusive scan of a packed 64-bit word over the wave
-__device__ __forceinline__ unsigned long long wave_scan_incl_u64(unsigned long long inc) {
+// inclusive scan over the wave (T: uint32_t counts, or a packed 64-bit word)
+template <typename T>
+__device__ __forceinline__ T wave_scan_incl(T inc) {
     const int lane = threadIdx.x & 63;
     for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long v = __shfl_up(inc, o);
+        const T v = __shfl_up(inc, o);
         if (lane >= o) inc += v;
     }
     return inc;

@@ -2,9 +2,8 @@
 //
 // pasn_explain_rank: per clip, the class contributions W[k, p] * sim[p] and their sums sim @ W.T (local_explainability.py:91, :181-183),
 // the prototypes of each class block ordered by descending similarity (:112-125), the argmax of the non-abstain logits and the top
-// k_sel prototypes of the predicted class.  One workgroup per clip; the rank of prototype p inside its block is the number of block
-// members that beat it: sim[q] > sim[p], or sim[q] == sim[p] and q > p (reversing a stable ascending argsort), O((P/K)^2) comparisons
-// out of LDS, no sort network, deterministic.
+// k_sel prototypes of the predicted class.  One workgroup per clip; the rank of prototype p inside its block is explain_block_rank of
+// explain_common.h (the number of block members that beat it), O((P/K)^2) comparisons out of LDS, no sort network, deterministic.
 //
 // pasn_explain_maps: get_normalized_upsample_occurence_maps (explainability_utils.py:158-174) and the heat-map overlay (:177-200,
 // local_explainability.py:76, :104).  Per map, torch.nn.Upsample(size, trilinear | bilinear), align_corners=False:
@@ -21,6 +20,7 @@
 // falls outside [0, 1].  A block keeps the x-interpolated rows X(t0 | t1, h) of its band in LDS (2 x rows x Wo floats), so a voxel costs
 // four LDS reads and three fmas.
 #include "common.h"
+#include "explain_common.h"
 
 namespace pasn {
 
@@ -49,23 +49,18 @@ struct ExGeom {
     float st, sh, sw;  // in / out per axis
 };
 
-__device__ __forceinline__ float ex_block_min(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+// op (fminf / fmaxf) over the block's 256 values; every thread gets the result
+template <typename Op>
+__device__ __forceinline__ float ex_block_reduce(float v, float* red, Op op) {
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    v = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    v = op(op(red[0], red[1]), op(red[2], red[3]));
     return v;
 }
-
-__device__ __forceinline__ float ex_block_max(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    return v;
-}
+__device__ __forceinline__ float ex_block_min(float v, float* red) { return ex_block_reduce(v, red, [](float a, float b) { return fminf(a, b); }); }
+__device__ __forceinline__ float ex_block_max(float v, float* red) { return ex_block_reduce(v, red, [](float a, float b) { return fmaxf(a, b); }); }
 
 template <typename TS>
 __device__ __forceinline__ float ex_src(const TS* p) { return (float)*p; }
@@ -233,20 +228,7 @@ __global__ __launch_bounds__(256) void explain_rank_kernel(const float* __restri
     __shared__ int s_pred;
     const int n = blockIdx.x, tid = threadIdx.x;
     for (int p = tid; p < P; p += 256) s_sim[p] = sim[(long)n * P + p];
-    if (tid == 0) {  // torch.argmax: the first maximum; NaN counts as the largest value
-        const float* l = logits + (long)n * K;
-        int best = 0;
-        float bv = l[0];
-        for (int c = 1; c < K_real; ++c) {
-            const float v = l[c];
-            if (!(bv != bv) && (v > bv || v != v)) {
-                bv = v;
-                best = c;
-            }
-        }
-        s_pred = best;
-        pred[n] = best;
-    }
+    if (tid == 0) pred[n] = s_pred = explain_pred(logits + (long)n * K, K_real);
     __syncthreads();
     for (int c = 0; c < K; ++c) {
         const float* w = fc_w + (long)c * P;
@@ -267,12 +249,7 @@ __global__ __launch_bounds__(256) void explain_rank_kernel(const float* __restri
     const int G = P / K, pc = s_pred;
     for (int p = tid; p < G * K; p += 256) {
         const int base = (p / G) * G;
-        const float v = s_sim[p];
-        int r = 0;
-        for (int q = base; q < base + G; ++q) {
-            const float o = s_sim[q];
-            r += (o > v || (o == v && q > p)) ? 1 : 0;
-        }
+        const int r = explain_block_rank(s_sim, base, G, p);
         order[(long)n * P + base + r] = p;
         if (rank) rank[(long)n * P + p] = r;
         if (sel && base == pc * G && r < k_sel) sel[(long)n * k_sel + r] = p;

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "eval_common.h"
+#include "explain_common.h"
 
 namespace pasn {
 
@@ -134,16 +135,6 @@ __device__ __forceinline__ int steps_at(const int32_t* counts, int S1, long pos)
     return n;
 }
 
-// inclusive scan over the wave
-__device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t inc) {
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    return inc;
-}
-
 // One block of PLAN_NT threads per map.  Thread (g, L) adds the tiles g, g + 4, ... of level L (eight loads in flight); threads L < 256
 // then own level L; at the end a wave per straddling level scans its counts over the tiles.
 __global__ __launch_bounds__(PLAN_NT) void perturb_plan_kernel(const int32_t* __restrict__ counts, int S1, long tiles, StepsWorkspace w) {
@@ -168,7 +159,7 @@ __global__ __launch_bounds__(PLAN_NT) void perturb_plan_kernel(const int32_t* __
     if (tid < S1) s_counts[tid] = counts[tid];
     __syncthreads();
     tot = owner ? s_part[L] + s_part[256 + L] + s_part[512 + L] + s_part[768 + L] : 0u;
-    const uint32_t inc = wave_scan_incl_u32(tot);
+    const uint32_t inc = wave_scan_incl(tot);
     if (owner && lane == 63) s_wave[wave] = inc;
     __syncthreads();
     int lo = 0, hi = 0;
@@ -212,7 +203,7 @@ __global__ __launch_bounds__(PLAN_NT) void perturb_plan_kernel(const int32_t* __
         for (long t0 = 0; t0 < tiles; t0 += 64) {
             const long tt = t0 + lane;
             const uint32_t h = tt < tiles ? hist[tt * 256 + lv] : 0u;
-            const uint32_t in = wave_scan_incl_u32(h);
+            const uint32_t in = wave_scan_incl(h);
             if (tt < tiles) prefix[tt * PT_MAX_S1] = (before + in - h) | (h ? PT_PRESENT : 0u);
             before += __shfl(in, 63);
         }
@@ -341,8 +332,7 @@ __global__ __launch_bounds__(PT_NT) void perturb_apply_kernel(ApplyArgs a) {
         const U* xr = static_cast<const U*>(a.x) + (n * a.C + ch) * V;
         const U* br = a.baseline ? static_cast<const U*>(a.baseline) + (n * a.C + ch) * V : nullptr;
         U* orow = static_cast<U*>(a.out) + ((nj * a.Sc + sc) * a.C + ch) * V;
-        const long lead = (long)(((16 - ((uintptr_t)(orow + lo) & 15)) & 15) / sizeof(U));
-        const long va = min(lo + lead, t1), nvec = (t1 - va) / EPV, vt = va + nvec * EPV;
+        const long va = min(lo + lead_to_16(orow + lo), t1), nvec = (t1 - va) / EPV, vt = va + nvec * EPV;
         const long nhead = va - lo, ntail = t1 - vt;  // fewer than EPV elements each
         if (tid < nhead + ntail) {
             const long v = tid < nhead ? lo + tid : vt + (tid - nhead);
@@ -437,20 +427,12 @@ __global__ __launch_bounds__(PT_NT) void perturb_curves_kernel(CurveArgs a) {
     if (!a.acc) return;
     __threadfence_block();
     __syncthreads();
-    const int nc = k * S1, total = 2 * nc + 2 * k + 1;
-    for (int e = tid; e < total; e += PT_NT) {
-        double t = a.acc[e];
-        if (e == total - 1) {
-            t += (double)a.N;
-        } else {
-            for (long n = 0; n < a.N; ++n) {
-                if (e < nc) t += (double)a.curve_sim[n * nc + e];
-                else if (e < 2 * nc) t += (double)a.curve_prob[n * nc + (e - nc)];
-                else t += a.auc[n * 2 * k + (e - 2 * nc)];
-            }
-        }
-        a.acc[e] = t;
-    }
+    const int nc = k * S1;  // acc = [similarity curves (k, S1), probability curves (k, S1), areas (k, 2), N]
+    sweep_acc_add<PT_NT>(a.acc, 2 * nc + 2 * k + 1, a.N, [&](long n, int e) {
+        if (e < nc) return (double)a.curve_sim[n * nc + e];
+        if (e < 2 * nc) return (double)a.curve_prob[n * nc + (e - nc)];
+        return a.auc[n * 2 * k + (e - 2 * nc)];
+    });
 }
 
 static bool steps_sizes_ok(long M, long V, int S1) { return M >= 1 && M <= PT_MAX_MAPS && V >= 1 && V <= PT_MAX_V && S1 >= 1 && S1 <= PT_MAX_S1; }
@@ -460,7 +442,7 @@ static uint32_t bf16_bits_rne(float f) {
     uint32_t u;
     memcpy(&u, &f, 4);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    return bf16_round_bits(u);
 }
 
 }  // namespace pasn
@@ -501,17 +483,7 @@ extern "C" int pasn_perturb_apply(const void* x, const uint8_t* steps, const int
     PASN_REQUIRE(V >= 1 && V <= PT_MAX_V, "V must lie in [1, 2^31)");
     const uintptr_t esz = dtype == PASN_BF16 ? 2 : 4;
     PASN_REQUIRE((((uintptr_t)x | (uintptr_t)baseline | (uintptr_t)out) & (esz - 1)) == 0, "x, baseline and out must be aligned to their element");
-    ApplyArgs a;
-    a.x = x;
-    a.baseline = baseline;
-    a.steps = steps;
-    a.step_ids = step_ids;
-    a.out = out;
-    a.V = V;
-    a.C = C;
-    a.k = k;
-    a.Sc = Sc;
-    a.mode = mode;
+    ApplyArgs a{x, baseline, steps, step_ids, out, V, C, k, Sc, mode, 0u};
     if (dtype == PASN_BF16) a.fill = bf16_bits_rne(fill);
     else memcpy(&a.fill, &fill, 4);
     const dim3 grid((unsigned)((V + 15 + PT_TILE - 1) / PT_TILE), (unsigned)Sc, (unsigned)(N * k));
@@ -531,23 +503,7 @@ extern "C" int pasn_perturb_curves(const float* sim, const float* logits, const 
     PASN_REQUIRE(K >= K_real && K <= 17, "K must lie in [K_real, 17]");
     PASN_REQUIRE(P >= 1, "P must be positive");
     PASN_REQUIRE(V >= 1 && V <= PT_MAX_V, "V must lie in [1, 2^31)");
-    CurveArgs a;
-    a.sim = sim;
-    a.logits = logits;
-    a.sel = sel;
-    a.cls = cls;
-    a.counts = counts;
-    a.N = N;
-    a.k = k;
-    a.S1 = S1;
-    a.P = P;
-    a.K = K;
-    a.K_real = K_real;
-    a.V = V;
-    a.curve_sim = curve_sim;
-    a.curve_prob = curve_prob;
-    a.auc = auc;
-    a.acc = acc;
+    const CurveArgs a{sim, logits, sel, cls, counts, N, k, S1, P, K, K_real, V, curve_sim, curve_prob, auc, acc};
     hipLaunchKernelGGL(perturb_curves_kernel, dim3(1), dim3(PT_NT), 0, (hipStream_t)stream, a);
     return check_launch("perturb_curves");
 }

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void rc_curve_kernel(const int32_t* __restrict
             run += (unsigned long long)(L[q] == k && P[q] == k) | ((unsigned long long)(L[q] == k) << 20) | ((unsigned long long)(P[q] == k) << 40);
             loc[q] = run;
         }
-        const unsigned long long inc = wave_scan_incl_u64(run);
+        const unsigned long long inc = wave_scan_incl(run);
         __syncthreads();  // wsum of the class before has been read; base is visible (k = 0)
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();

@@ -55,6 +55,40 @@ def _is_xproto(model) -> bool:
     return isinstance(model, _XProtoHeadMixin)
 
 
+# entry point -> the words of its messages: what it covers, why PPNet is out
+_COVERS = {"explain": ("local explanations cover", "the reference has none for PPNet"),
+           "faithfulness": ("faithfulness curves cover", "PPNet has no occurrence maps"),
+           "robustness": ("robustness evaluation covers", "PPNet has no occurrence maps")}
+
+
+def _check_model(model, x: torch.Tensor, what: str, maps: Optional[str] = None) -> None:
+    """A head-B model, in eval mode, with its input on the GPU: the checks of ``explain_batch`` (``what`` = "explain", which also
+    passes its ``maps``), ``perturbation_curves`` ("faithfulness") and ``stability`` ("robustness"), in the order they fire."""
+    covers, why = _COVERS[what]
+    if not _is_xproto(model):
+        raise NotImplementedError(f"{covers} XProtoNet and Video_XProtoNet; {why}")
+    if maps not in MAPS:
+        raise ValueError(f"maps must be one of {MAPS}, got {maps!r}")
+    if model.training:
+        raise RuntimeError(f"{what} runs in eval mode (call model.eval())")
+    if not x.is_cuda:
+        raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
+
+
+def _int_select(select, per_clip: str) -> int:
+    if isinstance(select, bool) or not isinstance(select, (int, np.integer)):
+        raise TypeError(f"select must be an int ({per_clip}), got {type(select).__name__}")
+    return int(select)
+
+
+def _dimensions(model, abstain_class: bool):
+    """(P, K, G, K_real): prototypes, classes, prototypes per class block, classes without the abstain class."""
+    P, K = int(model.num_prototypes), int(model.num_classes)
+    if P % K:
+        raise ValueError(f"{P} prototypes do not split into {K} class blocks")
+    return P, K, P // K, K - 1 if abstain_class else K
+
+
 def _check_lut(lut, device) -> Optional[torch.Tensor]:
     if lut is None:
         return None
@@ -124,19 +158,8 @@ def explain_batch(model, x: torch.Tensor, select: Union[None, str, int] = None, 
     reference renders), "predicted" = the predicted class's prototypes by descending similarity, int k = the first k of those.
     ``maps``: "float" (normalised fp32), "uint8" (``np.uint8(255 * map)``) or None.  ``lut`` (256, 3): also the overlays
     ``(x * std + mean) + alpha * lut[uint8 map]``."""
-    if not _is_xproto(model):
-        raise NotImplementedError("local explanations cover XProtoNet and Video_XProtoNet; the reference has none for PPNet")
-    if maps not in MAPS:
-        raise ValueError(f"maps must be one of {MAPS}, got {maps!r}")
-    if model.training:
-        raise RuntimeError("explain runs in eval mode (call model.eval())")
-    if not x.is_cuda:
-        raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
-    P, K = model.num_prototypes, model.num_classes
-    if P % K:
-        raise ValueError(f"{P} prototypes do not split into {K} class blocks")
-    G = P // K
-    K_real = K - 1 if abstain_class else K
+    _check_model(model, x, "explain", maps)
+    P, K, G, K_real = _dimensions(model, abstain_class)
     if K_real < 1:
         raise ValueError("abstain_class needs at least two classes")
     k_sel = _select_count(select, G, P)

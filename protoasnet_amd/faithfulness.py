@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .explain import _clip_geometry, _is_xproto, explain_batch
+from .explain import _check_model, _clip_geometry, _dimensions, _int_select, explain_batch
 
 MAX_STEPS = 64                      # S1 = steps + 1 entries of counts at most
 MODES = ("deletion", "insertion")   # mode 0, mode 1 of pasn_perturb_apply
@@ -160,17 +160,6 @@ def accumulator_size(k: int, S1: int) -> int:
     return 2 * k * S1 + 2 * k + 1
 
 
-def _check_model(model, x: torch.Tensor) -> None:
-    if not _is_xproto(model):
-        raise NotImplementedError("faithfulness curves cover XProtoNet and Video_XProtoNet; PPNet has no occurrence maps")
-    if model.training:
-        raise RuntimeError("faithfulness runs in eval mode (call model.eval())")
-    if not x.is_cuda:
-        raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"the clip must be fp32 or bf16, got {x.dtype}")
-
-
 def random_saliency(x: torch.Tensor, k: int, seed: int = 0) -> torch.Tensor:
     """The control: a uniform uint8 map (N, k, [T,] H, W) from a device generator seeded with ``seed``."""
     g = torch.Generator(device=x.device)
@@ -219,18 +208,18 @@ def perturbation_curves(model, x: torch.Tensor, select: int = 1, steps: Union[in
     ``model.forward`` at most ``max_batch`` at a time, every chunk of steps with the same batch size, so that one plan is compiled (a last,
     smaller group of clips compiles a second one).  Step 0 of the default counts is the untouched clip under deletion and the baseline
     under insertion; the last step the reverse."""
-    _check_model(model, x)
+    _check_model(model, x, "faithfulness")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"the clip must be fp32 or bf16, got {x.dtype}")
     if mode not in MODES + ("both",):
         raise ValueError(f"mode must be 'deletion', 'insertion' or 'both', got {mode!r}")
-    if isinstance(select, bool) or not isinstance(select, (int, np.integer)):
-        raise TypeError(f"select must be an int (maps per clip), got {type(select).__name__}")
+    k = _int_select(select, "maps per clip")
     if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)) or max_batch < 1:
         raise ValueError(f"max_batch must be a positive integer, got {max_batch!r}")
     _, grid = _clip_geometry(x)
     V = grid[0] * grid[1] * grid[2]
     counts = step_counts(V, steps) if isinstance(steps, (int, np.integer)) else step_counts(V, fractions=steps)
-    K_real = model.num_classes - 1 if abstain_class else model.num_classes
-    k = int(select)
+    K_real = _dimensions(model, abstain_class)[3]
     x = x.contiguous()
     with torch.no_grad():
         own = saliency is None

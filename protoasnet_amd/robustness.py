@@ -27,7 +27,7 @@ import torch
 
 from . import _lib
 from .data import ECHO_MEAN, ECHO_STD
-from .explain import _is_xproto
+from .explain import _check_model, _dimensions, _int_select, _select_count
 
 MAX_RADIUS = 8   # taps: 2 R + 1 <= 17
 MAX_MAP = 4096   # voxels of an occurrence map pasn_stability_stats ranks in LDS
@@ -173,15 +173,6 @@ def accumulator_size(k: int) -> int:
     return 6 + 4 * k + 1
 
 
-def _check_model(model, x: torch.Tensor) -> None:
-    if not _is_xproto(model):
-        raise NotImplementedError("robustness evaluation covers XProtoNet and Video_XProtoNet; PPNet has no occurrence maps")
-    if model.training:
-        raise RuntimeError("robustness runs in eval mode (call model.eval())")
-    if not x.is_cuda:
-        raise RuntimeError("protoasnet_amd models run on the GPU only; there is no CPU fallback")
-
-
 def _forward(model, x: torch.Tensor):
     """(logits (N, K), sim (N, P), occ (N, P, S), (Ti, Hi, Wi)) of ``push_forward``, fp32 and contiguous."""
     with torch.no_grad():
@@ -204,17 +195,12 @@ def stability(model, x: torch.Tensor, x_corrupted: torch.Tensor, select: int = 1
     """Compare the model on the clips ``x`` and on ``x_corrupted`` (the same clips, corrupted): two ``push_forward``s and one
     ``pasn_stability_stats``.  ``select``: the k best prototypes of the clean prediction's class; ``top_fraction``: the share of an
     occurrence map's voxels in its top set; ``labels`` (N,) for the two correctness columns."""
-    _check_model(model, x)
+    _check_model(model, x, "robustness")
     if x_corrupted.shape != x.shape or x_corrupted.device != x.device:
         raise ValueError(f"the corrupted clips {tuple(x_corrupted.shape)} do not belong to the clips {tuple(x.shape)}")
-    if isinstance(select, bool) or not isinstance(select, (int, np.integer)):
-        raise TypeError(f"select must be an int (prototypes per clip), got {type(select).__name__}")
-    P, K = int(model.num_prototypes), int(model.num_classes)
-    if P % K:
-        raise ValueError(f"{P} prototypes do not split into {K} class blocks")
-    k, K_real = int(select), K - 1 if abstain_class else K
-    if not 1 <= k <= P // K:
-        raise ValueError(f"select={select} must lie in [1, {P // K}] (prototypes per class)")
+    k = _int_select(select, "prototypes per clip")
+    P, K, G, K_real = _dimensions(model, abstain_class)
+    _select_count(select, G, P)  # k lies in [1, G]
     la, sa, oa, grid = _clean if _clean is not None else _forward(model, x)
     lb, sb, ob, grid_b = _forward(model, x_corrupted)
     S = grid[0] * grid[1] * grid[2]
@@ -238,7 +224,7 @@ def robustness(model, x: torch.Tensor, corruption: Union[str, Corruption], sever
                top_fraction: float = 0.1, labels=None, abstain_class: bool = True, mean: float = ECHO_MEAN,
                std: float = ECHO_STD) -> Stability:
     """``stability`` of the clips ``x`` against ``corrupt(x, corruption, severity, seed)`` (also ``model.robustness(x, ...)``)."""
-    _check_model(model, x)
+    _check_model(model, x, "robustness")
     return stability(model, x, corrupt(x, corruption, severity, seed, mean, std), select=select, top_fraction=top_fraction, labels=labels,
                      abstain_class=abstain_class)
 
@@ -264,7 +250,7 @@ class RobustnessAccumulator:
         self.acc = None       # (corruptions, severities, accumulator_size) fp64, on the first batch's device
 
     def update(self, x: torch.Tensor, labels=None) -> None:
-        _check_model(self.model, x)
+        _check_model(self.model, x, "robustness")
         if self.acc is None:
             self.acc = torch.zeros((len(self.corruptions), len(self.severities), accumulator_size(self.select)), dtype=torch.float64,
                                    device=x.device)

@@ -115,6 +115,31 @@ def select_ref(sim, base, G, k):
     return sorted(range(base, base + G), key=lambda p: (-float(sim[p]), -p))[:k]
 
 
+AGREE_K, AGREE_K_REAL, AGREE_G, AGREE_SELECT, AGREE_GRID = 4, 3, 5, 3, (1, 2, 2)
+
+
+def agreement_case():
+    """Six hand-made clips on which pasn_stability_stats and pasn_explain_rank must report the same class and the same k = 3 prototypes
+    (K = 4, K_real = 3, G = 5, P = 20; no NaN similarities).  Returns (logits (6, 4), sim (6, 20), occ (6, 20, 4), fc_w (4, 20),
+    pred by hand (6,), sel by hand for the first three clips (3, 3))."""
+    nan = np.nan
+    logits = np.array([[0.5, 2.0, 1.0, 9.0],   # distinct; the abstain logit is the largest and is not looked at: class 1
+                       [0.0, 1.0, 3.0, 0.0],   # class 2
+                       [4.0, 1.0, 0.0, 0.0],   # class 0
+                       [2.0, nan, 3.0, 0.0],   # NaN at class 1 counts as the largest: class 1
+                       [nan, 5.0, 1.0, 0.0],   # NaN at class 0, a larger finite logit after it: class 0
+                       [1.0, 1.0, 1.0, 1.0]],  # all equal: class 0
+                      np.float32)
+    rng = np.random.default_rng(5)
+    sim = (np.stack([rng.permutation(20) for _ in range(6)]) / 8.0).astype(np.float32)  # distinct within every clip
+    sim[0, 5:10] = [.125, .875, .5, 1.0, .25]  # clip 0, block 1, distinct: 8, 6, 7
+    sim[1, 10:15] = [.5, .25, .75, .5, 1.0]    # clip 1, block 2: 14, 12, then 13 and 10 tie across rank k - 1 / k: the HIGHER index is in
+    sim[2, 0:5] = .375                         # clip 2, block 0: all equal: 4, 3, 2
+    occ = (rng.integers(0, 17, (6, 20, 4)) / 16.0).astype(np.float32)
+    fc_w = (rng.integers(-8, 9, (4, 20)) / 8.0).astype(np.float32)
+    return logits, sim, occ, fc_w, np.array([1, 2, 0, 1, 0, 0]), np.array([[8, 6, 7], [14, 12, 13], [4, 3, 2]])
+
+
 def softmax64(l):
     z = np.asarray(l, np.float64)
     e = np.exp(z - z.max())

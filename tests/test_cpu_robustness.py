@@ -250,6 +250,22 @@ def test_clip_statistics_and_selection_rules():
     assert res["pair"][3, :, 1:].tolist() == [[1.0, 1.0, 0.0]] * 3 and 0 < res["clip"][:, 0].sum() < 5  # identical maps; some flips
 
 
+def test_the_two_restatements_select_the_same_prototypes():
+    """The CPU half of test_gpu_robustness.py::test_stability_and_explain_rank_select_the_same_prototypes: on its six clips the expected
+    class and prototypes do not depend on which restatement is asked (robustness_cases against explain_cases), and match the hand values."""
+    from explain_cases import rank_ref
+
+    logits, sim, _, fc_w, pred_hand, sel_hand = rc.agreement_case()
+    K_real, G, k = rc.AGREE_K_REAL, rc.AGREE_G, rc.AGREE_SELECT
+    assert logits.shape == (6, rc.AGREE_K) and sim.shape == (6, rc.AGREE_K * G) and not np.isnan(sim).any()
+    pred = [rc.pred_ref(logits[n], K_real) for n in range(6)]
+    sel = [rc.select_ref(sim[n], pred[n] * G, G, k) for n in range(6)]
+    _, _, _, _, pred_e, sel_e = rank_ref(sim, fc_w, logits, K_real, k)
+    assert pred == pred_e.tolist() == pred_hand.tolist()
+    assert sel == sel_e.tolist() and sel[:3] == sel_hand.tolist()
+    assert all(s[0] // G == p for s, p in zip(sel, pred))
+
+
 def test_trainer_refuses_ppnet_and_the_cpu():
     from protoasnet_amd.trainer import DPTrainer
     from test_cpu_trainer import TRAIN_CFG

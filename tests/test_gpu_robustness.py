@@ -199,6 +199,24 @@ def test_stability_refuses_a_map_too_large_for_lds():
         _stats_call(case, 3, 1, 1, (1, 64, 65), True)
 
 
+def test_stability_and_explain_rank_select_the_same_prototypes():
+    """pasn_stability_stats (robustness) and pasn_explain_rank (explanations, faithfulness) report the same predicted class and the same
+    k best prototypes: distinct values, a tie across rank k - 1 / k, an all-equal block, NaN logits, all-equal logits."""
+    from explain_cases import rank_ref
+    from test_gpu_explain import _rank
+
+    logits, sim, occ, fc_w, pred_hand, sel_hand = rc.agreement_case()
+    K_real, G, k = rc.AGREE_K_REAL, rc.AGREE_G, rc.AGREE_SELECT
+    _, _, sel_s, _ = _stats_call((logits, logits, sim, sim, occ, occ, None), K_real, k, 1, rc.AGREE_GRID, False)
+    _, _, _, _, pred_e, sel_e = _rank(*(torch.from_numpy(a) for a in (sim, fc_w, logits)), K_real, k)
+    pred_e, sel_e = pred_e.cpu().numpy(), sel_e.cpu().numpy()
+    _, _, _, _, pred_r, sel_r = rank_ref(sim, fc_w, logits, K_real, k)
+    assert np.array_equal(sel_s, sel_e), (sel_s, sel_e)
+    assert np.array_equal(sel_s[:, 0] // G, pred_e)
+    assert np.array_equal(sel_s, sel_r.numpy()) and np.array_equal(pred_e, pred_r.numpy())
+    assert np.array_equal(pred_e, pred_hand) and np.array_equal(sel_s[:3], sel_hand)
+
+
 # ---- 3. the whole path ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cfg,shape", [(CFG_VIDEO_X3D, (2, 3, 4, 64, 64)), (CFG_XPROTO, (2, 3, 224, 224))], ids=["x3d_s", "xprotonet_image"])
 def test_model_robustness_end_to_end(cfg, shape):
