@@ -197,6 +197,24 @@ int pasn_conv3d_short_fwd(const void* x, const void* w, const float* scale, cons
                           const void* w2, const float* scale2, void* y, const pasn_conv_desc* d, const pasn_conv_desc* d2, int dtype,
                           void* stream);
 
+/*
+ * Which kernel instance a fused launch runs, read from the geometry its launch reads (host only, nothing is launched; the arguments are
+ * those of the matching _supported() probe).  0 = not covered.
+ *   pasn_conv3d_se_variant       7000 + KS*10 + MT            pwconv_ws_kernel<KS, MT, true, residual>[se]     (pasn_conv3d_se_fwd)
+ *   pasn_conv3d_short_variant    KS*100 + NT*10 + KS2         pwconv_persist_kernel<bf16, KS, NT, false, KS2>  (pasn_conv3d_short_fwd)
+ *   pasn_conv3d_pair_instance    arm*10000 + KS1*100 + KS2    arm = pasn_conv3d_pair_variant's answer: 1 pwconv_xpair_kernel<KS1, KS2, transform>,
+ *                                                             2 pwconv_ws_kernel<KS1, 1, transform, true, KS2>  (pasn_conv3d_pair_fwd; flags as there)
+ *   pasn_conv3d_pair_se_variant  20000 + KS1*100 + KS2        pwconv_ws_kernel<KS1, 1, true, true, KS2>[se]     (pasn_conv3d_pair_se_fwd)
+ *   pasn_x3d_pe_variant          KSC*1000 + KSA*10 + MT       x3d_pe_kernel<KSC, KSA, gate, MT>                 (pasn_x3d_pe_fwd; MT: PASN_PE_MT)
+ *   pasn_x3d_edp_variant         KSA*100 + KSC                x3d_edp_kernel<KSA, KSC, next expand>             (pasn_x3d_edp_fwd)
+ */
+int pasn_conv3d_se_variant(const pasn_conv_desc* d, int dtype, int Cse, int has_residual);
+int pasn_conv3d_short_variant(const pasn_conv_desc* d, const pasn_conv_desc* d2, int dtype);
+int pasn_conv3d_pair_instance(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int flags);
+int pasn_conv3d_pair_se_variant(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int Cse);
+int pasn_x3d_pe_variant(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int Cse);
+int pasn_x3d_edp_variant(const pasn_conv_desc* d_a, const pasn_conv_desc* d_dw, const pasn_conv_desc* d_c, const pasn_conv_desc* d_n, int dtype);
+
 /* Which kernel instance pasn_conv3d_fwd picks for this geometry: 1000 + KS*10 + NT = pwconv_persist_kernel<dtype, KS, NT>
  * (1x1x1 stride-1 convs whose weights fit 64 VGPRs per lane); 2500 + 2*KS (+1 with in_swish) = pwconv_xtile_kernel<dtype, KS, ..>
  * (1x1x1 stride-1 convs with Cin_p >= 64: whole-K position tiles in LDS); 2000 / 2001 = gemm_conv_kernel<dtype, pointwise /

@@ -962,6 +962,35 @@ extern "C" int pasn_conv3d_short_fwd(const void* x, const void* w, const float* 
     return launch_pwconv<__bf16>(x, w, scale, bias, nullptr, gate, y, *d, pw_geom(*d, dtype), (hipStream_t)stream, &sc);
 }
 
+// ---- the instance a fused launch runs (encodings: include/protoasnet_amd.h): each reads the route its launch reads, nothing else -----------
+extern "C" int pasn_conv3d_se_variant(const pasn_conv_desc* d, int dtype, int Cse, int has_residual) {
+    const WsGeom g = ws_se_route(d, nullptr, dtype, Cse, has_residual != 0);
+    return g.ok ? 7000 + g.KS * 10 + g.MT : 0;
+}
+
+extern "C" int pasn_conv3d_short_variant(const pasn_conv_desc* d, const pasn_conv_desc* d2, int dtype) {
+    if (!conv_desc_ok(d) || !conv_desc_ok(d2)) return 0;
+    const int ks2 = pw_short_ks2(*d, *d2, dtype);
+    const PwGeom g = pw_geom(*d, dtype);
+    return ks2 ? g.TM * 100 + g.xrow * 10 + ks2 : 0;
+}
+
+extern "C" int pasn_conv3d_pair_instance(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int flags) {
+    if (!conv_desc_ok(d1) || !conv_desc_ok(d2)) return 0;
+    const PairRoute r = pair_route(*d1, *d2, dtype, (flags & 1) != 0);
+    if (r.arm == PairRoute::WS) return 20000 + r.ws.KS * 100 + r.ws.KS2;
+    if (r.arm != PairRoute::XPAIR) return 0;
+    int ks2 = 0;
+    const int ks1 = pw_xpair_ks(*d1, *d2, dtype, &ks2);
+    return 10000 + ks1 * 100 + ks2;
+}
+
+extern "C" int pasn_conv3d_pair_se_variant(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int Cse) {
+    if (!d2) return 0;
+    const WsGeom g = ws_se_route(d1, d2, dtype, Cse, true);
+    return g.ok ? 20000 + g.KS * 100 + g.KS2 : 0;
+}
+
 static int dw_variant_code(const pasn_conv_desc* d, int dtype, bool wants_pool) {
     if (!dw_desc_ok(d)) return 0;
     const DwRoute r = dw_route(*d, dtype, wants_pool);

@@ -431,6 +431,12 @@ extern "C" int pasn_x3d_edp_supported(const pasn_conv_desc* d_a, const pasn_conv
     return edp_geom(*d_a, *d_dw, *d_c, d_n, dtype).ok;
 }
 
+extern "C" int pasn_x3d_edp_variant(const pasn_conv_desc* d_a, const pasn_conv_desc* d_dw, const pasn_conv_desc* d_c, const pasn_conv_desc* d_n, int dtype) {
+    if (!edp_desc_ok(d_a) || !edp_desc_ok(d_dw) || !edp_desc_ok(d_c) || (d_n && !edp_desc_ok(d_n))) return 0;
+    const EdpGeom g = edp_geom(*d_a, *d_dw, *d_c, d_n, dtype);
+    return g.ok ? g.KSA * 100 + g.KSC : 0;
+}
+
 extern "C" int pasn_x3d_edp_fwd(const void* x, const void* w_a, const float* scale_a, const float* bias_a, const void* w_dw, const float* scale_dw,
                                 const float* bias_dw, const void* w_c, const float* scale_c, const float* bias_c, void* y, const void* w_n,
                                 const float* scale_n, const float* bias_n, void* e_next, const pasn_conv_desc* d_a, const pasn_conv_desc* d_dw,

@@ -278,6 +278,9 @@ PeGeom pe_geom(const pasn_conv_desc& d1, const pasn_conv_desc& d2, int dtype, bo
     return g;
 }
 
+// rows per wave group of the instance, <.., MT>: 4, or 2 under PASN_PE_MT=2 (read by the launch and by pasn_x3d_pe_variant)
+static int pe_mt() { return (tune("PASN_PE_MT") && tune("PASN_PE_MT")[0] == '2') ? 2 : 4; }
+
 int launch_x3d_pe(const void* x, const void* w1, const float* s1, const float* b1, const void* res, const float* pool, int pool_blocks,
                   int positions, const float* fc1_w, const float* fc1_b, const float* fc2_w, const float* fc2_b, int cse, void* y1,
                   const pasn_conv_desc& d1, const void* w2, const float* s2, const float* b2, void* y2, const pasn_conv_desc& d2, const PeGeom& g,
@@ -287,7 +290,7 @@ int launch_x3d_pe(const void* x, const void* w1, const float* s1, const float* b
              positions > 0 ? 1.0f / (float)positions : 0.0f, fc1_w, fc1_b, fc2_w, fc2_b, d1.Cin, cse, (int)M, d1.To * d1.Ho * d1.Wo, d1.Cin_p,
              d1.Cout_p, d2.Cout_p};
     const dim3 grid(g.grid), block(512);
-    const bool mt4 = !(tune("PASN_PE_MT") && tune("PASN_PE_MT")[0] == '2');
+    const bool mt4 = pe_mt() == 4;
 #define PASN_PE(SE_, MT_)                                                                                           \
     do {                                                                                                            \
         PASN_MAX_LDS(160 * 1024, x3d_pe_kernel<28, 12, SE_, MT_>);                                                  \
@@ -317,6 +320,12 @@ static bool pe_desc_ok(const pasn_conv_desc* d) { return d && d->N > 0 && d->To 
 extern "C" int pasn_x3d_pe_supported(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int Cse) {
     if (!pe_desc_ok(d1) || !pe_desc_ok(d2)) return 0;
     return pe_geom(*d1, *d2, dtype, Cse > 0, Cse).ok;
+}
+
+extern "C" int pasn_x3d_pe_variant(const pasn_conv_desc* d1, const pasn_conv_desc* d2, int dtype, int Cse) {
+    if (!pe_desc_ok(d1) || !pe_desc_ok(d2)) return 0;
+    const PeGeom g = pe_geom(*d1, *d2, dtype, Cse > 0, Cse);
+    return g.ok ? g.KSC * 1000 + g.KSA * 10 + pe_mt() : 0;
 }
 
 extern "C" int pasn_x3d_pe_fwd(const void* x, const void* w1, const float* scale1, const float* bias1, const void* residual,

@@ -17,7 +17,8 @@ view), ``se_operands`` (squeeze-excite fc pair), ``pack_dw_taps`` (depthwise [ta
 A ``PlanBuilder`` method that may answer "not covered" probes first and allocates after: it asks the library with ``_geom`` (output
 extents, no buffer) and ``_probe_desc`` (a descriptor nobody keeps), and only a launch that will be recorded reserves buffers
 (``_alloc``) and appends to ``keep`` -- a declined launch leaves no trace in the arena plan.  ``conv_kernel_name`` /
-``dwconv_kernel_name`` decode the library's variant codes into the instance names of ``meta``.
+``dwconv_kernel_name`` / ``fused_kernel_name`` / ``x3d_pe_kernel_name`` / ``x3d_edp_kernel_name`` decode the library's variant codes into the
+instance names of ``meta``: no name is a formula of the shapes here.
 
 Replaying is then a tight loop of ctypes calls on torch's current stream -- no allocation (bar the
 output tensor), no host sync, capturable into a hipGraph.  Packed weights are refreshed automatically
@@ -236,6 +237,33 @@ def dwconv_kernel_name(dv: int, tname: str, act: str, pool: bool, wo: int) -> st
     if dv:
         return f"dwconv3d_strip_kernel<{tname},{dv // 100},{dv // 10 % 10},{dv % 10}>"
     return f"dwconv3d_kernel<{tname}>"
+
+
+def fused_kernel_name(v: int, tname: str, transform: bool = False, res: bool = False, se: bool = False) -> str:
+    """Instance names of the fused multi-stage launches, decoded from the library's codes (include/protoasnet_amd.h): ``pasn_conv3d_se_variant``
+    (>= 7000, with ``se``), ``pasn_conv3d_pair_instance`` / ``pasn_conv3d_pair_se_variant`` (>= 10000), ``pasn_conv3d_short_variant`` (< 1000)."""
+    tf = lambda b: "true" if b else "false"
+    assert v > 0, "the launch is covered (its _supported probe said so) but its variant probe names no instance"
+    if v >= 10000:
+        ks1, ks2 = v // 100 % 100, v % 100
+        if v // 10000 == 1:
+            return f"pwconv_xpair_kernel<{ks1},{ks2},{tf(transform)}>"
+        return f"pwconv_ws_kernel<{ks1},1,{tf(transform or se)},true,{ks2}>" + ("[se]" if se else "")
+    if v >= CONV_PW_WS:
+        return conv_kernel_name(v, tname, True, True, res) + "[se]"
+    return f"pwconv_persist_kernel<{tname},{v // 100},{v // 10 % 10},false,{v % 10}>"
+
+
+def x3d_pe_kernel_name(v: int, se: bool) -> str:
+    """``pasn_x3d_pe_variant``'s code KSC * 1000 + KSA * 10 + MT."""
+    assert v > 0
+    return f"x3d_pe_kernel<{v // 1000},{v // 10 % 100},{'true' if se else 'false'},{v % 10}>"
+
+
+def x3d_edp_kernel_name(v: int, nxt: bool) -> str:
+    """``pasn_x3d_edp_variant``'s code KSA * 100 + KSC."""
+    assert v > 0
+    return f"x3d_edp_kernel<{v // 100},{v % 100},{'true' if nxt else 'false'}>"
 
 
 class PlanBuilder:
@@ -487,7 +515,8 @@ class PlanBuilder:
         xb, yb, rb, pbuf, dref, pos = x.buf, y.buf, (residual.buf if residual is not None else None), pool_buf, ctypes.byref(d), x.positions
         self._use(xb, yb, rb, pbuf)
         out_pos = y.N * y.positions
-        self._note("conv+se", f"pwconv_ws_kernel<{max(4, kc // 16 + kc // 16 % 2) if kc // 16 <= 16 else 28},1,true,{'true' if residual is not None else 'false'}>[se]",
+        self._note("conv+se", fused_kernel_name(int(self.lib.pasn_conv3d_se_variant(dref, self.code, cse, int(residual is not None))), self.tname,
+                                                res=residual is not None, se=True),
                    (out_pos * (x.C + y.C * (2 if residual is not None else 1)) + y.C * x.C) * self.es + (x.N * pool_blocks * c + 2 * c * cse) * 4,
                    2 * out_pos * y.C * x.C + 4 * x.N * c * cse, None)
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[rb] if rb is not None else 0, ptrs[pbuf], pool_blocks, pos,
@@ -542,8 +571,7 @@ class PlanBuilder:
         xb, x2b, gb, yb, r1, r2 = x.buf, x2.buf, in_gate, y.buf, ctypes.byref(d), ctypes.byref(d2)
         self._use(xb, x2b, gb, yb)
         pos = y.N * y.positions
-        self._note("conv+shortcut", f"pwconv_persist_kernel<{self.tname},{max(2, 1 << (kc // 16 - 1).bit_length()) if kc // 16 > 2 else 2},{(y.Cp + 31) // 32},false,"
-                                    f"{2 if kc2 // 16 <= 2 else 4}>",
+        self._note("conv+shortcut", fused_kernel_name(int(self.lib.pasn_conv3d_short_variant(r1, r2, self.code)), self.tname),
                    (pos * (x.C + x2.C + y.C) + y.C * (x.C + x2.C)) * self.es + (x.N * x.C * 4 if in_gate is not None else 0),
                    2 * pos * y.C * (x.C + x2.C), d2)  # (the row shows the shortcut conv's shape: it carries the block's stride)
         self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[gb] if gb is not None else 0, ptrs[x2b], a[3], a[4],
@@ -609,19 +637,17 @@ class PlanBuilder:
             if pe:
                 fn = self.lib.pasn_x3d_pe_fwd
                 self._note("conv_pair+se" if se is not None else "conv_pair",
-                           f"x3d_pe_kernel<{kc1 // 16},{kc2 // 16},{'true' if se is not None else 'false'}>", nbytes, flops, None)
+                           x3d_pe_kernel_name(int(self.lib.pasn_x3d_pe_variant(r1, r2, self.code, cse)), se is not None), nbytes, flops, None)
             else:
                 fn = self.lib.pasn_conv3d_pair_se_fwd
-                self._note("conv_pair+se", f"pwconv_ws_kernel<{max(8, kc1 // 16 + kc1 // 16 % 2)},1,true,true,{4 if kc2 // 16 <= 4 else 6}>[se]",
+                self._note("conv_pair+se", fused_kernel_name(int(self.lib.pasn_conv3d_pair_se_variant(r1, r2, self.code, cse)), self.tname, se=True),
                            nbytes, flops + 4 * x.N * x.C * cse, None)
             self.ops.append(lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[rb], ptrs[pool_buf] if pool_buf is not None else 0, pool_blocks, npos,
                                                            sa[0], sa[1], sa[2], sa[3], cse, ptrs[y1b], r1, a[3], a[4], a[5], ptrs[y2b], r2, code, st)))
             return y1, y2
         fn = self.lib.pasn_conv3d_pair_fwd
-        pv = int(self.lib.pasn_conv3d_pair_variant(r1, r2, self.code, int(in_gate is not None)))
-        xf_name = 'true' if (in_gate is not None or in_swish) else 'false'
-        self._note("conv_pair", f"pwconv_ws_kernel<{max(8, kc1 // 16 + kc1 // 16 % 2)},1,{xf_name},true,{4 if kc2 // 16 <= 4 else 6}>" if pv == 2 else
-                                f"pwconv_xpair_kernel<{max(8, kc1 // 16 + kc1 // 16 % 2)},{kc2 // 16 + kc2 // 16 % 2},{xf_name}>",
+        pv = int(self.lib.pasn_conv3d_pair_instance(r1, r2, self.code, int(in_gate is not None)))
+        self._note("conv_pair", fused_kernel_name(pv, self.tname, transform=in_gate is not None or in_swish),
                    nbytes + (x.N * x.C * 4 if in_gate is not None else 0), flops, None)
         self.ops.append(
             lambda ptrs, st: _lib.check(fn(ptrs[xb], a[0], a[1], a[2], ptrs[rb], ptrs[gb] if gb is not None else 0, ptrs[y1b], r1,
@@ -704,7 +730,7 @@ class PlanBuilder:
         r = (ctypes.byref(da), ctypes.byref(dd), ctypes.byref(dc), ctypes.byref(dn) if dn is not None else None)
         self._use(xb, yb, nb)
         pos, cn = y.N * y.positions, (en.C if en is not None else 0)
-        self._note("block" if en is None else "block+expand", f"x3d_edp_kernel<{kca // 16},{kcc // 16},{'true' if en is not None else 'false'}>",
+        self._note("block" if en is None else "block+expand", x3d_edp_kernel_name(int(self.lib.pasn_x3d_edp_variant(r[0], r[1], r[2], r[3], self.code)), en is not None),
                    (pos * (2 * x.C + y.C + cn) + cm * x.C + 27 * cm + y.C * cm + cn * y.C) * self.es, 2 * pos * (cm * x.C + 27 * cm + y.C * cm + cn * y.C), None)
         self.meta[-1]["shape"] = f"{x.C}->{cm} k111 -> dw k333 -> {cm}->{y.C}" + (f" -> {y.C}->{cn}" if cn else "") + f" k111 in{x.T}x{x.H}x{x.W}"
         fn, code = self.lib.pasn_x3d_edp_fwd, self.code

@@ -751,8 +751,9 @@ def test_x3d_whole_block_one_launch_7x7(n, t, chain, monkeypatch):
 def test_streamed_project_expand_pair_432(n, thw, se, monkeypatch):
     """pasn_x3d_pe_fwd (x3d_pe.hip): the 432 -> 192 -> 432 project + expand pair of X3D's last stage in ONE launch, weights streamed per row tile,
     with the block's squeeze-excite gate computed in the launch's prologue (se) -- against torch, and BIT-IDENTICAL to the launches it replaces
-    (gate prologue + project conv on the weight-stationary kernel, expand conv on its own).  Shapes: tiles of 98 rows that never straddle a clip
-    (the benchmark's layout, 32 clips), tiles that straddle clips (two gate rows per tile), a ragged last tile."""
+    (gate prologue + project conv on the weight-stationary kernel, expand conv on its own).  Shapes: 32 clips of 196 positions, three clips
+    and a ragged last tile; pe_geom gives every one of them tiles of R = 32 rows (one 32-row sub-tile), which straddle clips in all three.
+    (R > 32 and the bound against fp64: tests/fused_kernel_cases.py.)"""
     dtype = torch.bfloat16
     c, c1, c2, cse = 432, 192, 432, 32
     torch.manual_seed(n + thw[0] + se)
