@@ -840,6 +840,62 @@ size_t pasn_temperature_workspace_bytes(long M, int K_real);
 int pasn_temperature_fit(const float* logits, const int32_t* labels, long M, int K, int K_real, double* fit, void* workspace, void* stream);
 int pasn_temperature_probs(const float* logits, long M, int K, int K_real, const double* beta, float* probs, float* u, void* stream);
 
+/* Conformal prediction (conformal.py): which classes can NOT be ruled out for a row, at a stated error rate?  Split conformal prediction:
+ * thresholds calibrated on one split, and on another a set of classes per row that holds the true one with probability >= 1 - alpha (for
+ * exchangeable rows).  The reference has no code for it; these definitions are the specification.  Every call is stream-ordered: no host
+ * synchronisation, no block waiting on another.
+ *
+ * Rows.  probs [M][K_real] fp32, labels [M] int32.  A row is valid when 0 <= label < K_real and none of its K_real probabilities is NaN.
+ * Padding rows (any other label) enter nothing; NaN rows enter nothing and are counted in nan_rows.
+ * Scores.  s(i, k) for every class k of row i, in fp64 from the fp32 probabilities, every operation rounded on its own (no FMA), then
+ * rounded once to fp32:
+ *   PASN_CONFORMAL_LAC   1.0 - p[k]
+ *   PASN_CONFORMAL_APS   rank the row's classes by descending probability, the lower class first on ties; s = acc + U p[k], acc the
+ *                        running fp64 sum, in rank order from 0.0, of the probabilities ranked strictly before k.  U = 1.0 unless
+ *                        `randomized`; then one uniform per row: word 0 of philox4x32_10 with the counter (i & 0xFFFFFFFF, i >> 32, salt,
+ *                        0) and the key (seed & 0xFFFFFFFF, seed >> 32), U = word * 2^-32
+ *   PASN_CONFORMAL_RAPS  the APS value, then + lam * max(0, rank - k_reg), rank the 1-based rank of k
+ *   Every score of a NaN row is NaN.  probabilities outside [0, 1] are ranked and added as they are.
+ * pasn_conformal_scores: scores [M][K_real] fp32; with labels also own [M] fp32 = s(i, label_i) (NaN for a row that is not valid) and
+ * stratum [M] int32 = the label of a valid row, -1 for a padding row, -2 for a NaN row.  labels, own and stratum are given together or
+ * not at all.  One launch, one thread per row.
+ *
+ * Thresholds.  Stratum 0 is all valid rows, stratum 1 + c the valid rows of label c; each holds n own-label scores.  For every alpha
+ * (host array of A doubles, each in (0, 1)): r = ceil((double)(n + 1) * (1.0 - alpha)) in fp64 on the device, and qhat is the r-th
+ * smallest of the stratum's scores -- a value, so the order among ties cannot matter --, +inf when r > n (n = 0 included).  The selection
+ * is exact: an element of the input (a score is never -0.0).
+ * pasn_conformal_quantiles: qhat [1 + K_real][A] fp32, n [1 + K_real] int64, r [1 + K_real][A] int64 from own and stratum as
+ * pasn_conformal_scores wrote them.  A byte-wise radix select on an order-preserving 32-bit key: one memset, four counting launches (a
+ * block counts the rows of its own stratum into 256 LDS bins per alpha, then integer atomics) and a finish, whatever M is; work linear
+ * in M.  `workspace`: pasn_conformal_workspace_bytes(M, K_real, A) bytes, 16-byte aligned, no initialisation.
+ *
+ * Sets.  Class k is in row i's set at level a iff s(i, k) <= qhat[0][a] (marginal) or s(i, k) <= qhat[1 + k][a] (`mondrian`), compared in
+ * fp32; +inf admits every class; a row whose scores hold a NaN gets the empty set.
+ * pasn_conformal_sets: masks [A][M] uint16 (bit k: class k) for every row, and tallies [A][T] int64, T = pasn_conformal_tally_words(K_real)
+ * = 3 + 4 (K_real + 1) + 2 K_real, per level in this order:
+ *   rows, covered, nan_rows                      rows that enter; of them, the label is in the set; rows with a NaN score
+ *   size_hist, covered_by_size [K_real + 1]      by set size
+ *   u_by_size (uint64), u_rows_by_size [K_real + 1]  with u [M] fp32 (or NULL): the sum of q = (uint64)((double)u * 4294967296.0) and the
+ *                                                number of rows, over the rows that enter with u in [0, 1]
+ *   class_n, class_covered [K_real]              by label
+ * With labels the rows that enter are the valid ones; with labels == NULL every row without a NaN score enters and covered,
+ * covered_by_size, class_n and class_covered stay 0.  All integer sums: exact and independent of order.  One memset and one launch;
+ * LDS counters per block, then integer atomics.
+ * 2 <= K_real <= 16, 1 <= M <= 2^20, 1 <= A <= PASN_CONFORMAL_MAX_ALPHAS, lam >= 0, k_reg >= 0; anything else, or a NULL required
+ * pointer, returns PASN_ERR_ARG before any launch (the size queries return 0). */
+#define PASN_CONFORMAL_MAX_ALPHAS 8
+#define PASN_CONFORMAL_LAC 0
+#define PASN_CONFORMAL_APS 1
+#define PASN_CONFORMAL_RAPS 2
+int pasn_conformal_scores(const float* probs, const int32_t* labels, long M, int K_real, int kind, int randomized, uint64_t seed,
+                          uint32_t salt, double lam, int k_reg, float* scores, float* own, int32_t* stratum, void* stream);
+size_t pasn_conformal_workspace_bytes(long M, int K_real, int A);
+int pasn_conformal_quantiles(const float* own, const int32_t* stratum, long M, int K_real, int A, const double* alphas, float* qhat,
+                             int64_t* n, int64_t* r, void* workspace, void* stream);
+int pasn_conformal_tally_words(int K_real);
+int pasn_conformal_sets(const float* scores, const float* qhat, const int32_t* labels, const float* u, long M, int K_real, int A,
+                        int mondrian, uint16_t* masks, int64_t* tallies, void* stream);
+
 /* Explanation faithfulness (faithfulness.py): deletion and insertion curves.  Do the voxels an occurrence map marks carry the prototype
  * similarity and the class probability?  The clip's voxels are removed (deletion) or inserted into a baseline (insertion) in the order of
  * the map, a step at a time, and the model is run on every perturbed copy.  The reference has no code for it; these definitions are the

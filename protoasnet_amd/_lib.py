@@ -187,6 +187,12 @@ SIGNATURES = {
     "pasn_temperature_workspace_bytes": (c_size_t, [c_long, c_int]),
     "pasn_temperature_fit": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "pasn_temperature_probs": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ---- conformal prediction sets (conformal.py)
+    "pasn_conformal_scores": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_uint64, c_uint, c_double, c_int] + [c_void_p] * 4),
+    "pasn_conformal_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "pasn_conformal_quantiles": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, POINTER(c_double)] + [c_void_p] * 5),
+    "pasn_conformal_tally_words": (c_int, [c_int]),
+    "pasn_conformal_sets": (c_int, [c_void_p] * 4 + [c_long, c_int, c_int, c_int] + [c_void_p] * 3),
     # ---- explanation faithfulness: deletion / insertion curves (faithfulness.py)
     "pasn_perturb_steps_workspace_bytes": (c_size_t, [c_long, c_long, c_int]),
     "pasn_perturb_steps": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),

@@ -14,7 +14,8 @@ definitions below ("Selective prediction"; ``include/protoasnet_
 * ``SelectiveEvaluator``: an ``EpochEvaluator(keep_logits=True)`` fed batch by batch together with the clips' file names; ``finish`` gives
   the curve read at a few coverages, per clip or per cine, with ONE synchronising device-to-host copy; ``finish(bootstrap=B)`` adds
   grouped-bootstrap confidence intervals (``bootstrap.py``) to the same read, ``finish(calibration=n_bins, temperature=...)`` reliability
-  bins, ECE and temperature-scaled probabilities (``calibration.py``).
+  bins, ECE and temperature-scaled probabilities (``calibration.py``), ``finish(conformal=fit)`` conformal prediction sets
+  (``conformal.py``).
 
 Everything runs on the device on the caller's stream; there is no CPU fallback.
 """
@@ -248,7 +249,8 @@ class SelectiveEvaluator:
         self.keys += keys
 
     def finish(self, coverages=DEFAULT_COVERAGES, level: str = "clip", bootstrap: int = 0, seed: int = 0, confidence: float = 0.95,
-               unit: str = "cine", calibration: int = 0, temperature=None) -> Dict[str, object]:
+               unit: str = "cine", calibration: int = 0, temperature=None, conformal=None,
+               conformal_mondrian: bool = False) -> Dict[str, object]:
         """``bootstrap=B > 0`` adds ``res["ci"]``: ``bootstrap.intervals`` of ``B`` grouped replicates (``seed``, ``confidence``) of the
         rows the level scores -- at cine level the cine predictions, the unit the cine; at clip level the clips, the unit the cine
         (``build_groups`` of the keys) or, with ``unit="clip"``, the clip.  Still one synchronising read; ``bootstrap=0`` is the call
@@ -260,7 +262,13 @@ class SelectiveEvaluator:
         ``res["calibration"]``: ``calibration.reliability(...).summary()`` of the level's rows (the clips; at cine level ``p_conf`` with
         the cine's label), and under ``["selective"]`` the same with ``conf = 1 - u`` -- is the uncertainty an honest probability of
         error? -- (``ece``, ``mce``, ``conf_gap``, ``bins``); with ``bootstrap=B`` ``res["ci"]`` gains the six calibration statistics, from
-        the same seed and units and therefore the same resamples.  Still one read; the defaults are the call without either."""
+        the same seed and units and therefore the same resamples.  Still one read; the defaults are the call without either.
+
+        ``conformal`` (a ``conformal.ConformalFit``) adds ``res["conformal"]``: ``{kind, mondrian, alphas, qhat, qhat_per_class,
+        levels}``, ``levels`` one ``ConformalSets.summary()`` dict per alpha of ``conformal.predict_sets`` on the rows the level scores
+        (the clips; at cine level ``p_conf.float()`` with the cine's label and ``u_mean``), after ``temperature`` if one is given;
+        ``conformal_mondrian`` takes each class's own threshold.  At cine level every entry of ``res["cines"]`` gains
+        ``"set@<alpha>"``, the list of class indices.  The same single read; ``conformal=None`` is the call without it."""
         if level not in ("clip", "cine"):
             raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
         if unit not in ("clip", "cine"):
@@ -284,10 +292,20 @@ class SelectiveEvaluator:
             if temperature is not None:
                 cal._check_temperature(temperature)
         n_bins = int(calibration)
+        conf = None
+        if conformal is not None:
+            from . import conformal as conf
+
+            if not isinstance(conformal, conf.ConformalFit):
+                raise ValueError(f"conformal must be a ConformalFit (conformal.calibrate) or None, got {conformal!r}")
+            if not isinstance(conformal_mondrian, (bool, np.bool_)):
+                raise ValueError(f"conformal_mondrian must be a bool, got {conformal_mondrian!r}")
         cs = _check_coverages(coverages)
         ev, K = self.ev, self.ev.K_real
         if ev.rows == 0:
             raise ValueError("no rows: call update() first")
+        if conf is not None and conformal.K != K:
+            raise ValueError(f"the conformal fit was calibrated on {conformal.K} classes, the evaluator scores {K}")
         probs, labels = ev.probs[: ev.rows], ev.labels[: ev.rows]
         if temperature is None:
             u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
@@ -298,7 +316,7 @@ class SelectiveEvaluator:
             u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
         if level == "clip":
             packed = risk_coverage(probs, labels, u).packed(cs)
-            if boot is None and not n_bins:
+            if boot is None and not n_bins and conf is None:
                 return self._result(RiskCoverage.unpack(packed.cpu(), cs))
             groups = build_groups(self.keys)[:2] if bootstrap and unit == "cine" else None
             parts = [packed]
@@ -306,8 +324,12 @@ class SelectiveEvaluator:
                 parts.append(boot.replicates(probs, labels, u, groups, bootstrap, seed).stats.flatten())
             if n_bins:
                 parts += self._calibration_parts(cal, probs, labels, u, groups, n_bins, bootstrap, seed)
+            if conf is not None:
+                parts += self._conformal_parts(conf, conformal, probs, labels, u, conformal_mondrian, masks=False)
             host = torch.cat(parts).cpu()  # the one read
             res = self._result(RiskCoverage.unpack(host[: packed.numel()], cs))
+            if conf is not None:
+                host = self._add_conformal(res, host, conf, conformal, conformal_mondrian, None)
             self._add_intervals(res, host[packed.numel():], boot, cal, n_bins, bootstrap, confidence)
             return res
         offsets, rows, names = build_groups(self.keys)
@@ -323,9 +345,15 @@ class SelectiveEvaluator:
             tail.append(boot.replicates(p, gl, gp.u_mean.float(), None, bootstrap, seed).stats.flatten())
         if n_bins:
             tail += self._calibration_parts(cal, p, gl, gp.u_mean.float(), None, n_bins, bootstrap, seed)
+        if conf is not None:
+            tail += self._conformal_parts(conf, conformal, p, gl, gp.u_mean.float(), conformal_mondrian, masks=True)
         host = torch.cat([rc.packed(cs)] + tail).cpu()  # the one read
         n_rc = 5 * len(cs) + 4
         res = self._result(RiskCoverage.unpack(host[:n_rc], cs))
+        masks = None
+        if conf is not None:
+            masks = host[host.numel() - len(conformal.alphas) * G:].view(len(conformal.alphas), G).long().tolist()
+            host = self._add_conformal(res, host, conf, conformal, conformal_mondrian, G)
         t = host[n_rc:]
         _raise_on_conflict(int(t[0]))
         from .trainer import confusion_to_metrics
@@ -338,8 +366,34 @@ class SelectiveEvaluator:
         um, lab, cnt, prd = (t[o + G * K + j * G: o + G * K + (j + 1) * G] for j in range(4))
         res["cines"] = [{"filename": n, "target_AS": l, "n_clips": c, "probs": p, "uncertainty": x, "pred": d}
                         for n, l, c, p, x, d in zip(names, lab.long().tolist(), cnt.long().tolist(), pc, um.tolist(), prd.long().tolist())]
+        if masks is not None:
+            for alpha, row in zip(conformal.alphas, masks):
+                for c, m in zip(res["cines"], row):
+                    c[f"set@{alpha:g}"] = conf.mask_classes(m, K)
         self._add_intervals(res, t[o + G * K + 4 * G:], boot, cal, n_bins, bootstrap, confidence)
         return res
+
+    @staticmethod
+    def _conformal_parts(conf, fit, probs, labels, u, mondrian: bool, masks: bool) -> List[torch.Tensor]:
+        """The device vectors ``conformal=fit`` adds at the END of the one read: the tallies, the thresholds and, at cine level, the
+        masks (every count is far below 2^53: fp64 carries it exactly)."""
+        sets = conf.predict_sets(probs, fit, labels, u, bool(mondrian))
+        parts = [sets.packed().double(), fit.qhat.double().flatten()]
+        if masks:  # (uint16 words through their int16 view: K_real = 16 may set bit 15)
+            parts.append((sets.masks.view(torch.int16).to(torch.int32) & 0xFFFF).double().flatten())
+        return parts
+
+    @staticmethod
+    def _add_conformal(res, host, conf, fit, mondrian: bool, G):
+        """Reads ``_conformal_parts`` off the end of ``host``, adds ``res["conformal"]`` and returns ``host`` without them."""
+        K, A = fit.K, len(fit.alphas)
+        n_t, n_q, n_m = A * conf.tally_words(K), (K + 1) * A, A * G if G is not None else 0
+        cut = host.numel() - n_t - n_q - n_m
+        q = host[cut + n_t: cut + n_t + n_q].view(K + 1, A)
+        res["conformal"] = {"kind": fit.kind, "mondrian": bool(mondrian), "alphas": list(fit.alphas), "qhat": q[0].tolist(),
+                            "qhat_per_class": q[1:].tolist(),
+                            "levels": conf.ConformalSets.unpack(host[cut: cut + n_t].numpy(), fit.alphas, K)}
+        return host[:cut]
 
     @staticmethod
     def _calibration_parts(cal, probs, labels, u, groups, n_bins: int, B: int, seed: int) -> List[torch.Tensor]:

@@ -100,6 +100,7 @@ class DPTrainer:
         self.device = next(model.parameters()).device
         self.current_epoch, self.current_iteration, self.best_metric = 0, 0, 0.0
         self.temperature_fit = None  # calibration.TemperatureFit of the last fit_temperature()
+        self.conformal_fit = None  # conformal.ConformalFit of the last fit_conformal()
         self.num_real_classes = model.num_classes - 1 if config.get("abstain_class") else model.num_classes
         self.get_criterion()
         self.get_optimizer()
@@ -453,7 +454,7 @@ class DPTrainer:
 
     def evaluate_selective(self, mode: str = "test", level: str = "cine", coverages=(1.0, 0.9, 0.8, 0.7, 0.5), score: str = "auto",
                            bootstrap: int = 0, seed: int = 0, confidence: float = 0.95, unit: str = "cine", calibration: int = 0,
-                           temperature=None) -> Dict[str, object]:
+                           temperature=None, conformal=None, conformal_mondrian: bool = False) -> Dict[str, object]:
         """Selective-prediction metrics of ``data_loaders[mode]`` (``protoasnet_amd.selective``): an eval-mode, forward-only sweep (no
         loss; the ``staged`` / ``prepare_input`` path of ``run_epoch``), the clips grouped by ``sample["filename"]`` -- with
         ``iterate_intervals`` every cardiac cycle of a cine is a row of its own -- and ``SelectiveEvaluator.finish(coverages, level)``'s
@@ -466,7 +467,11 @@ class DPTrainer:
         adds ``res["calibration"]`` (``protoasnet_amd.calibration``: reliability bins, ECE, MCE, class-wise ECE, Brier, NLL, confidence
         gap; with ``save_dir`` also ``save_dir/csv_<mode>_reliability/e<epoch>.csv``: ``bin, lo, hi, n, accuracy, confidence``), and
         ``temperature`` -- a float ``T > 0``, a ``calibration.TemperatureFit`` or ``"fitted"``: what ``fit_temperature`` left in
-        ``self.temperature_fit`` -- rescales the class probabilities the call scores.
+        ``self.temperature_fit`` -- rescales the class probabilities the call scores.  ``conformal`` -- a ``conformal.ConformalFit`` or
+        ``"fitted"``: what ``fit_conformal`` left in ``self.conformal_fit`` -- adds ``res["conformal"]`` (prediction sets of the level's
+        rows: coverage, set sizes, per-class and size-stratified coverage, mean uncertainty by set size; ``conformal_mondrian``: each
+        class its own threshold) and, at cine level, ``"set@<alpha>"`` to every cine; with ``save_dir`` also
+        ``save_dir/conformal_<mode>.csv``, one row per alpha.
 
         It issues NO collectives: each rank that calls it sweeps the loader it was given and reports on those rows alone (call it on one
         rank with the full loader, or on every rank for per-shard figures; ranks need not call it together).  The model is left in the
@@ -477,8 +482,15 @@ class DPTrainer:
             if self.temperature_fit is None:
                 raise ValueError("temperature='fitted' needs fit_temperature() first")
             temperature = self.temperature_fit
+        if isinstance(conformal, str):
+            if conformal != "fitted":
+                raise ValueError(f"conformal must be a ConformalFit, 'fitted' or None, got {conformal!r}")
+            if self.conformal_fit is None:
+                raise ValueError("conformal='fitted' needs fit_conformal() first")
+            conformal = self.conformal_fit
+        extra = {} if conformal is None else {"conformal": conformal, "conformal_mondrian": conformal_mondrian}  # (None: the call as it was)
         res = self._selective_sweep(mode, score).finish(coverages, level, bootstrap=bootstrap, seed=seed, confidence=confidence, unit=unit,
-                                                        calibration=calibration, temperature=temperature)
+                                                        calibration=calibration, temperature=temperature, **extra)
         self.log(f"Epoch: {self.current_epoch} | {mode} | selective ({level}) | AURC {res['aurc']:.4f} | error AUROC {res['error_auroc']:.4f}")
         if level == "cine" and self.config.get("save_dir"):
             d = os.path.join(self.config["save_dir"], f"csv_{mode}_cine")
@@ -497,6 +509,23 @@ class DPTrainer:
                 w.writerow(["bin", "lo", "hi", "n", "accuracy", "confidence"])
                 for j, b in enumerate(res["calibration"]["bins"]):
                     w.writerow([j, repr(b["lo"]), repr(b["hi"]), b["n"], repr(b["accuracy"]), repr(b["confidence"])])
+        if conformal is not None:
+            c = res["conformal"]
+            for lv in c["levels"]:
+                self.log(f"Epoch: {self.current_epoch} | {mode} | conformal {c['kind']} ({level}) | alpha {lv['alpha']:g} | coverage "
+                         f"{lv['coverage']:.4f} | mean set size {lv['mean_size']:.3f}")
+            if self.config.get("save_dir"):
+                import csv
+
+                os.makedirs(self.config["save_dir"], exist_ok=True)
+                with open(os.path.join(self.config["save_dir"], f"conformal_{mode}.csv"), "w", newline="") as f:
+                    w = csv.writer(f, lineterminator="\n")
+                    w.writerow(["alpha", "kind", "mondrian", "level", "qhat", "rows", "coverage", "mean_size", "empty", "singleton",
+                                "singleton_accuracy", "min_coverage_by_size"])
+                    for q, lv in zip(c["qhat"], c["levels"]):
+                        w.writerow([repr(lv["alpha"]), c["kind"], int(c["mondrian"]), level, repr(q), lv["rows"]]
+                                   + [repr(lv[k]) for k in ("coverage", "mean_size", "empty", "singleton", "singleton_accuracy",
+                                                            "min_coverage_by_size")])
         return res
 
     def _selective_sweep(self, mode: str, score: str = "auto"):
@@ -564,6 +593,49 @@ class DPTrainer:
         res = self.temperature_fit.read()
         self.log(f"Epoch: {self.current_epoch} | {mode} | temperature {res['temperature']:.4f} ({res['status']}) | "
                  f"NLL {res['nll_before']:.4f} -> {res['nll_after']:.4f}")
+        return res
+
+    def fit_conformal(self, mode: str = "val", alphas=(0.1,), kind: str = "aps", level: str = "cine", temperature=None,
+                      randomized: bool = True, seed: int = 0, lam: float = 0.0, k_reg: int = 1, score: str = "auto") -> Dict[str, object]:
+        """Conformal thresholds calibrated on ``data_loaders[mode]`` (``conformal.calibrate``; the forward-only sweep of
+        ``evaluate_selective``): keeps the device result in ``self.conformal_fit`` -- ``evaluate_selective(conformal="fitted")`` applies
+        it --, logs the thresholds and returns ``ConformalFit.read()``.  ``level="cine"`` (the default) calibrates on one row per
+        cine, ``p_conf.float()`` with the cine's label, exactly the rows ``evaluate_selective(level="cine")`` scores: the clips of one
+        cine are not exchangeable with the clips of another patient's, so a clip-level guarantee on correlated clips is not a
+        guarantee.  ``temperature`` as in ``evaluate_selective`` (apply the same one there).  No collectives; the model is left in the
+        mode it was in; no training or epoch state is touched."""
+        from . import calibration, conformal, selective
+
+        if level not in ("clip", "cine"):
+            raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
+        al = conformal.check_alphas(alphas)
+        conformal.check_settings(kind, randomized, seed, lam, k_reg)
+        if isinstance(temperature, str):
+            if temperature != "fitted":
+                raise ValueError(f"temperature must be a number, a TemperatureFit or 'fitted', got {temperature!r}")
+            if self.temperature_fit is None:
+                raise ValueError("temperature='fitted' needs fit_temperature() first")
+            temperature = self.temperature_fit
+        if temperature is not None:
+            calibration._check_temperature(temperature)
+        sel = self._selective_sweep(mode, score)
+        ev = sel.ev
+        if ev.rows == 0:
+            raise ValueError("no rows: the loader is empty")
+        logits, probs, labels = ev.logits[: ev.rows], ev.probs[: ev.rows], ev.labels[: ev.rows]
+        if temperature is not None:
+            probs = calibration.scaled_probs(logits, ev.K_real, temperature)
+        if level == "cine":
+            if temperature is not None and selective.score_mode(sel.abstain, sel.score, sel.ab_logitpath) == selective.MAXPROB:
+                u = 1.0 - probs.amax(dim=1)  # what scaled_probs(with_u=True) returns, bitwise
+            else:
+                u = selective.uncertainty(logits, sel.abstain, sel.score, sel.ab_logitpath)
+            gp = selective.group_predictions(probs, u, labels, selective.build_groups(sel.keys)[:2])
+            probs, labels = gp.p_conf.float(), gp.labels
+        self.conformal_fit = conformal.calibrate(probs, labels, al, kind, randomized, seed, lam, k_reg)
+        res = self.conformal_fit.read()
+        self.log(f"Epoch: {self.current_epoch} | {mode} | conformal {kind} ({level}) | n {res['n']} | "
+                 + " | ".join(f"alpha {a:g}: qhat {q:.6f}" for a, q in zip(res["alphas"], res["qhat"])))
         return res
 
     def evaluate_faithfulness(self, mode: str = "val", steps: int = 10, select: int = 1, max_clips: Optional[int] = None,
