@@ -896,6 +896,67 @@ int pasn_conformal_tally_words(int K_real);
 int pasn_conformal_sets(const float* scores, const float* qhat, const int32_t* labels, const float* u, long M, int K_real, int A,
                         int mondrian, uint16_t* masks, int64_t* tallies, void* stream);
 
+/* Out-of-distribution detection (ood.py): does a row look like anything the model was trained on?  A HIGHER score means MORE
+ * out-of-distribution.  The reference has no code for it; these definitions are the specification.  Every call is stream-ordered: no
+ * host synchronisation, no block waiting on another, no floating-point atomics.  The file is compiled without contraction: "rounded on
+ * its own" below means exactly that (no FMA).
+ *
+ * pasn_ood_head_scores: scores that need no fit, from sim [M][P] fp32 (the prototype similarities the last layer sees) and logits [M][K]
+ * fp32, one launch.  maxsim [M] fp32 = 1.0f - max_p sim[p]; a row with a NaN in sim gives NaN.  energy [M] fp32, in fp64 from the first
+ * K_real logits: m = max_k l_k, -(m + log(sum_k exp(l_k - m))), the sum taken in class order from 0.0, rounded once to fp32; a row with a
+ * NaN among them gives NaN.  Either output (with its input) may be NULL, not both.  1 <= M <= 2^20, 1 <= P <= 4096, 1 <= K_real <= K <=
+ * 4096.
+ *
+ * pasn_ood_knn: the k nearest rows of bank [Mb][E] fp32 for every row of q [Mq][E] fp32, exact.
+ *   Distance.  d(i, m) is accumulated in fp32 from 0.0f for j = 0 .. E - 1 in that order: t = q[i][j] - bank[m][j], acc = acc + t * t; the
+ *   subtraction, the product and the add each rounded on their own.  A function of the two rows only: two calls are bitwise equal
+ *   however the work is tiled.
+ *   Eligibility.  Bank row m is eligible for query i unless it holds a NaN, or self_base >= 0 and m == self_base + i (leave-one-out: the
+ *   queries are themselves rows self_base .. of the bank), or d(i, m) is NaN (inf - inf in some coordinate).
+ *   dist [Mq][k] fp32 and index [Mq][k] int32: the k eligible rows of smallest d in ascending d, the lower bank index first on ties;
+ *   entries past the number of eligible rows are +inf / -1; a query holding a NaN gets NaN / -1 throughout.  status [2] int64 = {bank
+ *   rows holding a NaN, query rows holding a NaN}; the call zeroes it.  The detector's score is dist[i][k - 1].
+ *   One memset and two launches whatever the sizes: the bank is split across blocks, each leaves per-query partial lists in
+ *   `workspace` (pasn_ood_knn_workspace_bytes(Mq, Mb, E, k) bytes, 16-byte aligned, no initialisation), a finish merges them in bank order.
+ *   1 <= E <= 1024, 1 <= k <= 64, 1 <= Mq <= 2^20, 1 <= Mb <= 2^24, -1 <= self_base <= Mb.
+ * pasn_ood_rows_normalize: y [M][E] = the rows of x [M][E] over their norm, one launch: n2 the fp32 sum of squares in j order from 0.0f
+ *   (product and add rounded on their own), y[j] = x[j] / sqrtf(n2), both correctly rounded; a row with n2 == 0 is copied unchanged.  y may
+ *   be x.  1 <= M <= 2^24, 1 <= E <= 1024.
+ *
+ * pasn_ood_moments: the sufficient statistics of class-conditional Gaussians with a shared covariance, from x [M][E] fp32 and labels [M]
+ *   int32.  A row is valid when 0 <= label < K and it holds no NaN; the others are skipped and counted.  n [K] int64 the valid rows per
+ *   class, sum [K][E] fp64 their sums, scatter [E][E] fp64 = sum x x^T over the valid rows, skipped [2] int64 = {rows with a label out
+ *   of range, rows with a label in range holding a NaN}.  Every term is exact in fp64; the order of the additions is fixed: the rows are
+ *   cut into chunks of pasn_ood_moment_chunk() consecutive rows (skipped rows included in the cut), a chunk is summed from 0.0 in row
+ *   order, and the chunk partials are added in chunk order from 0.0.  With accumulate != 0 the call's result is then added to what the
+ *   outputs hold (one addition); otherwise it overwrites them.  One memset and two launches.  `workspace`:
+ *   pasn_ood_moments_workspace_bytes(M, E, K) bytes, 16-byte aligned.  1 <= M <= 2^24, 1 <= E <= 256, 1 <= K <= 16.
+ * pasn_ood_mahalanobis: m [M][K] fp64, m_c = || W (x - mu_c) ||^2 from x [M][E] fp32, mu [K][E] fp64 and W [E][E] fp64 lower triangular
+ *   (the entries above the diagonal are not read), in fp64; the order of the sums inside is NOT defined (held to a bound, not bitwise).
+ *   score [M] fp32 = (float) min_c m_c over the classes with a finite mean (mu[c][0] finite), argclass [M] int32 that class, the lower
+ *   one on ties; NaN / -1 when no class qualifies.  One launch.  1 <= M <= 2^20, 1 <= E <= 256, 1 <= K <= 16.
+ *
+ * pasn_ood_tally: flags [A][M] uint8 and tallies [A][8] int64 from scores [M] fp32, kind [M] int32 (0 in-distribution, 1 shifted,
+ *   anything else a padding row), correct [M] int32 (or NULL) and tau [A] fp32.  A row is flagged iff score > tau or the score is NaN
+ *   (padding rows get their flag too).  Per level: id_rows, id_flagged, ood_rows, ood_flagged, nan_rows (rows of kind 0 or 1 with a NaN
+ *   score), id_correct_kept, id_kept, id_correct_flagged (the last three stay 0 without `correct`).  One memset and one launch; LDS
+ *   counters per block, then integer atomics.  1 <= M <= 2^20, 1 <= A <= 8.
+ *
+ * Anything else, or a NULL required pointer, returns PASN_ERR_ARG before any launch (the size queries return 0). */
+int pasn_ood_head_scores(const float* sim, const float* logits, long M, int P, int K, int K_real, float* maxsim, float* energy, void* stream);
+size_t pasn_ood_knn_workspace_bytes(long Mq, long Mb, int E, int k);
+int pasn_ood_knn(const float* q, const float* bank, long Mq, long Mb, int E, int k, long self_base, float* dist, int32_t* index,
+                 int64_t* status, void* workspace, void* stream);
+int pasn_ood_rows_normalize(const float* x, long M, int E, float* y, void* stream);
+int pasn_ood_moment_chunk(void);
+size_t pasn_ood_moments_workspace_bytes(long M, int E, int K);
+int pasn_ood_moments(const float* x, const int32_t* labels, long M, int E, int K, int accumulate, int64_t* n, double* sum, double* scatter,
+                     int64_t* skipped, void* workspace, void* stream);
+int pasn_ood_mahalanobis(const float* x, const double* mu, const double* W, long M, int E, int K, double* m, float* score, int32_t* argclass,
+                         void* stream);
+int pasn_ood_tally(const float* scores, const int32_t* kind, const int32_t* correct, const float* tau, long M, int A, uint8_t* flags,
+                   int64_t* tallies, void* stream);
+
 /* Explanation faithfulness (faithfulness.py): deletion and insertion curves.  Do the voxels an occurrence map marks carry the prototype
  * similarity and the class probability?  The clip's voxels are removed (deletion) or inserted into a baseline (insertion) in the order of
  * the map, a step at a time, and the model is run on every perturbed copy.  The reference has no code for it; these definitions are the

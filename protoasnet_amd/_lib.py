@@ -193,6 +193,16 @@ SIGNATURES = {
     "pasn_conformal_quantiles": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, POINTER(c_double)] + [c_void_p] * 5),
     "pasn_conformal_tally_words": (c_int, [c_int]),
     "pasn_conformal_sets": (c_int, [c_void_p] * 4 + [c_long, c_int, c_int, c_int] + [c_void_p] * 3),
+    # ---- out-of-distribution detection (ood.py)
+    "pasn_ood_head_scores": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "pasn_ood_knn_workspace_bytes": (c_size_t, [c_long, c_long, c_int, c_int]),
+    "pasn_ood_knn": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_long] + [c_void_p] * 5),
+    "pasn_ood_rows_normalize": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    "pasn_ood_moment_chunk": (c_int, []),
+    "pasn_ood_moments_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "pasn_ood_moments": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int] + [c_void_p] * 6),
+    "pasn_ood_mahalanobis": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int] + [c_void_p] * 4),
+    "pasn_ood_tally": (c_int, [c_void_p] * 4 + [c_long, c_int] + [c_void_p] * 3),
     # ---- explanation faithfulness: deletion / insertion curves (faithfulness.py)
     "pasn_perturb_steps_workspace_bytes": (c_size_t, [c_long, c_long, c_int]),
     "pasn_perturb_steps": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),

@@ -101,6 +101,7 @@ class DPTrainer:
         self.current_epoch, self.current_iteration, self.best_metric = 0, 0, 0.0
         self.temperature_fit = None  # calibration.TemperatureFit of the last fit_temperature()
         self.conformal_fit = None  # conformal.ConformalFit of the last fit_conformal()
+        self.ood_fit = None  # ood.OODFit of the last fit_ood(), with its detector, level and thresholds
         self.num_real_classes = model.num_classes - 1 if config.get("abstain_class") else model.num_classes
         self.get_criterion()
         self.get_optimizer()
@@ -683,6 +684,170 @@ class DPTrainer:
                          f"{c['acc_clean']:.4f} -> {c['acc_corrupted']:.4f} | flip rate {c['flip_rate']:.4f} | tv {c['tv']:.4f} | "
                          f"prob drop {c['prob_drop']:.4f} | top-{select} overlap {c['overlap']:.4f} | map corr {float(c['corr'][0]):.4f} | "
                          f"IoU {float(c['iou'][0]):.4f} | shift {float(c['shift'][0]):.4f}")
+        return res
+
+    # ---- out-of-distribution detection (protoasnet_amd.ood) ------------------------------------------------------------------------------
+    def _ood_sweep(self, mode: str, det, max_clips: Optional[int] = None, fit: bool = False, cells=(), seed: int = 0) -> Dict[str, object]:
+        """One forward-only ``push_forward`` sweep of ``data_loaders[mode]``: the rows' embedding, similarities, logits, labels and file
+        names (``fit``: the detector's bank and moments are filled on the way), and for every (corruption, severity) of ``cells`` the
+        same three of the corrupted copies (batch ``b`` corrupts with ``seed + b``).  Device tensors, concatenated; no read."""
+        from . import robustness
+
+        names = ("emb", "sim", "logits")
+        parts = {n: [] for n in names}
+        shifted = {c: {n: [] for n in names} for c in cells}
+        labels, keys = [], []
+
+        def outputs(x):
+            feats, proto_dist, _, logits = self.model.push_forward(x)
+            return det.embed(feats, proto_dist), (1 - proto_dist).float().contiguous(), logits.float().contiguous()
+
+        with self._forward_only(mode, head_b="out-of-distribution detection covers", max_clips=max_clips) as batches:
+            for b, (sample, x) in enumerate(batches):
+                n = int(x.shape[0])
+                out = outputs(x)
+                y = torch.as_tensor(sample["target_AS"])[:n].to(self.device, non_blocking=True)
+                if fit:
+                    det.fit_update(out[0], y)
+                for name, t in zip(names, out):
+                    parts[name].append(t)
+                labels.append(y)
+                keys += list(sample["filename"])[:n]
+                for c in cells:
+                    for name, t in zip(names, outputs(robustness.corrupt(x, c[0], c[1], seed + b))):
+                        shifted[c][name].append(t)
+        if not labels:
+            raise ValueError("no rows: the loader is empty")
+        rows = {n: torch.cat(v) for n, v in parts.items()}
+        rows.update(labels=torch.cat(labels), keys=keys, shifted={c: {n: torch.cat(v) for n, v in d.items()} for c, d in shifted.items()})
+        return rows
+
+    def _ood_level_rows(self, det, rows: Dict[str, object], level: str, groups=None, self_base: int = -1):
+        """``(scores, correct)`` of swept rows at ``level``: per detector the (M,) fp32 scores and whether the model's prediction is the
+        label; at cine level one row per cine -- the fp64 mean of its clips' scores in row order (``selective.group_predictions`` with
+        the score in the place of ``u``, ``u_mean`` cast once to fp32) and the cine's ``p_conf`` prediction."""
+        from . import calibration, selective
+
+        scores = det.scores(rows["emb"], rows["sim"], rows["logits"], self_base=self_base)
+        probs = calibration.scaled_probs(rows["logits"], self.num_real_classes, 1.0)
+        labels = rows["labels"].to(torch.int32)
+        if level == "clip":
+            return scores, (selective.first_largest(probs) == labels).to(torch.int32)
+        u = selective.uncertainty(rows["logits"], bool(self.config.get("abstain_class")))
+        gp = selective.group_predictions(probs, u, labels, groups, check=False)
+        correct = (selective.first_largest(gp.p_conf.float()) == gp.labels).to(torch.int32)
+        return {d: selective.group_predictions(probs, s, labels, groups, check=False).u_mean.float() for d, s in scores.items()}, correct
+
+    def fit_ood(self, bank: str = "train", calibrate: str = "val", level: str = "cine", tprs=(0.95,), max_bank: Optional[int] = None,
+                **detector_kw) -> Dict[str, object]:
+        """Fits the out-of-distribution detectors (``protoasnet_amd.ood.OODDetector(**detector_kw)``: ``detectors``, ``embedding``, ``k``,
+        ``normalize``, ``shrink``) and calibrates their thresholds.  One forward-only ``push_forward`` sweep of ``data_loaders[bank]``
+        (its first ``max_bank`` clips) fills the kNN bank and the Mahalanobis moments; one sweep of ``data_loaders[calibrate]`` gives
+        the in-distribution scores whose ``ceil((n + 1) tpr)``-th smallest is the threshold of level ``tpr``: an exchangeable
+        in-distribution row is then flagged with probability at most ``1 - tpr``.  ``level="cine"`` (the default) calibrates on one row
+        per cine, the fp64 mean of its clips' scores -- the clips of one cine are not exchangeable with another patient's, so a
+        clip-level guarantee on correlated clips is not a guarantee (``fit_conformal``); ``level="clip"`` calibrates on the rows.  With
+        ``bank == calibrate`` the rows of the one sweep are scored against the bank they are in, and the kNN scan leaves every row out
+        of its own neighbours; the Mahalanobis fit is NOT leave-one-out (its means and covariance include the row), so its thresholds
+        are optimistic then.  Keeps the fit, with its detector, level and thresholds, in ``self.ood_fit`` -- ``evaluate_ood`` applies it
+        --, logs the thresholds and returns ``{level, bank_rows, rows, tprs, detectors: {name: {tau, n, nan_rows}}}``.  Without an
+        abstention class the default detectors leave ``"abstain"`` out.  No collectives; the model is left in the mode it was in; no
+        training or epoch state is touched."""
+        from . import ood, selective
+
+        if level not in ("clip", "cine"):
+            raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
+        tp = ood.check_tprs(tprs)
+        ood.OODDetector(**detector_kw)  # the detector's own checks, before any sweep
+        abstain = bool(self.config.get("abstain_class"))
+        kw = dict(detector_kw)
+        kw.setdefault("abstain_class", abstain)
+        kw.setdefault("num_classes", self.num_real_classes)
+        if not abstain:
+            kw.setdefault("detectors", tuple(d for d in ood.DETECTORS if d != "abstain"))
+        det = ood.OODDetector(**kw)
+        rows = self._ood_sweep(bank, det, max_clips=max_bank, fit=True)
+        fit = det.fit_finish()
+        same = bank == calibrate
+        cal = rows if same else self._ood_sweep(calibrate, det)
+        groups = selective.build_groups(cal["keys"])[:2] if level == "cine" else None
+        scores, _ = self._ood_level_rows(det, cal, level, groups, self_base=0 if same else -1)
+        th = det.calibrate(scores, tp)
+        fit.detector, fit.level = det, level
+        self.ood_fit = fit
+        res = th.read()
+        res.update(level=level, bank_rows=int(rows["emb"].shape[0]), rows=int(next(iter(scores.values())).shape[0]))
+        for d, r in res["detectors"].items():
+            self.log(f"Epoch: {self.current_epoch} | {calibrate} | ood {d} ({level}) | n {r['n']} | "
+                     + " | ".join(f"tpr {t:g}: tau {q:.6f}" for t, q in zip(res["tprs"], r["tau"])))
+        return res
+
+    def evaluate_ood(self, mode: str = "test", shift="corruptions", corruptions: Optional[Sequence[str]] = None,
+                     severities: Sequence[int] = (1, 3, 5), level: str = "cine", max_clips: Optional[int] = None,
+                     seed: int = 0) -> Dict[str, object]:
+        """Do the fitted detectors (``fit_ood``) tell shifted clips from ``data_loaders[mode]``'s?  In-distribution scores come from the
+        split; shifted scores from the SAME clips through ``robustness.corrupt``, per (corruption, severity) cell (``corruptions=None``:
+        all of ``robustness.CORRUPTIONS``), or, when ``shift`` names a loader, from ``data_loaders[shift]`` (one cell, severity 0).
+        Returns ``{level, rows, tprs, detectors: {name: {tau, id_flagged_rate, accuracy_kept, accuracy_flagged (one per tpr),
+        nan_rows, cells: {cell: {severity: {auroc, flagged_rate (one per tpr), rows}}}}}}``: the rate at the FITTED threshold and the
+        AUROC (shifted rows positive), not the literature's FPR@95, whose threshold is chosen on the test rows themselves.  ``level``
+        must be the fit's (a cine's mean score and a clip's do not share a threshold).  Tallies stay on the device until the ONE read
+        at the end.  Each rank sweeps its own loaders; no collectives, no training or epoch state; the model is left in the mode it
+        was in."""
+        from . import ood, robustness, selective
+
+        if self.ood_fit is None or self.ood_fit.thresholds is None:
+            raise ValueError("evaluate_ood needs fit_ood() first")
+        if level not in ("clip", "cine"):
+            raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
+        det, th = self.ood_fit.detector, self.ood_fit.thresholds
+        if level != self.ood_fit.level:
+            raise ValueError(f"the thresholds were calibrated at level {self.ood_fit.level!r} (fit_ood), not {level!r}")
+        if shift == "corruptions":
+            names = tuple(robustness.CORRUPTIONS) if corruptions is None else tuple(corruptions)
+            cells = [(n, int(s)) for n in names for s in severities]
+            for n, s in cells:
+                robustness.describe(n, s, (1, 1, 2, 2, 2))  # unknown names and severities fail here, not in the middle of a sweep
+            if not cells:
+                raise ValueError("at least one corruption and one severity")
+        elif isinstance(shift, str) and shift in self.data_loaders:
+            cells = []
+        else:
+            raise ValueError(f"shift must be 'corruptions' or a key of data_loaders, got {shift!r}")
+        rows = self._ood_sweep(mode, det, max_clips=max_clips, cells=tuple(cells), seed=seed)
+        groups = selective.build_groups(rows["keys"])[:2] if level == "cine" else None
+        s_id, correct = self._ood_level_rows(det, rows, level, groups)
+        shifted = []
+        for c in cells:
+            shifted.append((c, self._ood_level_rows(det, dict(rows, **rows["shifted"][c]), level, groups)[0]))
+        if not cells:
+            other = self._ood_sweep(shift, det, max_clips=max_clips)
+            g2 = selective.build_groups(other["keys"])[:2] if level == "cine" else None
+            shifted.append(((shift, 0), self._ood_level_rows(det, other, level, g2)[0]))
+        n_id = int(correct.shape[0])
+        packed, counts = [torch.cat([th.tau[d].double() for d in s_id])], []
+        for c, s_c in shifted:
+            n_c = int(next(iter(s_c.values())).shape[0])
+            kind = torch.cat([torch.zeros(n_id, dtype=torch.int32, device=self.device), torch.ones(n_c, dtype=torch.int32, device=self.device)])
+            ok = torch.cat([correct, torch.zeros(n_c, dtype=torch.int32, device=self.device)])
+            packed.append(ood.evaluate({d: torch.cat([s_id[d], s_c[d]]) for d in s_id}, kind, th, ok).packed())
+            counts.append(n_c)
+        host = torch.cat(packed).cpu().numpy()  # the one read
+        dets, A = list(s_id), len(th.tprs)
+        res = {"level": level, "rows": n_id, "tprs": list(th.tprs), "detectors": {}}
+        per = len(dets) * (A * ood.TALLY_WORDS + 1)
+        evs = [ood.OODEvaluation.unpack(host[len(dets) * A + j * per: len(dets) * A + (j + 1) * per], dets, th.tprs) for j in range(len(shifted))]
+        for i, d in enumerate(dets):
+            first = evs[0][d]["levels"]
+            out = {"tau": host[i * A: (i + 1) * A].tolist(), "id_flagged_rate": [lv["id_flagged_rate"] for lv in first],
+                   "accuracy_kept": [lv["accuracy_kept"] for lv in first], "accuracy_flagged": [lv["accuracy_flagged"] for lv in first],
+                   "nan_rows": first[0]["nan_rows"], "cells": {}}
+            for (c, _), ev, n_c in zip(shifted, evs, counts):
+                out["cells"].setdefault(c[0], {})[c[1]] = {"auroc": ev[d]["auroc"], "rows": n_c,
+                                                          "flagged_rate": [lv["ood_flagged_rate"] for lv in ev[d]["levels"]]}
+                self.log(f"Epoch: {self.current_epoch} | {mode} | ood {d} ({level}) | {c[0]} severity {c[1]} | AUROC {ev[d]['auroc']:.4f} | "
+                         f"flagged {ev[d]['levels'][0]['ood_flagged_rate']:.4f} (in-distribution {first[0]['id_flagged_rate']:.4f})")
+            res["detectors"][d] = out
         return res
 
     def push(self, replace_prototypes: bool = True):
