@@ -1005,6 +1005,63 @@ int pasn_perturb_curves(const float* sim, const float* logits, const int32_t* se
                         int S1, int P, int K, int K_real, long V, float* curve_sim, float* curve_prob, double* auc, double* acc,
                         void* stream);
 
+/* Black-box saliency (saliency.py): RISE (Petsiuk, Das, Saenko, BMVC 2018) as the baseline the occurrence maps' faithfulness is compared
+ * with.  The model is run on many randomly masked copies of a clip and the masks are averaged, weighted by the score.  The masks are never
+ * stored: a mask is a function of (seed, clip id, mask index) through Philox and is regenerated wherever it is needed, and every sum runs
+ * in a fixed order, so a map is reproducible bit for bit and does not depend on which batch the clip arrived in.  The reference has no
+ * code for it; these definitions are the specification (tests/saliency_cases.py restates them in numpy).  Every call is stream-ordered:
+ * no host synchronisation, no global atomics, no block waiting on another.
+ *
+ * Geometry.  A clip has V = T H W voxels (images: T = 1).  A coarse grid (gt, gh, gw) gives the cells ct = ceil(T / gt), ch = ceil(H / gh),
+ * cw = ceil(W / gw) and a lattice of (gt + 2)(gh + 2)(gw + 2) points.  keep is a uint32, min(2^32 - 1, floor(p 2^32)) of the keep
+ * probability p, computed by the host.  seed: 64 bits, the Philox key is (seed & 0xffffffff, seed >> 32).  clip = clip0 + n (mod 2^32) is
+ * the caller's id of clip n of the call.
+ *   lattice bit   of point c = (it (gh + 2) + iy)(gw + 2) + ix of mask m: word c & 3 of philox4x32_10(counter (c >> 2, m, clip, 0), key);
+ *                 1.0f iff that word < keep, else 0.0f
+ *   shift         of mask m: the words w of philox4x32_10((0, m, clip, 1), key); st = (w0 ct) >> 32, sh = (w1 ch) >> 32, sw = (w2 cw) >> 32
+ *                 (the multiply-shift of the bootstrap's draws)
+ *   mask value    at voxel (t, y, x), all fp32, every multiply and add rounded on its own (no contraction, as the OOD distances):
+ *                 px = x + sw, ix = px / cw (integers), fx = (float)(px - ix cw) / (float)cw (IEEE division); the same along H and T;
+ *                 lerp(a, b, f) = a + (b - a) f; first along W (four times), then along H (twice), then along T.
+ *                 ix + 1 <= gw + 1 (the lattice has g + 2 points per axis for that), the value lies in [0, 1]; T = 1 gives ft = 0 and
+ *                 the lower plane exactly.
+ *
+ * pasn_rise_apply: the masked copies of the clips for the masks m0 .. m0 + Mc - 1.  x [N][C][V] (PASN_F32 / PASN_BF16), baseline of the
+ * same shape and dtype or NULL (then every baseline element is `fill`, rounded to the dtype once, to nearest even).
+ *   out [N][Mc][C][V] = b + (x - b) mask: x and b widened to fp32, every operation rounded on its own, the result rounded to the dtype
+ *   once, to nearest even; a NaN result is the canonical quiet NaN (0x7fc00000 / 0x7fc0).  One mask serves the C channels of a voxel.
+ * One launch; a block owns 4096 voxels of one (n, m): it generates the mask's lattice in LDS, computes the 4096 mask values once and walks
+ * the C channels.  16-byte stores wherever the output address allows (a row's head and tail element by element), 16-byte loads where the
+ * input addresses allow.  1 <= N <= 65 535, 0 <= m0, 1 <= Mc, m0 + Mc <= 65 535, 1 <= C <= 64.
+ *
+ * pasn_rise_scores: after the model has run on the masked copies, in [n][m] order with ALL M masks: sim [N M][P] fp32, logits [N M][K] fp32.
+ *   scores [N][M][k] fp32.  target 0 (prototype): sim[row][sel[n][j]], a copy (sel [N][k] int32; logits, cls may be NULL).
+ *   target 1 (class), k = 1: softmax(logits[row][0 .. K_real))[cls[n]] with pasn_perturb_curves' arithmetic (the largest logit
+ *   subtracted, expf, the sum in column order, one IEEE division; cls [N] int32; sim, sel may be NULL), K_real <= 16, K_real <= K <= 17.
+ * An entry of sel outside [0, P) or of cls outside [0, K_real) gives NaN, nothing is read out of bounds.
+ *
+ * pasn_rise_maps: S[n][j][v] = sum_m (double)scores[n][m][j] (double)mask_m[v] and Cov[n][v] = sum_m (double)mask_m[v], both with m
+ * ascending in fp64 (the product of two fp32 values is exact in fp64, so contracting it into the sum cannot change the result).
+ *   norm 0 (coverage): S / Cov, 0 where Cov == 0;  norm 1 (expected): S / ((double)M ((double)keep / 4294967296.0)); rounded to fp32 once.
+ *   saliency [N][k][V] fp32 (or NULL), cov [N][V] fp64 (or NULL), maps [N][k][V] uint8 (or NULL) by pasn_explain_maps' rule, so that both
+ *   kinds of map are on one scale: min / max over the map's V fp32 values, v = (s - min) / ((max - min) + 1e-7f), (uint8)(255.0f v)
+ *   truncated.  A map that holds a NaN has an unspecified uint8 map.
+ * Launches: the lattices and shifts of all (n, m) into the workspace; per group of at most four maps one launch in which a thread owns a
+ * voxel and walks the masks (staged in LDS, pasn_rise_stage_masks(gt, gh, gw) at a time) with one fp64 accumulator per map and one for
+ * the coverage, and leaves the block's extrema in the workspace; one launch that combines the extrema and quantises.
+ * `workspace`: pasn_rise_maps_workspace_bytes(...) bytes, 16-byte aligned, no initialisation.  1 <= M <= 65 535, N k <= 65 535.
+ *
+ * Everywhere: 1 <= gt <= 16, 1 <= gh, gw <= 32, at most 8 192 lattice points, T, H, W >= 1, V < 2^31, keep >= 1; anything else, or a NULL
+ * required pointer, returns PASN_ERR_ARG before any launch (the size queries return 0). */
+int pasn_rise_apply(const void* x, const void* baseline, float fill, int N, int C, int T, int H, int W, int gt, int gh, int gw,
+                    uint32_t keep, uint64_t seed, uint32_t clip0, int m0, int Mc, int dtype, void* out, void* stream);
+int pasn_rise_scores(const float* sim, const float* logits, const int32_t* sel, const int32_t* cls, int N, int M, int k, int P, int K,
+                     int K_real, int target, float* scores, void* stream);
+int pasn_rise_stage_masks(int gt, int gh, int gw);
+size_t pasn_rise_maps_workspace_bytes(int N, int k, int M, int T, int H, int W, int gt, int gh, int gw);
+int pasn_rise_maps(const float* scores, int N, int k, int M, int T, int H, int W, int gt, int gh, int gw, uint32_t keep, uint64_t seed,
+                   uint32_t clip0, int norm, float* saliency, uint8_t* maps, double* cov, void* workspace, void* stream);
+
 /* Robustness (robustness.py): echo-style corruptions of a clip, and the stability of the prediction and of its explanation under them.
  * Does the prototype explanation survive the perturbations the class prediction survives?  The reference has no code for it; these
  * definitions are the specification.  Every call is stream-ordered: no host synchronisation, no allocation, no global atomics, no block

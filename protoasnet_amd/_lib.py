@@ -208,6 +208,12 @@ SIGNATURES = {
     "pasn_perturb_steps": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),
     "pasn_perturb_apply": (c_int, [c_void_p] * 4 + [c_float, c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
     "pasn_perturb_curves": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_long] + [c_void_p] * 5),
+    # ---- black-box saliency: RISE masks, scores and maps (saliency.py)
+    "pasn_rise_apply": (c_int, [c_void_p, c_void_p, c_float] + [c_int] * 8 + [c_uint, c_uint64, c_uint, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "pasn_rise_scores": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p]),
+    "pasn_rise_stage_masks": (c_int, [c_int] * 3),
+    "pasn_rise_maps_workspace_bytes": (c_size_t, [c_int] * 9),
+    "pasn_rise_maps": (c_int, [c_void_p] + [c_int] * 9 + [c_uint, c_uint64, c_uint, c_int] + [c_void_p] * 5),
     # ---- robustness: clip corruptions and explanation stability (robustness.py)
     "pasn_clip_corrupt": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [POINTER(CorruptDesc), c_void_p]),
     "pasn_stability_stats": (c_int, [c_void_p] * 7 + [c_int] * 9 + [c_void_p] * 6),

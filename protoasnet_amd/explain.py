@@ -58,12 +58,13 @@ def _is_xproto(model) -> bool:
 # entry point -> the words of its messages: what it covers, why PPNet is out
 _COVERS = {"explain": ("local explanations cover", "the reference has none for PPNet"),
            "faithfulness": ("faithfulness curves cover", "PPNet has no occurrence maps"),
+           "saliency": ("RISE saliency covers", "PPNet has no occurrence maps to compare it with"),
            "robustness": ("robustness evaluation covers", "PPNet has no occurrence maps")}
 
 
 def _check_model(model, x: torch.Tensor, what: str, maps: Optional[str] = None) -> None:
     """A head-B model, in eval mode, with its input on the GPU: the checks of ``explain_batch`` (``what`` = "explain", which also
-    passes its ``maps``), ``perturbation_curves`` ("faithfulness") and ``stability`` ("robustness"), in the order they fire."""
+    passes its ``maps``), ``perturbation_curves`` ("faithfulness"), ``rise`` ("saliency") and ``stability`` ("robustness"), in the order they fire."""
     covers, why = _COVERS[what]
     if not _is_xproto(model):
         raise NotImplementedError(f"{covers} XProtoNet and Video_XProtoNet; {why}")

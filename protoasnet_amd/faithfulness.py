@@ -6,7 +6,8 @@ clip's voxels are ordered by the map (level descending, flat index ascending), a
 * **deletion**: replaced by the baseline -- a faithful map makes the score fall early (a SMALL area under the curve);
 * **insertion**: the only ones taken from the clip, the rest is baseline -- a faithful map makes the score rise early (a LARGE area).
 
-Both are compared with the same curves under a random map (``saliency="random"``).  The reference has no code for this: the definitions
+Both are compared with the same curves under a random map (``saliency="random"``) and, on request, under a RISE map obtained without
+looking inside the model (``saliency="rise"``, ``saliency.py``).  The reference has no code for this: the definitions
 in ``include/protoasnet_amd.h`` ("Explanation faithfulness") are the specification, ``tests/faithfulness_cases.py`` their
 numpy restatement.
 
@@ -199,11 +200,14 @@ def _run_mode(model, x, steps_vol, counts_dev, fractions, code: int, selected, p
 
 def perturbation_curves(model, x: torch.Tensor, select: int = 1, steps: Union[int, Sequence[float]] = 10, mode: str = "both",
                         saliency=None, baseline: Optional[torch.Tensor] = None, fill: float = 0.0, max_batch: int = 64,
-                        abstain_class: bool = True, seed: int = 0, _acc: Optional[Dict[str, torch.Tensor]] = None):
+                        abstain_class: bool = True, seed: int = 0, _acc: Optional[Dict[str, torch.Tensor]] = None,
+                        rise: Optional[Dict[str, object]] = None):
     """Deletion / insertion curves of the clips ``x`` (the model's input, on the GPU) for the ``select`` best prototypes of the predicted
     class.  ``steps``: an int (``step_counts(V, steps)``) or a sequence of fractions.  ``mode``: "deletion", "insertion" (a ``Curves``) or
     "both" (a ``CurvePair``).  ``saliency``: None = the model's own uint8 occurrence maps (``explain_batch(maps="uint8")``), a uint8 tensor
-    (N, select, [To,] Ho, Wo) of the caller's, or "random" (``random_saliency(x, select, seed)``, the control).  ``baseline``: a tensor like
+    (N, select, [To,] Ho, Wo) of the caller's, "random" (``random_saliency(x, select, seed)``, the control) or "rise" (the uint8 maps of
+    ``saliency.rise(model, x, select=select, abstain_class=abstain_class, **rise)``, the black-box baseline; ``rise`` holds its other
+    arguments: masks, grid, p, target, norm, seed, clip0, max_batch, baseline, fill).  ``baseline``: a tensor like
     ``x`` (a blurred clip, say) or None for the scalar ``fill`` (0 = the mean grey of a normalised clip).  The perturbed clips go through
     ``model.forward`` at most ``max_batch`` at a time, every chunk of steps with the same batch size, so that one plan is compiled (a last,
     smaller group of clips compiles a second one).  Step 0 of the default counts is the untouched clip under deletion and the baseline
@@ -214,6 +218,8 @@ def perturbation_curves(model, x: torch.Tensor, select: int = 1, steps: Union[in
     if mode not in MODES + ("both",):
         raise ValueError(f"mode must be 'deletion', 'insertion' or 'both', got {mode!r}")
     k = _int_select(select, "maps per clip")
+    if rise is not None and saliency != "rise":
+        raise ValueError("rise holds the arguments of saliency='rise' and goes with nothing else")
     if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)) or max_batch < 1:
         raise ValueError(f"max_batch must be a positive integer, got {max_batch!r}")
     _, grid = _clip_geometry(x)
@@ -227,9 +233,14 @@ def perturbation_curves(model, x: torch.Tensor, select: int = 1, steps: Union[in
         if own:
             maps = ex.maps
         elif isinstance(saliency, str):
-            if saliency != "random":
-                raise ValueError(f"saliency must be None, 'random' or a uint8 tensor, got {saliency!r}")
-            maps = random_saliency(x, k, seed)
+            if saliency == "rise":
+                from .saliency import rise as rise_maps
+
+                maps = rise_maps(model, x, **{**dict(rise or {}), "select": k, "maps": "uint8", "abstain_class": abstain_class}).maps
+            elif saliency == "random":
+                maps = random_saliency(x, k, seed)
+            else:
+                raise ValueError(f"saliency must be None, 'random', 'rise' or a uint8 tensor, got {saliency!r}")
         else:
             maps = saliency
             if not isinstance(maps, torch.Tensor) or maps.dtype != torch.uint8 or maps.numel() != x.shape[0] * k * V or maps.shape[:2] != (x.shape[0], k):
@@ -248,33 +259,48 @@ def perturbation_curves(model, x: torch.Tensor, select: int = 1, steps: Union[in
 
 class FaithfulnessAccumulator:
     """The sums of a sweep: per batch the curves of the model's maps and of the random control (batch ``b`` draws it with ``seed + b``),
-    both modes, added on the device onto fp64 accumulators (clips in ascending order); ``result()`` is the ONE synchronising read."""
+    both modes, added on the device onto fp64 accumulators (clips in ascending order); ``result()`` is the ONE synchronising read.
+    ``kinds``: which maps are swept, "model" first; "rise" adds the black-box baseline (``saliency.rise`` with the arguments ``rise``,
+    ``seed`` unless it names its own, and ``clip0`` = its own plus the clips seen so far: a clip's masks do not depend on the batching)."""
 
     KINDS = ("model", "random")
+    ALL_KINDS = ("model", "random", "rise")
 
-    def __init__(self, model, select: int = 1, steps=10, fill: float = 0.0, max_batch: int = 64, abstain_class: bool = True, seed: int = 0):
+    def __init__(self, model, select: int = 1, steps=10, fill: float = 0.0, max_batch: int = 64, abstain_class: bool = True, seed: int = 0,
+                 kinds: Sequence[str] = KINDS, rise: Optional[Dict[str, object]] = None):
+        kinds = tuple(kinds)
+        if not kinds or kinds[0] != "model" or len(set(kinds)) != len(kinds) or any(kd not in self.ALL_KINDS for kd in kinds):
+            raise ValueError(f"kinds must start with 'model' and add any of 'random', 'rise' once, got {kinds!r}")
+        if rise is not None and "rise" not in kinds:
+            raise ValueError("rise holds the arguments of the 'rise' kind, which is not swept")
+        self.kinds, self.rise, self.clips = kinds, dict(rise or {}), 0
         self.model, self.select, self.steps, self.fill, self.max_batch = model, int(select), steps, fill, max_batch
         self.abstain_class, self.seed = abstain_class, int(seed)
         self.S1 = (int(steps) + 1) if isinstance(steps, (int, np.integer)) else len(steps)
         self.batches = 0
-        self.acc = None       # (2 kinds, 2 modes, accumulator_size) fp64, on the first batch's device
+        self.acc = None       # (kinds, 2 modes, accumulator_size) fp64, on the first batch's device
         self.fractions = None
 
     def update(self, x: torch.Tensor) -> None:
         if self.acc is None:
-            self.acc = torch.zeros((2, 2, accumulator_size(self.select, self.S1)), dtype=torch.float64, device=x.device)
-        for i, kind in enumerate(self.KINDS):
+            self.acc = torch.zeros((len(self.kinds), 2, accumulator_size(self.select, self.S1)), dtype=torch.float64, device=x.device)
+        for i, kind in enumerate(self.kinds):
+            args = None
+            if kind == "rise":
+                args = {"seed": self.seed, **self.rise, "clip0": int(self.rise.get("clip0", 0)) + self.clips}
             pair = perturbation_curves(self.model, x, select=self.select, steps=self.steps, mode="both",
-                                       saliency=None if kind == "model" else "random", fill=self.fill, max_batch=self.max_batch,
+                                       saliency=None if kind == "model" else kind, fill=self.fill, max_batch=self.max_batch,
                                        abstain_class=self.abstain_class, seed=self.seed + self.batches,
-                                       _acc={m: self.acc[i, j] for j, m in enumerate(MODES)})
+                                       _acc={m: self.acc[i, j] for j, m in enumerate(MODES)}, rise=args)
         self.fractions = pair.deletion.fractions
         self.batches += 1
+        self.clips += int(x.shape[0])
 
     def result(self) -> Dict[str, object]:
         """``{clips, fractions, deletion, insertion, random: {deletion, insertion}, difference: {deletion, insertion}}``: per mode the mean
         curves ``similarity`` / ``prob`` (k, S1) and the mean areas ``auc_similarity`` / ``auc_prob`` (k,), numpy float64; ``difference`` is
-        model minus random for the areas (faithful maps: negative under deletion, positive under insertion)."""
+        model minus random for the areas (faithful maps: negative under deletion, positive under insertion).  ``random`` and ``difference``
+        come with the "random" kind; the "rise" kind adds ``rise`` and ``difference_rise`` (model minus RISE) of the same layout."""
         if self.acc is None:
             raise ValueError("no clips: update() was never called")
         k, S1 = self.select, self.S1
@@ -288,6 +314,8 @@ class FaithfulnessAccumulator:
 
         res = {"clips": int(host[0, 0, -1]), "fractions": fractions}
         res.update({m: unpack(host[0, j]) for j, m in enumerate(MODES)})
-        res["random"] = {m: unpack(host[1, j]) for j, m in enumerate(MODES)}
-        res["difference"] = {m: {a: res[m][a] - res["random"][m][a] for a in ("auc_similarity", "auc_prob")} for m in MODES}
+        for i, kind in enumerate(self.kinds[1:], 1):
+            res[kind] = {m: unpack(host[i, j]) for j, m in enumerate(MODES)}
+            res["difference" if kind == "random" else f"difference_{kind}"] = \
+                {m: {a: res[m][a] - res[kind][m][a] for a in ("auc_similarity", "auc_prob")} for m in MODES}
         return res

@@ -460,6 +460,12 @@ class _XProtoHeadMixin:
 
         return perturbation_curves(self, x, **kw)
 
+    def rise(self, x: torch.Tensor, **kw):
+        """RISE saliency maps of the clips ``x``, the black-box baseline of the faithfulness curves (saliency.rise)."""
+        from .saliency import rise
+
+        return rise(self, x, **kw)
+
     def robustness(self, x: torch.Tensor, corruption, severity=None, **kw):
         """Stability of the prediction and of its occurrence maps on the clips ``x`` under one corruption (robustness.robustness)."""
         from .robustness import robustness

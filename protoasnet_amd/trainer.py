@@ -640,25 +640,28 @@ class DPTrainer:
         return res
 
     def evaluate_faithfulness(self, mode: str = "val", steps: int = 10, select: int = 1, max_clips: Optional[int] = None,
-                              max_batch: int = 64, seed: int = 0) -> Dict[str, object]:
+                              max_batch: int = 64, seed: int = 0, kinds: Sequence[str] = ("model", "random"),
+                              rise: Optional[Dict[str, object]] = None) -> Dict[str, object]:
         """Are the occurrence maps faithful on ``data_loaders[mode]``?  (``protoasnet_amd.faithfulness``)  An eval-mode sweep: per batch
         (through ``prepare_input``) the deletion and insertion curves of the ``select`` best prototypes of the predicted class under the
         model's maps and under a random map, summed in fp64 on the device and read once.  Returns
-        ``FaithfulnessAccumulator.result()``: the mean curves, the mean areas, the random control's and their differences.  ``max_clips``
-        ends the sweep after that many clips.  Each rank sweeps its own loader; no collectives, no training or epoch state; the model is
+        ``FaithfulnessAccumulator.result()``: the mean curves, the mean areas, the random control's and their differences.  With "rise"
+        among ``kinds`` the same curves are swept under RISE maps (``saliency.rise`` with the arguments ``rise``), the black-box baseline:
+        ``res["rise"]`` and ``res["difference_rise"]``, and one more log line.  ``max_clips`` ends the sweep after that many clips.  Each rank sweeps its own loader; no collectives, no training or epoch state; the model is
         left in the mode it was in."""
         from . import faithfulness
 
         with self._forward_only(mode, head_b="faithfulness curves cover", max_clips=max_clips) as batches:
             acc = faithfulness.FaithfulnessAccumulator(self.model, select=select, steps=steps, max_batch=max_batch,
-                                                       abstain_class=bool(self.config.get("abstain_class")), seed=seed)
+                                                       abstain_class=bool(self.config.get("abstain_class")), seed=seed, kinds=kinds, rise=rise)
             for _, x in batches:
                 acc.update(x)
         res = acc.result()
-        self.log(f"Epoch: {self.current_epoch} | {mode} | faithfulness ({res['clips']} clips) | deletion AUC (prob) "
-                 f"{float(res['deletion']['auc_prob'].mean()):.4f} vs random {float(res['random']['deletion']['auc_prob'].mean()):.4f} | "
-                 f"insertion AUC (prob) {float(res['insertion']['auc_prob'].mean()):.4f} vs random "
-                 f"{float(res['random']['insertion']['auc_prob'].mean()):.4f}")
+        for kind in acc.kinds[1:] or ("model",):
+            versus = {m: f" vs {kind} {float(res[kind][m]['auc_prob'].mean()):.4f}" if kind != "model" else "" for m in faithfulness.MODES}
+            self.log(f"Epoch: {self.current_epoch} | {mode} | faithfulness ({res['clips']} clips) | deletion AUC (prob) "
+                     f"{float(res['deletion']['auc_prob'].mean()):.4f}{versus['deletion']} | "
+                     f"insertion AUC (prob) {float(res['insertion']['auc_prob'].mean()):.4f}{versus['insertion']}")
         return res
 
     def evaluate_robustness(self, mode: str = "val", corruptions: Optional[Sequence[str]] = None, severities: Sequence[int] = (1, 3, 5),
