@@ -1298,6 +1298,49 @@ int pasn_adam_step(const pasn_adam_job* jobs, const pasn_adam_job* jobs_host, in
 int pasn_grad_accumulate(const pasn_accum_job* jobs, const pasn_accum_job* jobs_host, int njobs, const int* block_job, const int* block_chunk,
                          int nblocks, void* stream);
 
+/* Prototype pruning (prune.py): what does the prediction lose when a prototype goes, and which prototypes can go?  The last layer is
+ * linear without a bias, so the logits of "the model without prototype p" follow from the similarities of ONE sweep: an M x P x K problem.
+ *
+ * Inputs: sim [M][P] fp32, fc_w [K][P] fp32 (the last layer), labels [M] int32 (a row whose label is < 0 or >= K_real is SKIPPED by every
+ * tally; its z is still kept), proto_class [P] int32, floor [K_real] int32.  1 <= M <= 2^24, 1 <= P <= PASN_PRUNE_MAX_P, 2 <= K_real <= K
+ * <= 16; every input finite.  The abstention logit, if any (K = K_real + 1), is the last one and takes no part in anything below.
+ *
+ *   base logits     z[n][k]  = the fp64 sum of (double)fc_w[k][j] * (double)sim[n][j] (exact products: 24 + 24 bits), sequential, j ascending
+ *                              from 0.0, no contraction; z is [M][K_real] fp64.  Every prototype is kept at the start.
+ *   ablated logits  za[n][k] = z[n][k] - (double)fc_w[k][p] * (double)sim[n][p] for candidate p: one rounding.
+ *   prediction      the argmax over k < K_real, the LOWEST k on ties.
+ *   margin          z[n][y] - max_{k != y} z[n][k], y the row's label.
+ *   tallies of p    over the rows with a label: wrong (prediction != y), wrong per true class, flips (the ablated prediction differs from the
+ *                   current model's), margin_sum (fp64).  The same for the current model, nothing removed (flips = 0).
+ *   margin_sum      the rows are cut into chunks of pasn_prune_chunk() consecutive rows (skipped rows included in the cut), a chunk is summed
+ *                   from 0.0 in row order, the chunk sums are added from 0.0 in ascending chunk order.  No result depends on the launch
+ *                   geometry or on the number of CUs.
+ *
+ * One elimination round: the candidates are the kept prototypes with proto_class[p] < K_real whose class has MORE kept prototypes than
+ * floor[class]; the one with the smallest (wrong, -margin_sum, index) is taken.  With `accept` != 0 it is removed only if wrong <= wrong_0 +
+ * max_extra_errors and (use_margin != 0) margin_sum >= fl(margin_fraction * margin_sum_0), wrong_0 / margin_sum_0 the tallies of the
+ * model before round 0.  If it is not removed (or there is no candidate) a stop flag is set in device memory: this round and every later one
+ * record removed = -1 and repeat the tallies of the model as it stands.  After a removal z becomes the za of the removed prototype -- the
+ * subtract chain, not a recomputation: a round is one pass over sim.  With |w| <= 2, |sim| <= 1, P <= 256 the chain stays within 1e-9 of the
+ * in-order sum over the kept prototypes (P roundings of at most ulp(2 P) / 2).
+ *
+ * pasn_prune_eliminate: one memset, one launch that builds z and the round-0 tallies (one wave per chunk, lanes over candidates, rows walked
+ * in order), then per round two launches: a one-block select (it adds the chunk sums in order, picks, records) and the pass that applies
+ * the removal to z and tallies the next round's candidates (after the last round it only applies).  rounds = 0: the building launch and the
+ * select launch's summing half.  No block waits for another, nothing is read back.
+ *   table_i [P + 1][2 + K_real] int64: per prototype (row P: the unpruned model) wrong, flips, wrong per class; table_m [P + 1] fp64 margin_sum
+ *   removed [rounds] int32; trace_i [rounds][1 + K_real] int64 (wrong, wrong per class) and trace_m [rounds] fp64 of the model AFTER the round
+ *   kept [P] int32 (1 / 0) at the end; z [M][K_real] fp64 the logits of the model at the end.
+ * `workspace`: pasn_prune_workspace_bytes(M, P, K_real) bytes (0: sizes out of range), 16-byte aligned, no initialisation. */
+#define PASN_PRUNE_MAX_P 256
+#define PASN_PRUNE_MAX_ROWS (1L << 24)
+int pasn_prune_chunk(void);
+size_t pasn_prune_workspace_bytes(long M, int P, int K_real);
+int pasn_prune_eliminate(const float* sim, const float* fc_w, const int32_t* labels, const int32_t* proto_class, const int32_t* floor, long M,
+                         int P, int K, int K_real, int rounds, int accept, int64_t max_extra_errors, int use_margin, double margin_fraction,
+                         double* z, int64_t* table_i, double* table_m, int32_t* removed, int64_t* trace_i, double* trace_m, int32_t* kept,
+                         void* workspace, void* stream);
+
 /*
  * Data-parallel gradient exchange on RCCL (xGMI), without torch.distributed in the data path: ONE in-place sum all-reduce of the
  * flat fp32 gradient bucket per optimizer step.  The reference trains on one GPU and has no collective

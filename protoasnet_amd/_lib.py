@@ -203,6 +203,10 @@ SIGNATURES = {
     "pasn_ood_moments": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int] + [c_void_p] * 6),
     "pasn_ood_mahalanobis": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int] + [c_void_p] * 4),
     "pasn_ood_tally": (c_int, [c_void_p] * 4 + [c_long, c_int] + [c_void_p] * 3),
+    # ---- prototype pruning: ablation tallies and greedy elimination (prune.py)
+    "pasn_prune_chunk": (c_int, []),
+    "pasn_prune_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "pasn_prune_eliminate": (c_int, [c_void_p] * 5 + [c_long, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_double] + [c_void_p] * 9),
     # ---- explanation faithfulness: deletion / insertion curves (faithfulness.py)
     "pasn_perturb_steps_workspace_bytes": (c_size_t, [c_long, c_long, c_int]),
     "pasn_perturb_steps": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),

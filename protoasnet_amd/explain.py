@@ -87,6 +87,9 @@ def _dimensions(model, abstain_class: bool):
     P, K = int(model.num_prototypes), int(model.num_classes)
     if P % K:
         raise ValueError(f"{P} prototypes do not split into {K} class blocks")
+    from .prune import require_balanced
+
+    require_balanced(model, "the explanation (it ranks within class blocks)")  # (7, 10, 10 prototypes also divide by 3)
     return P, K, P // K, K - 1 if abstain_class else K
 
 

@@ -99,10 +99,37 @@ def _zero(t):
     return torch.tensor(0, device=t.device)
 
 
-def _per_class_extreme(scores, num_classes, largest):
-    """(N, P) scores -> (N, classes): best prototype score of every class (prototypes are laid out class-major)."""
+def _per_class_extreme(scores, num_classes, largest, proto_class=None):
+    """(N, P) scores -> (N, classes): best prototype score of every class.  ``proto_class`` None: the prototypes are laid out class-major
+    in equal blocks (the model as built).  Else (P,) the class of every prototype -- a pruned model whose classes own different numbers
+    of prototypes --: the extreme over each class's own prototypes; a class that owns none contributes 0."""
+    if proto_class is not None:
+        own = _class_mask(proto_class, num_classes, scores.device)  # (classes, P)
+        fill = float("-inf") if largest else float("inf")
+        spread = scores[:, None, :].masked_fill(~own[None], fill)
+        best = spread.amax(dim=2) if largest else spread.amin(dim=2)
+        return torch.where(own.any(dim=1)[None], best, torch.zeros_like(best))
+    if scores.shape[1] % num_classes:
+        from .prune import check_class_blocks
+
+        check_class_blocks(scores.shape[1], num_classes, "the cluster / separation cost")
     grouped = scores.reshape(scores.shape[0], num_classes, -1)
     return grouped.max(dim=2)[0] if largest else grouped.min(dim=2)[0]
+
+
+def _class_mask(proto_class, num_classes, device):
+    if proto_class.shape[0] == 0 or int(proto_class.max()) >= num_classes or int(proto_class.min()) < 0:
+        raise ValueError(f"proto_class must hold classes in [0, {num_classes})")
+    return proto_class.to(device)[None, :] == torch.arange(num_classes, device=device)[:, None]
+
+
+def _class_index(loss, P):
+    """``loss.proto_class`` (None: equal class-major blocks), checked against the P prototypes the cost is handed."""
+    pc = loss.proto_class
+    if pc is not None and pc.shape[0] != P:
+        raise ValueError(f"unbalanced prototype blocks: the criterion groups {pc.shape[0]} prototypes by class, the model has {P} "
+                         "(rebuild the criterion after pruning)")
+    return pc
 
 
 def _batch_reduce(per_class, reduction):
@@ -123,6 +150,8 @@ class CeLoss(object):
 
 
 class ClusterPatch(object):
+    proto_class = None  # (P,) class of every prototype when the blocks are unequal (DPTrainer.get_criterion sets it)
+
     """loss.py:37-65 -- ProtoPNet cluster cost on min_distances (N, P)."""
 
     def __init__(self, loss_weight, num_classes=4, reduction="mean"):
@@ -132,10 +161,12 @@ class ClusterPatch(object):
         if self.loss_weight == 0:
             return _zero(target)
         own = torch.nn.functional.one_hot(target, num_classes=self.num_classes)
-        return self.loss_weight * _batch_reduce(_per_class_extreme(min_distances, self.num_classes, largest=False) * own, self.reduction)
+        return self.loss_weight * _batch_reduce(_per_class_extreme(min_distances, self.num_classes, False, _class_index(self, min_distances.shape[1])) * own, self.reduction)
 
 
 class SeparationPatch(object):
+    proto_class = None  # (P,) class of every prototype when the blocks are unequal (DPTrainer.get_criterion sets it)
+
     """loss.py:68-95 -- ProtoPNet separation cost."""
 
     def __init__(self, loss_weight, num_classes=4, reduction="mean"):
@@ -145,10 +176,12 @@ class SeparationPatch(object):
         if self.loss_weight == 0:
             return _zero(target)
         other = 1 - torch.nn.functional.one_hot(target, num_classes=self.num_classes)
-        return -self.loss_weight * _batch_reduce(_per_class_extreme(min_distances, self.num_classes, largest=False) * other, self.reduction)
+        return -self.loss_weight * _batch_reduce(_per_class_extreme(min_distances, self.num_classes, False, _class_index(self, min_distances.shape[1])) * other, self.reduction)
 
 
 class ClusterRoiFeat(object):
+    proto_class = None  # (P,) class of every prototype when the blocks are unequal (DPTrainer.get_criterion sets it)
+
     """loss.py:98-138 -- XProtoNet cluster cost on similarities (N, P)."""
 
     def __init__(self, loss_weight, num_classes=4, reduction="sum"):
@@ -158,10 +191,12 @@ class ClusterRoiFeat(object):
         if self.loss_weight == 0:
             return _zero(target)
         own = torch.nn.functional.one_hot(target, num_classes=self.num_classes)
-        return -self.loss_weight * _batch_reduce(_per_class_extreme(similarities, self.num_classes, largest=True) * own, self.reduction)
+        return -self.loss_weight * _batch_reduce(_per_class_extreme(similarities, self.num_classes, True, _class_index(self, similarities.shape[1])) * own, self.reduction)
 
 
 class SeparationRoiFeat(object):
+    proto_class = None  # (P,) class of every prototype when the blocks are unequal (DPTrainer.get_criterion sets it)
+
     """loss.py:141-183 -- XProtoNet separation cost; the abstain class (last) is never penalised when ``abstain_class``."""
 
     def __init__(self, loss_weight, num_classes=4, reduction="sum", abstain_class=True):
@@ -174,10 +209,12 @@ class SeparationRoiFeat(object):
         if self.abstain_class:
             own = own.clone()
             own[:, -1] = 1
-        return self.loss_weight * _batch_reduce(_per_class_extreme(similarities, self.num_classes, largest=True) * (1 - own), self.reduction)
+        return self.loss_weight * _batch_reduce(_per_class_extreme(similarities, self.num_classes, True, _class_index(self, similarities.shape[1])) * (1 - own), self.reduction)
 
 
 class OrthogonalityLoss(object):
+    proto_class = None  # as in the cluster / separation costs
+
     """loss.py:186-229 -- sum of the pairwise cosine similarities of the prototypes (upper triangle), per class or over all."""
 
     def __init__(self, loss_weight, num_classes=4, mode="per_class"):
@@ -189,7 +226,15 @@ class OrthogonalityLoss(object):
         if self.loss_weight == 0:
             return _zero(prototype_vectors)
         p = prototype_vectors.reshape(prototype_vectors.shape[0], prototype_vectors.shape[1])
+        if self.mode == "per_class" and self.proto_class is not None:  # unequal blocks: the pairs of a class, picked by a mask
+            c = _class_index(self, p.shape[0]).to(p.device)
+            sim = torch.nn.functional.cosine_similarity(p.unsqueeze(1), p.unsqueeze(0), dim=2)
+            return self.loss_weight * (torch.triu(sim, diagonal=1) * (c[:, None] == c[None, :])).sum()
         if self.mode == "per_class":
+            if p.shape[0] % self.num_classes:
+                from .prune import check_class_blocks
+
+                check_class_blocks(p.shape[0], self.num_classes, "the per-class orthogonality loss")
             p = p.reshape(self.num_classes, -1, p.shape[1])
             sim = torch.nn.functional.cosine_similarity(p.unsqueeze(1), p.unsqueeze(2), dim=3)
         else:
@@ -342,6 +387,9 @@ class FusedCriterion(object):
     def from_config(cls, criterion: dict, model, abstain_class: bool) -> "FusedCriterion":
         """From a ``train.criterion`` block of the reference's XProto configs, as ``XProtoNet_Base.get_criterion`` reads it (:54-81)."""
         cfg, K = criterion, model.num_classes
+        from .prune import require_balanced
+
+        require_balanced(model, "the one-launch criterion (it indexes equal class blocks)")
         ce = CeLossAbstain(**cfg["CeLossAbstain"]) if abstain_class else CeLoss(**cfg["CeLoss"])
         return cls(ce, ClusterRoiFeat(num_classes=K, **cfg["ClusterRoiFeat"]),
                    SeparationRoiFeat(num_classes=K, **cfg["SeparationRoiFeat"], abstain_class=bool(abstain_class)),

@@ -299,6 +299,11 @@ class PPNet(nn.Module):
         (Video_XProtoNet_e2e.py:118-141; ``compute_occurence_map`` is called with gradients by loss.py:302)."""
         from .train import TrainRunner
 
+        if self.__dict__.get("_balanced_at") != self.num_prototypes:  # (once per shape: the runner and the losses reshape by class)
+            from . import prune
+
+            prune.require_balanced(self, "the training pass")
+            self._balanced_at = self.num_prototypes
         x = self._train_input(x)
         if "_train_runners" not in self.__dict__:
             self._train_runners = PlanCache(self._train_signature)
@@ -326,6 +331,7 @@ class PPNet(nn.Module):
         return conv_output, dist.view(n, self.num_prototypes, h, w)
 
     def prune_prototypes(self, prototypes_to_prune) -> None:
+        before = int(self.num_prototypes)
         keep = sorted(set(range(self.num_prototypes)) - set(prototypes_to_prune))
         self.prototype_vectors = nn.Parameter(self.prototype_vectors.data[keep, ...], requires_grad=True)
         self.prototype_shape = list(self.prototype_vectors.size())
@@ -335,6 +341,9 @@ class PPNet(nn.Module):
         self.last_layer.weight.data = self.last_layer.weight.data[:, keep]
         self.ones = nn.Parameter(self.ones.data[keep, ...], requires_grad=False)
         self.prototype_class_identity = self.prototype_class_identity[keep, :]
+        from . import prune
+
+        prune.track(self, keep, before)  # (what a checkpoint needs to rebuild this shape)
 
     def __repr__(self):
         return (
@@ -398,6 +407,17 @@ class _XProtoHeadMixin:
         )
         occ = occ.view((N, P, 1) + tuple(feat.shape[2:]))
         return logits, sim, occ, featx
+
+    def prune_prototypes(self, prototypes_to_prune) -> None:
+        """``PPNet.prune_prototypes`` plus what head B adds: the occurrence module's last conv has one output channel per prototype (left
+        at the old width the fused head is handed inconsistent shapes), and the last layer's weight is made contiguous again."""
+        from . import prune
+
+        prototypes_to_prune = [int(i) for i in prototypes_to_prune]
+        keep = sorted(set(range(self.num_prototypes)) - set(prototypes_to_prune))
+        PPNet.prune_prototypes(self, prototypes_to_prune)
+        self.last_layer.weight.data = self.last_layer.weight.data.contiguous()
+        prune.slice_occurrence(self, keep)
 
     def forward(self, x: torch.Tensor):
         logits, sim, occ, _ = self._xproto(x, 0)

@@ -183,9 +183,19 @@ class DPTrainer:
         self.Lnorm_occurrence = losses.L_norm(**cfg["Lnorm_occurrence"])
         self.Trans_occurrence = losses.TransformLoss(**cfg["trans_occurrence"])
         self.Lnorm_fc = losses.L_norm(**cfg["Lnorm_FC"], mask=1 - torch.t(self.model.prototype_class_identity))
+        # a pruned model whose classes own different numbers of prototypes: the class-grouped costs group by the class identity, not by
+        # reshaping (N, P) to (N, K, P / K), so that an eval epoch reports the loss of the model as it stands (training refuses it)
+        from . import prune
+
+        balanced = prune.is_balanced(self.model)
+        if not balanced:
+            cls = prune.proto_classes(self.model)
+            self.Cluster.proto_class = self.Separation.proto_class = self.Orthogonality.proto_class = cls
         # train.fused_loss (not a key of the reference's configs; default off): the same seven objects evaluated by one library call
         self.fused = None
         if self.train_config.get("fused_loss", False):
+            if not balanced:
+                prune.require_balanced(self.model, "train.fused_loss (the one-launch criterion indexes equal class blocks)")
             self.fused = losses.FusedCriterion(self.CeLoss, self.Cluster, self.Separation, self.Orthogonality, self.Lnorm_occurrence,
                                                self.Trans_occurrence, self.Lnorm_fc)
 
@@ -228,8 +238,14 @@ class DPTrainer:
 
     # ---- base.py:143-169, XProtoNet_e2e.py:84-107 ------------------------------------------------------------------------------
     def get_state(self) -> dict:
-        return {"epoch": self.current_epoch, "iteration": self.current_iteration, "state_dict": self.model.state_dict(),
-                "optimizer": self.optimizer.state_dict()}
+        state = {"epoch": self.current_epoch, "iteration": self.current_iteration, "state_dict": self.model.state_dict(),
+                 "optimizer": self.optimizer.state_dict()}
+        from . import prune
+
+        pruned = prune.state(self.model)
+        if pruned:  # (a model that was never pruned writes the keys it always wrote)
+            state["pruned_prototypes"] = pruned  # indices into the model as built: load_checkpoint removes them before load_state_dict
+        return state
 
     def save_checkpoint(self, is_best: bool = False) -> None:
         if not self.train_config.get("save", True):
@@ -252,6 +268,12 @@ class DPTrainer:
             return False
         ck = torch.load(file_name, map_location=self.device)
         self.current_epoch, self.current_iteration = ck["epoch"], ck["iteration"]
+        if ck.get("pruned_prototypes"):
+            from . import prune
+
+            if prune.state(self.model) != list(ck["pruned_prototypes"]):
+                prune.restore(self.model, ck["pruned_prototypes"])
+                self._rebuild_after_surgery()
         self.model.load_state_dict(ck["state_dict"])
         self.optimizer.load_state_dict(ck["optimizer"])
         self.log(f"Checkpoint loaded successfully from '{file_name}' at (epoch {ck['epoch']}) at (iteration {ck['iteration']})")
@@ -579,6 +601,58 @@ class DPTrainer:
                 yield batches()
         finally:
             self.model.train(was_training)
+
+    def _rebuild_after_surgery(self) -> None:
+        """Prototype surgery replaced parameters: the criterion's class mask and grouping, the optimizer and the scheduler are built again
+        on the model as it stands.  BOTH start afresh: the optimizer's moments are dropped and the learning-rate schedule restarts from its
+        initial state (a ReduceLROnPlateau forgets its best value and its reductions), so a prune in the middle of training resets the
+        schedule; prune before training or between schedules."""
+        self.get_criterion()
+        self.get_optimizer()
+        self.scheduler = self.get_lr_scheduler()
+        self.params = [p for g in self.optimizer.param_groups for p in g["params"]]
+
+    def prune_prototypes(self, mode: str = "val", apply: bool = False, **kw):
+        """Prototype pruning on ``data_loaders[mode]`` (``protoasnet_amd.prune``): ONE forward-only sweep that keeps the similarities and
+        the labels on the device, then ``prune.eliminate(sim, last layer, labels, K_real, class of each prototype, **kw)`` (``budget``,
+        ``keep_per_class``, ``min_per_class``, ``max_extra_errors``, ``margin_fraction``).  Logs the trace and returns the
+        ``PruneResult``.  ``apply=True`` also edits the model (``prune.apply``; the criterion, optimizer and scheduler are rebuilt) and
+        returns ``(result, evaluate(mode) before, evaluate(mode) after)``.  With ``world_size > 1`` the rows of every rank are gathered
+        to every rank, rank-major, and every rank computes the same result (a collective: every rank calls it)."""
+        from . import prune, sweep
+
+        sims, labels = [], []
+        with self._forward_only(mode) as batches:
+            for sample, x in batches:
+                out = self.model(x)  # head B: (logits, similarities, maps); head A: (logits, min distances)
+                sims.append((out[1] if len(out) == 3 else self.model.distance_2_similarity(out[1])).float())
+                labels.append(sample["target_AS"].to(self.device, non_blocking=True).to(torch.int32))
+        if not sims:
+            raise ValueError("no rows: the loader is empty")
+        sim, lab = torch.cat(sims), torch.cat(labels)
+        if self.world_size > 1:
+            n = torch.tensor([sim.shape[0]], dtype=torch.int64, device=self.device)
+            most = max(int(t[0]) for (t,) in sweep.gather_ranks([n], self.device))
+            pad = most - sim.shape[0]  # all_gather takes equal shapes: pad with rows that carry no label
+            sim = torch.cat([sim, sim.new_zeros(pad, sim.shape[1])])
+            lab = torch.cat([lab, lab.new_full((pad,), -1)])
+            parts = sweep.gather_ranks([sim, lab], self.device)
+            sim, lab = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        cls = prune.proto_classes(self.model).to(self.device)
+        res = prune.eliminate(sim, self.model.last_layer.weight.detach().float(), lab, self.num_real_classes, cls, **kw)
+        out = res.read()
+        t = out["table"]
+        self.log(f"Epoch: {self.current_epoch} | {mode} | prune | rows {sim.shape[0]} | wrong {t['wrong_0']} | margin sum {t['margin_sum_0']:.6f}")
+        for r, step in enumerate(out["trace"]):
+            self.log(f"Epoch: {self.current_epoch} | {mode} | prune round {r} | removed {step['removed']} | wrong {step['wrong']} | "
+                     f"margin sum {step['margin_sum']:.6f}")
+        if not apply:
+            return res
+        before = self.evaluate(mode)
+        if out["order"]:
+            prune.apply(self.model, out["order"])
+            self._rebuild_after_surgery()
+        return res, before, self.evaluate(mode)
 
     def fit_temperature(self, mode: str = "val") -> Dict[str, object]:
         """Temperature scaling fitted on the clips of ``data_loaders[mode]`` (``calibration.fit_temperature``; the sweep of
