@@ -896,6 +896,84 @@ int pasn_conformal_tally_words(int K_real);
 int pasn_conformal_sets(const float* scores, const float* qhat, const int32_t* labels, const float* u, long M, int K_real, int A,
                         int mondrian, uint16_t* masks, int64_t* tallies, void* stream);
 
+/* Ordinal evaluation (ordinal.py): the statistics that use the ORDER of the classes.  Class index = grade (the reference's class_labels
+ * are listed in ascending severity: No AS < Early AS < Significant AS).  The reference has no code for it; these definitions are the
+ * specification, tests/ordinal_cases.py their restatement.  Every call is stream-ordered: no host synchronisation, no block waiting on
+ * another, no floating-point atomics; two calls are bitwise equal.  The file is compiled so that every fp64 operation is rounded on its
+ * own (fp contract(off)).
+ *
+ * Rows.  probs [M][K_real] fp32, labels [M] int32.  A row with label < 0 or label >= K_real is padding and never enters.  A row's
+ * prediction is its first largest probability.  NaN probabilities: unspecified, as in pasn_bootstrap_metrics.  2 <= K_real <= 16 and
+ * 1 <= M <= 2^20; anything else, or a NULL required pointer, returns PASN_ERR_ARG before any launch (the size query returns 0).
+ *
+ * Agreement.  From a confusion matrix cm [true][pred] int64 with row sums r_i, column sums c_j and total n.  All sums are int64 and each
+ * result is one fp64 expression of them, so a result is a function of the matrix alone (bitwise):
+ *   mae             (double)(sum |i - j| cm_ij) / (double)n
+ *   within_one      (double)(sum_{|i - j| <= 1} cm_ij) / (double)n
+ *   under           (double)(sum_{j < i} cm_ij) / (double)n         predicted grade below the true one
+ *   over            (double)(sum_{j > i} cm_ij) / (double)n
+ *   kappa_linear, kappa_quadratic   1.0 - ((double)n * (double)A) / (double)E, with A = sum w_ij cm_ij, E = sum w_ij r_i c_j, and
+ *                   w_ij = |i - j| (linear) or (i - j)^2 (quadratic) as integers
+ * NaN for a kappa whose E is 0 (all weight in one row class and the same column class); all six NaN when n == 0.  E stays inside int64
+ * for n < 2^27 (225 n^2 < 2^63); above that the kappas are unspecified.
+ * pasn_ordinal_agreement: cm [R][K_real][K_real] int64 -> out [R][6] fp64 in the order above, one launch (a thread per matrix),
+ * 1 <= R <= 65 537.  Given pasn_bootstrap_metrics' cm it yields all replicates and the point estimate at once.
+ * pasn_ordinal_confusion: cm [K_real][K_real] int64 of the rows (one memset, one launch; integer atomics).
+ *
+ * Cuts.  For c = 1 .. K_real - 1 (output index c - 1) the positive class is label >= c, the score is
+ *   s_c = p[c] + p[c + 1] + ... + p[K_real - 1]   in fp32, added in that order (a sum of its own per cut, from p[c] upwards),
+ * and the decision at threshold theta is "positive iff s_c >= theta".  pasn_ordinal_cut_scores writes scores [K_real - 1][M] fp32.
+ * Scores compare as floats do, -0 equal to +0; a reported theta that is zero is +0.
+ *
+ * Weights.  w_i = the row's number of copies: 1 for the sample (output row B), counts[b][unit(i)] for replicate b (output row b < B).
+ * Draws, units and the groups CSR are exactly those of pasn_bootstrap_counts / pasn_bootstrap_metrics, so replicate b of this call and of
+ * pasn_bootstrap_metrics with the same (seed, G) is the same multiset of rows; a row that no group lists never enters.  The expanded
+ * rows of a replicate must number less than 2^31.
+ *
+ * Per output row and cut:
+ *   pn [2] int64    P, N: the weight of the positives and of the negatives
+ *   u2 int64        U2 = sum over i positive, j negative of w_i w_j (2 [s_j < s_i] + [s_j == s_i]), as in pasn_roc_auc_ovr with weights
+ *   stats [2] fp64  auc = (double)U2 / (2.0 * (double)P * (double)N);
+ *                   ap = sum over the distinct score values v that carry positive weight of ((double)tp_v / (double)P) *
+ *                   ((double)TP_v / (double)(TP_v + FP_v)), tp_v the positive weight at exactly v, TP_v and FP_v the positive and
+ *                   negative weight at scores >= v; values without positive weight add nothing.  Summation order: the positions of the
+ *                   ascending order are dealt out in chunks of 2048, eight consecutive positions per thread; a term belongs to the
+ *                   position behind its value's last row; each of the 256 threads adds its terms in position order, chunk after chunk,
+ *                   and the threads are added in the tree of the other evaluation kernels (a butterfly within each wave of 64, then
+ *                   (w0 + w1) + (w2 + w3)).  A restatement that sums in another order agrees within M 2^-50 (a term is at most 1 and
+ *                   carries three roundings; at most M terms and M adds of partial sums <= 1 on each side).
+ *   Candidate thresholds: the distinct scores of the rows with w > 0, and +inf (nobody positive: TP = FP = 0).
+ *   Operating points, T = n_spec + n_sens + 1 per cut, in this order:
+ *     specificity tau   the SMALLEST candidate theta with (double)(N - FP_theta) / (double)N >= tau  (+inf always qualifies)
+ *     sensitivity tau   the LARGEST candidate theta with (double)TP_theta / (double)P >= tau         (the lowest candidate always does)
+ *     Youden            the candidate maximising TP_theta N - FP_theta P as int64, ties to the larger theta (+inf scores 0)
+ *   op_theta [T] fp32 and op_tally [T][2] int64 = TP_theta, FP_theta.
+ *   fix_tally [F][2] int64 = TP_theta, FP_theta for the caller's thresholds fixed [K_real - 1][F] fp32 (device memory; a NaN threshold
+ *   admits nobody).  This is how a fit from another split is applied, and how a decision curve is read.
+ * A cut with P == 0 or N == 0 has auc, ap and every op_theta NaN and its op_tally 0; pn, u2 (= 0) and fix_tally are written as usual,
+ * and no other cut or output row is disturbed.
+ * Sensitivity TP / P, specificity (N - FP) / N, PPV, NPV and net benefit TP / n - (FP / n) pt / (1 - pt) (treat-all: P / n - (N / n)
+ * pt / (1 - pt)) are host arithmetic on these tallies (ordinal.py).
+ *
+ * pasn_ordinal_screen: groups as in pasn_bootstrap_metrics (both NULL: every row its own group, G == M); specificities / sensitivities
+ * are HOST arrays of n_spec / n_sens doubles, each in (0, 1), 0 <= n <= PASN_ORDINAL_MAX_TARGETS each; 0 <= n_fixed <=
+ * PASN_ORDINAL_MAX_FIXED; 0 <= B <= 65 536 (B == 0: the point estimate only), 1 <= G <= M.  Outputs are [B + 1][K_real - 1][...] as
+ * above.  Up to four memsets and six launches whatever B is: the order of each cut's scores (a rank by counting, order_key.h) is shared
+ * by all replicates; a block owns a replicate, the unit counts in LDS for G <= PASN_BOOTSTRAP_LDS_MAX_G and in a slice of the workspace
+ * above that (the blocks looping over the replicates), and settles U2, ap, every operating point and every fixed tally of a cut in ONE
+ * pass over its sorted rows (packed wave scans).  `workspace`: pasn_ordinal_workspace_bytes(M, G, K_real, B) bytes, 16-byte aligned, no
+ * initialisation. */
+#define PASN_ORDINAL_MAX_TARGETS 8
+#define PASN_ORDINAL_MAX_FIXED 32
+int pasn_ordinal_agreement(const int64_t* cm, long R, int K_real, double* out, void* stream);
+int pasn_ordinal_confusion(const float* probs, const int32_t* labels, long M, int K_real, int64_t* cm, void* stream);
+int pasn_ordinal_cut_scores(const float* probs, long M, int K_real, float* scores, void* stream);
+size_t pasn_ordinal_workspace_bytes(long M, long G, int K_real, int B);
+int pasn_ordinal_screen(const float* probs, const int32_t* labels, const int64_t* group_offsets, const int32_t* group_rows, long M, long G,
+                        int K_real, int B, uint64_t seed, const double* specificities, int n_spec, const double* sensitivities, int n_sens,
+                        const float* fixed, int n_fixed, int64_t* pn, int64_t* u2, double* stats, float* op_theta, int64_t* op_tally,
+                        int64_t* fix_tally, void* workspace, void* stream);
+
 /* Out-of-distribution detection (ood.py): does a row look like anything the model was trained on?  A HIGHER score means MORE
  * out-of-distribution.  The reference has no code for it; these definitions are the specification.  Every call is stream-ordered: no
  * host synchronisation, no block waiting on another, no floating-point atomics.  The file is compiled without contraction: "rounded on

@@ -9,11 +9,11 @@ See DESIGN.md for the path, the boundary and the kernels; INTEGRATION.md for the
 from . import synth  # noqa: F401
 from .build import build_extension, lib_path  # noqa: F401
 
-__all__ = ["model_builder", "nets", "backbones", "push", "explain", "global_explain", "metrics", "selective", "bootstrap", "calibration", "conformal", "ood", "prune", "faithfulness", "saliency", "robustness", "synth", "build_extension", "lib_path"]
+__all__ = ["model_builder", "nets", "backbones", "push", "explain", "global_explain", "metrics", "selective", "bootstrap", "calibration", "conformal", "ordinal", "ood", "prune", "faithfulness", "saliency", "robustness", "synth", "build_extension", "lib_path"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need the built library
-    if name in ("model_builder", "nets", "backbones", "push", "explain", "global_explain", "metrics", "selective", "bootstrap", "calibration", "conformal", "ood", "prune", "faithfulness", "saliency", "robustness", "plan", "receptive_field", "_lib"):
+    if name in ("model_builder", "nets", "backbones", "push", "explain", "global_explain", "metrics", "selective", "bootstrap", "calibration", "conformal", "ordinal", "ood", "prune", "faithfulness", "saliency", "robustness", "plan", "receptive_field", "_lib"):
         import importlib
 
         return importlib.import_module(f"{__name__}.{name}")

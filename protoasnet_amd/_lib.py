@@ -193,6 +193,13 @@ SIGNATURES = {
     "pasn_conformal_quantiles": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, POINTER(c_double)] + [c_void_p] * 5),
     "pasn_conformal_tally_words": (c_int, [c_int]),
     "pasn_conformal_sets": (c_int, [c_void_p] * 4 + [c_long, c_int, c_int, c_int] + [c_void_p] * 3),
+    # ---- ordinal evaluation: agreement, cuts and operating points (ordinal.py)
+    "pasn_ordinal_agreement": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    "pasn_ordinal_confusion": (c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    "pasn_ordinal_cut_scores": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    "pasn_ordinal_workspace_bytes": (c_size_t, [c_long, c_long, c_int, c_int]),
+    "pasn_ordinal_screen": (c_int, [c_void_p] * 4 + [c_long, c_long, c_int, c_int, c_uint64, POINTER(c_double), c_int, POINTER(c_double), c_int,
+                                    c_void_p, c_int] + [c_void_p] * 8),
     # ---- out-of-distribution detection (ood.py)
     "pasn_ood_head_scores": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "pasn_ood_knn_workspace_bytes": (c_size_t, [c_long, c_long, c_int, c_int]),

@@ -23,65 +23,17 @@
 // every copy of a row, each thread its positions in order, the threads in the tree of block_sum_fixed.  One barrier per chunk (wave
 // summaries in a double-buffered LDS table).  Thread 0 turns the confusion matrix into accuracy, balanced accuracy and mean F1 with the
 // ClassTally of eval_common.h, the arithmetic of rc_curve_kernel (selective.hip).
+#include "boot_draw.h"
 #include "common.h"
 #include "eval_common.h"
-#include "philox.h"
 
 namespace pasn {
 
-constexpr int BOOT_LDS_MAX_G = PASN_BOOTSTRAP_LDS_MAX_G;  // uint16 counts: 32 KiB of LDS, four blocks per CU
-constexpr int BOOT_NT = 256, BOOT_E = 8, BOOT_CHUNK = BOOT_NT * BOOT_E;
-constexpr size_t BOOT_SLOT_BYTES = 256ull << 20;  // the count slices of the global path together
-constexpr int BOOT_MAX_SLOTS = 512;
+constexpr int BOOT_E = 8, BOOT_CHUNK = BOOT_NT * BOOT_E;
 constexpr uint32_t BOOT_EMPTY = 0xFFFFFFFFu, BOOT_TIE = 1u << 31, BOOT_POS = 1u << 30, BOOT_NAN = 1u << 29, BOOT_GID = 0xFFFFFu;
 constexpr ClassCell BOOT_CELL = {20, 24};  // info = group | label << 20 | prediction << 24
 
-// ---- draws -------------------------------------------------------------------------------------------------------------------------------
-// counts of replicate b as uint16 pairs in s_cnt[(G + 1) / 2]; ones: the point estimate.  Ends with a barrier.
-__device__ __forceinline__ void boot_draw_lds(uint32_t* s_cnt, int G, uint32_t b, uint32_t k0, uint32_t k1, bool ones) {
-    const int tid = threadIdx.x;
-    for (int w = tid; w < (G + 1) / 2; w += BOOT_NT) s_cnt[w] = ones ? 0x00010001u : 0u;
-    __syncthreads();
-    if (!ones)
-        for (int q = tid; q < (G + 3) / 4; q += BOOT_NT) {
-            uint32_t r[4];
-            philox4x32_10((uint32_t)q, b, 0u, 0u, k0, k1, r);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * q + j < G) {
-                    const uint32_t g = philox_unit(r[j], (uint32_t)G);  // a count never exceeds G < 2^16: no carry into the neighbour
-                    atomicAdd(&s_cnt[g >> 1], 1u << (16 * (g & 1)));
-                }
-        }
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t boot_count_lds(const uint32_t* s_cnt, uint32_t g) { return (s_cnt[g >> 1] >> (16 * (g & 1))) & 0xFFFFu; }
-
-// the same into an int32 slice of global memory that this block owns.  The adds happen in L2; boot_count_global reads there too.
-__device__ __forceinline__ void boot_draw_global(int32_t* cg, long G, uint32_t b, uint32_t k0, uint32_t k1, bool ones) {
-    const int tid = threadIdx.x;
-    for (long g = tid; g < G; g += BOOT_NT) cg[g] = ones ? 1 : 0;
-    __threadfence();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores have reached L2 before another wave's atomic finds the word
-    __syncthreads();
-    if (!ones)
-        for (long q = tid; q < (G + 3) / 4; q += BOOT_NT) {
-            uint32_t r[4];
-            philox4x32_10((uint32_t)q, b, 0u, 0u, k0, k1, r);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * q + j < G) atomicAdd(&cg[philox_unit(r[j], (uint32_t)G)], 1);
-        }
-    __threadfence();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t boot_count_global(const int32_t* cg, uint32_t g) {
-    return (uint32_t)__hip_atomic_load(cg + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
+// ---- draws (the per-block draws themselves: boot_draw.h) -------------------------------------------------------------------------------
 __global__ __launch_bounds__(BOOT_NT) void boot_counts_lds_kernel(int32_t* __restrict__ counts, int G, int B, uint32_t k0, uint32_t k1, int b0) {
     extern __shared__ uint32_t boot_lds[];
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
@@ -369,12 +321,6 @@ struct BootWorkspace {
     int nslots;
     size_t bytes;
 };
-
-static int boot_slots(long G, int B) {
-    if (G <= BOOT_LDS_MAX_G) return 0;
-    const long fit = std::max(1L, (long)(BOOT_SLOT_BYTES / ((size_t)G * sizeof(int32_t))));
-    return (int)std::min({(long)B + 1, (long)BOOT_MAX_SLOTS, fit});
-}
 
 static BootWorkspace boot_workspace(void* ws, long M, long G, int K, int B) {
     BootWorkspace w;

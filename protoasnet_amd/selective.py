@@ -249,7 +249,7 @@ class SelectiveEvaluator:
         self.keys += keys
 
     def finish(self, coverages=DEFAULT_COVERAGES, level: str = "clip", bootstrap: int = 0, seed: int = 0, confidence: float = 0.95,
-               unit: str = "cine", calibration: int = 0, temperature=None, conformal=None,
+               unit: str = "cine", calibration: int = 0, temperature=None, ordinal=None, ordinal_net_benefit_at=(), conformal=None,
                conformal_mondrian: bool = False) -> Dict[str, object]:
         """``bootstrap=B > 0`` adds ``res["ci"]``: ``bootstrap.intervals`` of ``B`` grouped replicates (``seed``, ``confidence``) of the
         rows the level scores -- at cine level the cine predictions, the unit the cine; at clip level the clips, the unit the cine
@@ -268,7 +268,17 @@ class SelectiveEvaluator:
         levels}``, ``levels`` one ``ConformalSets.summary()`` dict per alpha of ``conformal.predict_sets`` on the rows the level scores
         (the clips; at cine level ``p_conf.float()`` with the cine's label and ``u_mean``), after ``temperature`` if one is given;
         ``conformal_mondrian`` takes each class's own threshold.  At cine level every entry of ``res["cines"]`` gains
-        ``"set@<alpha>"``, the list of class indices.  The same single read; ``conformal=None`` is the call without it."""
+        ``"set@<alpha>"``, the list of class indices.  The same single read; ``conformal=None`` is the call without it.
+
+        ``ordinal`` (``True``, or an ``ordinal.OperatingFit`` from another split) adds ``res["ordinal"]``: ``{"agreement": {mae,
+        within_one, under, over, kappa_linear, kappa_quadratic}, "cuts": [...]}``, ``cuts`` being ``ordinal.Screening.unpack``'s list
+        (per cut ``grade >= c``: ``P``, ``N``, ``prevalence``, ``auc``, ``ap`` and the operating points with their sensitivity,
+        specificity, PPV, NPV and threshold) of the rows the level scores (the clips; at cine level ``p_conf.float()`` with the cine's
+        label), after ``temperature`` if one is given.  ``True`` reports the operating points at specificity 0.9, sensitivity 0.9 and
+        Youden's; a fit reports those of its own targets and, under ``"fitted"``, its thresholds applied unchanged;
+        ``ordinal_net_benefit_at`` (threshold probabilities) adds ``"net_benefit"``.  With ``bootstrap=B`` the six agreement
+        statistics and each cut's ``auc``, ``ap`` and every reported sensitivity / specificity join ``res["ci"]``, on the same
+        resamples.  The same single read; ``ordinal=None`` is the call without it."""
         if level not in ("clip", "cine"):
             raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
         if unit not in ("clip", "cine"):
@@ -300,12 +310,23 @@ class SelectiveEvaluator:
                 raise ValueError(f"conformal must be a ConformalFit (conformal.calibrate) or None, got {conformal!r}")
             if not isinstance(conformal_mondrian, (bool, np.bool_)):
                 raise ValueError(f"conformal_mondrian must be a bool, got {conformal_mondrian!r}")
+        ordm = None
+        if ordinal is not None:
+            from . import ordinal as ordm
+
+            if ordinal is not True and not isinstance(ordinal, ordm.OperatingFit):
+                raise ValueError(f"ordinal must be True, an OperatingFit (ordinal.fit_operating_points) or None, got {ordinal!r}")
+            ord_fit = None if ordinal is True else ordinal
+            ord_spec, ord_sens = ((0.9,), (0.9,)) if ord_fit is None else (ord_fit.specificities, ord_fit.sensitivities)
+            ord_spec, ord_sens, ord_pts = ordm._check_screen_args(ord_spec, ord_sens, int(bootstrap), 0, ord_fit, ordinal_net_benefit_at)
         cs = _check_coverages(coverages)
         ev, K = self.ev, self.ev.K_real
         if ev.rows == 0:
             raise ValueError("no rows: call update() first")
         if conf is not None and conformal.K != K:
             raise ValueError(f"the conformal fit was calibrated on {conformal.K} classes, the evaluator scores {K}")
+        if ordm is not None and ord_fit is not None and ord_fit.K != K:
+            raise ValueError(f"the operating points were fitted on {ord_fit.K} classes, the evaluator scores {K}")
         probs, labels = ev.probs[: ev.rows], ev.labels[: ev.rows]
         if temperature is None:
             u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
@@ -316,21 +337,30 @@ class SelectiveEvaluator:
             u = uncertainty(ev.logits[: ev.rows], self.abstain, self.score, self.ab_logitpath)
         if level == "clip":
             packed = risk_coverage(probs, labels, u).packed(cs)
-            if boot is None and not n_bins and conf is None:
+            if boot is None and not n_bins and conf is None and ordm is None:
                 return self._result(RiskCoverage.unpack(packed.cpu(), cs))
             groups = build_groups(self.keys)[:2] if bootstrap and unit == "cine" else None
             parts = [packed]
+            rep = None
             if boot is not None:
-                parts.append(boot.replicates(probs, labels, u, groups, bootstrap, seed).stats.flatten())
+                rep = boot.replicates(probs, labels, u, groups, bootstrap, seed)
+                parts.append(rep.stats.flatten())
             if n_bins:
                 parts += self._calibration_parts(cal, probs, labels, u, groups, n_bins, bootstrap, seed)
             if conf is not None:
                 parts += self._conformal_parts(conf, conformal, probs, labels, u, conformal_mondrian, masks=False)
+            if ordm is not None:
+                parts += self._ordinal_parts(ordm, rep, probs, labels, groups, bootstrap, seed, ord_spec, ord_sens, ord_fit, ord_pts)
             host = torch.cat(parts).cpu()  # the one read
             res = self._result(RiskCoverage.unpack(host[: packed.numel()], cs))
+            ord_ci = None
+            if ordm is not None:
+                host, ord_ci = self._add_ordinal(res, host, ordm, K, bootstrap, ord_spec, ord_sens, ord_fit, ord_pts, confidence)
             if conf is not None:
                 host = self._add_conformal(res, host, conf, conformal, conformal_mondrian, None)
             self._add_intervals(res, host[packed.numel():], boot, cal, n_bins, bootstrap, confidence)
+            if ord_ci:
+                res["ci"].update(ord_ci)
             return res
         offsets, rows, names = build_groups(self.keys)
         G = len(names)
@@ -341,15 +371,22 @@ class SelectiveEvaluator:
         auc, auc_k = roc_auc_ovr_weighted(p, gl, K, per_class=True)
         rc = risk_coverage(p, gl, gp.u_mean.float())
         tail = [gp.status.double(), cm.double(), auc.reshape(1), auc_k, gp.p_conf.flatten(), gp.u_mean, gl.double(), gp.counts.double(), pred.double()]
+        rep = None
         if boot is not None:  # the rows are the cine predictions: every row is its own unit
-            tail.append(boot.replicates(p, gl, gp.u_mean.float(), None, bootstrap, seed).stats.flatten())
+            rep = boot.replicates(p, gl, gp.u_mean.float(), None, bootstrap, seed)
+            tail.append(rep.stats.flatten())
         if n_bins:
             tail += self._calibration_parts(cal, p, gl, gp.u_mean.float(), None, n_bins, bootstrap, seed)
         if conf is not None:
             tail += self._conformal_parts(conf, conformal, p, gl, gp.u_mean.float(), conformal_mondrian, masks=True)
+        if ordm is not None:
+            tail += self._ordinal_parts(ordm, rep, p, gl, None, bootstrap, seed, ord_spec, ord_sens, ord_fit, ord_pts)
         host = torch.cat([rc.packed(cs)] + tail).cpu()  # the one read
         n_rc = 5 * len(cs) + 4
         res = self._result(RiskCoverage.unpack(host[:n_rc], cs))
+        ord_ci = None
+        if ordm is not None:
+            host, ord_ci = self._add_ordinal(res, host, ordm, K, bootstrap, ord_spec, ord_sens, ord_fit, ord_pts, confidence)
         masks = None
         if conf is not None:
             masks = host[host.numel() - len(conformal.alphas) * G:].view(len(conformal.alphas), G).long().tolist()
@@ -371,7 +408,35 @@ class SelectiveEvaluator:
                 for c, m in zip(res["cines"], row):
                     c[f"set@{alpha:g}"] = conf.mask_classes(m, K)
         self._add_intervals(res, t[o + G * K + 4 * G:], boot, cal, n_bins, bootstrap, confidence)
+        if ord_ci:
+            res["ci"].update(ord_ci)
         return res
+
+    @staticmethod
+    def _ordinal_parts(ordm, rep, probs, labels, groups, B: int, seed: int, spec, sens, fit, pts) -> List[torch.Tensor]:
+        """The device vectors ``ordinal=`` adds at the very END of the one read: the agreement statistics (of every replicate's
+        confusion matrix when the bootstrap ran: ``rep`` is its ``Replicates``) and the packed screening, on the same resamples."""
+        agr = ordm.agreement_of(rep.cm) if rep is not None else ordm.agreement(probs, labels)
+        scr = ordm.screen(probs, labels, spec, sens, groups, int(B), int(seed), fit, pts)
+        return [agr.stats.flatten(), scr.packed()]
+
+    @staticmethod
+    def _add_ordinal(res, host, ordm, K: int, B: int, spec, sens, fit, pts, confidence: float):
+        """Reads ``_ordinal_parts`` off the end of ``host``, adds ``res["ordinal"]`` and returns ``host`` without them and the
+        intervals that join ``res["ci"]`` (None without a bootstrap)."""
+        T, F = len(spec) + len(sens) + 1, (0 if fit is None else len(fit.kinds)) + len(pts)
+        n_s, n_a = ordm.Screening.packed_size(K, B, T, F), (B + 1 if B else 1) * 6
+        cut = host.numel() - n_s - n_a
+        agr = host[cut: cut + n_a].numpy().reshape(-1, 6)
+        scr = ordm.Screening.unpack(host[cut + n_a:].numpy(), K, B, spec, sens, fit, pts, confidence if B else None)
+        res["ordinal"] = {"agreement": ordm.Agreement.unpack(agr), "cuts": scr["cuts"]}
+        ci = None
+        if B:
+            from .bootstrap import intervals_of
+
+            ci = intervals_of(agr, confidence, names=ordm.AGREEMENT_NAMES)
+            ci.update(scr["ci"])
+        return host[:cut], ci
 
     @staticmethod
     def _conformal_parts(conf, fit, probs, labels, u, mondrian: bool, masks: bool) -> List[torch.Tensor]:

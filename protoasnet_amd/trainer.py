@@ -101,6 +101,7 @@ class DPTrainer:
         self.current_epoch, self.current_iteration, self.best_metric = 0, 0, 0.0
         self.temperature_fit = None  # calibration.TemperatureFit of the last fit_temperature()
         self.conformal_fit = None  # conformal.ConformalFit of the last fit_conformal()
+        self.operating_fit = None  # ordinal.OperatingFit of the last fit_operating_points()
         self.ood_fit = None  # ood.OODFit of the last fit_ood(), with its detector, level and thresholds
         self.num_real_classes = model.num_classes - 1 if config.get("abstain_class") else model.num_classes
         self.get_criterion()
@@ -477,7 +478,8 @@ class DPTrainer:
 
     def evaluate_selective(self, mode: str = "test", level: str = "cine", coverages=(1.0, 0.9, 0.8, 0.7, 0.5), score: str = "auto",
                            bootstrap: int = 0, seed: int = 0, confidence: float = 0.95, unit: str = "cine", calibration: int = 0,
-                           temperature=None, conformal=None, conformal_mondrian: bool = False) -> Dict[str, object]:
+                           temperature=None, conformal=None, conformal_mondrian: bool = False, ordinal=None,
+                           ordinal_net_benefit_at=()) -> Dict[str, object]:
         """Selective-prediction metrics of ``data_loaders[mode]`` (``protoasnet_amd.selective``): an eval-mode, forward-only sweep (no
         loss; the ``staged`` / ``prepare_input`` path of ``run_epoch``), the clips grouped by ``sample["filename"]`` -- with
         ``iterate_intervals`` every cardiac cycle of a cine is a row of its own -- and ``SelectiveEvaluator.finish(coverages, level)``'s
@@ -494,7 +496,11 @@ class DPTrainer:
         ``"fitted"``: what ``fit_conformal`` left in ``self.conformal_fit`` -- adds ``res["conformal"]`` (prediction sets of the level's
         rows: coverage, set sizes, per-class and size-stratified coverage, mean uncertainty by set size; ``conformal_mondrian``: each
         class its own threshold) and, at cine level, ``"set@<alpha>"`` to every cine; with ``save_dir`` also
-        ``save_dir/conformal_<mode>.csv``, one row per alpha.
+        ``save_dir/conformal_<mode>.csv``, one row per alpha.  ``ordinal`` -- ``True``, an ``ordinal.OperatingFit`` or ``"fitted"``: what
+        ``fit_operating_points`` left in ``self.operating_fit`` -- adds ``res["ordinal"]`` (``protoasnet_amd.ordinal``: the agreement
+        statistics that use the order of the grades, and every cut ``grade >= c`` as a screening test: AUC, average precision,
+        operating points; a fit's thresholds applied unchanged under ``"fitted"``; ``ordinal_net_benefit_at``: net benefit at those
+        threshold probabilities), with ``bootstrap`` also their intervals in ``res["ci"]``.
 
         It issues NO collectives: each rank that calls it sweeps the loader it was given and reports on those rows alone (call it on one
         rank with the full loader, or on every rank for per-shard figures; ranks need not call it together).  The model is left in the
@@ -511,7 +517,15 @@ class DPTrainer:
             if self.conformal_fit is None:
                 raise ValueError("conformal='fitted' needs fit_conformal() first")
             conformal = self.conformal_fit
+        if isinstance(ordinal, str):
+            if ordinal != "fitted":
+                raise ValueError(f"ordinal must be True, an OperatingFit, 'fitted' or None, got {ordinal!r}")
+            if self.operating_fit is None:
+                raise ValueError("ordinal='fitted' needs fit_operating_points() first")
+            ordinal = self.operating_fit
         extra = {} if conformal is None else {"conformal": conformal, "conformal_mondrian": conformal_mondrian}  # (None: the call as it was)
+        if ordinal is not None:
+            extra.update(ordinal=ordinal, ordinal_net_benefit_at=ordinal_net_benefit_at)
         res = self._selective_sweep(mode, score).finish(coverages, level, bootstrap=bootstrap, seed=seed, confidence=confidence, unit=unit,
                                                         calibration=calibration, temperature=temperature, **extra)
         self.log(f"Epoch: {self.current_epoch} | {mode} | selective ({level}) | AURC {res['aurc']:.4f} | error AUROC {res['error_auroc']:.4f}")
@@ -549,6 +563,11 @@ class DPTrainer:
                         w.writerow([repr(lv["alpha"]), c["kind"], int(c["mondrian"]), level, repr(q), lv["rows"]]
                                    + [repr(lv[k]) for k in ("coverage", "mean_size", "empty", "singleton", "singleton_accuracy",
                                                             "min_coverage_by_size")])
+        if ordinal is not None:
+            o = res["ordinal"]
+            self.log(f"Epoch: {self.current_epoch} | {mode} | ordinal ({level}) | MAE {o['agreement']['mae']:.4f} | under "
+                     f"{o['agreement']['under']:.4f} | over {o['agreement']['over']:.4f} | kappa(quadratic) {o['agreement']['kappa_quadratic']:.4f} | "
+                     + " | ".join(f"cut>={c['cut']}: AUC {c['auc']:.4f} AP {c['ap']:.4f}" for c in o["cuts"]))
         return res
 
     def _selective_sweep(self, mode: str, score: str = "auto"):
@@ -711,6 +730,51 @@ class DPTrainer:
         res = self.conformal_fit.read()
         self.log(f"Epoch: {self.current_epoch} | {mode} | conformal {kind} ({level}) | n {res['n']} | "
                  + " | ".join(f"alpha {a:g}: qhat {q:.6f}" for a, q in zip(res["alphas"], res["qhat"])))
+        return res
+
+    def fit_operating_points(self, mode: str = "val", level: str = "cine", specificities=(0.9,), sensitivities=(0.9,), temperature=None,
+                             score: str = "auto") -> Dict[str, object]:
+        """Screening thresholds fitted on ``data_loaders[mode]`` (``ordinal.fit_operating_points``; the forward-only sweep of
+        ``evaluate_selective``): per cut ``grade >= c`` the threshold that reaches each stated specificity and sensitivity, and
+        Youden's.  Keeps the device result in ``self.operating_fit`` -- ``evaluate_selective(ordinal="fitted")`` applies it unchanged
+        --, logs the thresholds and returns ``OperatingFit.read()``.  ``level="cine"`` (the default) fits on one row per cine,
+        ``p_conf.float()`` with the cine's label, exactly the rows ``evaluate_selective(level="cine")`` scores.  ``temperature`` as in
+        ``evaluate_selective`` (apply the same one there).  No collectives; the model is left in the mode it was in; no training or
+        epoch state is touched."""
+        from . import calibration, ordinal, selective
+
+        if level not in ("clip", "cine"):
+            raise ValueError(f"level must be 'clip' or 'cine', got {level!r}")
+        spec, sens = ordinal.check_targets(specificities, "specificities"), ordinal.check_targets(sensitivities, "sensitivities")
+        if isinstance(temperature, str):
+            if temperature != "fitted":
+                raise ValueError(f"temperature must be a number, a TemperatureFit or 'fitted', got {temperature!r}")
+            if self.temperature_fit is None:
+                raise ValueError("temperature='fitted' needs fit_temperature() first")
+            temperature = self.temperature_fit
+        if temperature is not None:
+            calibration._check_temperature(temperature)
+        sel = self._selective_sweep(mode, score)
+        ev = sel.ev
+        if ev.rows == 0:
+            raise ValueError("no rows: the loader is empty")
+        logits, probs, labels = ev.logits[: ev.rows], ev.probs[: ev.rows], ev.labels[: ev.rows]
+        # the rows SelectiveEvaluator.finish scores, by the calls it makes
+        if temperature is None:
+            u = selective.uncertainty(logits, sel.abstain, sel.score, sel.ab_logitpath)
+        elif selective.score_mode(sel.abstain, sel.score, sel.ab_logitpath) == selective.MAXPROB:
+            probs, u = calibration.scaled_probs(logits, ev.K_real, temperature, with_u=True)
+        else:
+            probs = calibration.scaled_probs(logits, ev.K_real, temperature)
+            u = selective.uncertainty(logits, sel.abstain, sel.score, sel.ab_logitpath)
+        if level == "cine":
+            gp = selective.group_predictions(probs, u, labels, selective.build_groups(sel.keys)[:2])
+            probs, labels = gp.p_conf.float(), gp.labels
+        self.operating_fit = ordinal.fit_operating_points(probs, labels, spec, sens)
+        res = self.operating_fit.read()
+        self.log(f"Epoch: {self.current_epoch} | {mode} | operating points ({level}) | "
+                 + " | ".join(f"cut>={c + 1}: " + ", ".join(f"{k}{'' if t is None else f'={t:g}'} {th:.6f}" for k, t, th in zip(res["kinds"], res["targets"], row))
+                              for c, row in enumerate(res["thresholds"])))
         return res
 
     def evaluate_faithfulness(self, mode: str = "val", steps: int = 10, select: int = 1, max_clips: Optional[int] = None,
